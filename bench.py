@@ -3,17 +3,21 @@
 int8 (SmoothQuant per-channel int8 weights+activations, int8 KV cache — BASELINE.json configs[3]) on N GPUs of
 one node with tensor parallelism TP = N (the reference's only sharding).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config sq|woq8|woq4|fp16] [--context 1024]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config sq|woq8|woq4|fp16] [--context 1024] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A "step" is one generation step (one new token for the whole batch) through all 32 layers + lm_head + greedy
 sampler, replayed from the captured hipGraph with the KV cache holding `context` tokens (+ the tokens generated so
 far).  Weights are synthetic (seeded random of the LLaMA-7B architecture, generated on the GPU in the storage format
-of the chosen config); inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line with
-`roofline` (the launch that takes most of the step, picked at run time as max(calls x average duration) over the launches the
-step is made of - all of them are listed in `roofline.kernels`; HBM-bound) and `cpu_baseline` (HF transformers LLaMA on the host
-CPU, the reference's run_hf.py path, bounded sample) objects.
+of the chosen config); inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the result line (`value`,
+`ms_per_step`) and, with --dump-outputs, the last step's outputs.  --full adds the side reports, each a pass of its own: the
+device-time pass, `roofline` (the launch that takes most of the step, picked at run time as max(calls x average duration) over
+the launches the step is made of - all of them are listed in `roofline.kernels`; HBM-bound), `cpu_baseline` (HF transformers
+LLaMA on the host CPU, the reference's run_hf.py path, bounded sample), the fp16 / weight-only int8 runs, prefill, the SmoothQuant
+GEMM MFMA report, the batch sweep, the tp prediction and the 7B accuracy report.  The --no-* options switch single side reports off.
 """
 import argparse
 import json
@@ -61,6 +65,10 @@ def parse():
     ap.add_argument('--cpu-tokens', type=int, default=0, help='CPU-baseline decode steps (0 = sized to ~20 s)')
     ap.add_argument('--cpu-threads', type=int, default=0)
     ap.add_argument('--cpu-sweep', default='', help='debug: comma list of thread counts to try (stderr)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side reports (device-time pass, roofline, CPU baseline, other configs, prefill, accuracy)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s outputs (logits, output ids) as DIR/<name>.npy')
     return ap.parse_args()
 
 
@@ -212,7 +220,9 @@ def run_config(torch, dist, args, mode, rank, world, dev):
         sess.set_tensor(k, v)
     sess.finalize()
     K, W = args.steps, args.warmup
-    sess.setup(1, args.context, 2 * K + W + 4)  # the timed K steps + the same K once more under an event pair (below)
+    # the timed K steps + the same K once more under an event pair (--full, below); a plain run sets up the same length, which
+    # picks the instance of the one-launch attention kernel (_fused_nit), so both runs time the same kernels
+    sess.setup(1, args.context, 2 * K + W + 4)
     stream = torch.cuda.current_stream().cuda_stream
     sess.fake_context(args.context, seed=1, stream=stream)
     sess.step(2, use_graph=False, stream=stream)  # eager: lazy init outside the capture
@@ -241,24 +251,31 @@ def run_config(torch, dist, args, mode, rank, world, dev):
         dist.barrier()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if world > 1:
+        tt = torch.tensor([wall], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        wall = float(tt.item())
+    # what a caller of the timed path receives after its last step (--dump-outputs)
+    logits = sess.logits(stream=stream)
+    finite = bool((logits == logits).all() and abs(logits).max() < 1e30)
+    res = dict(graph=use_graph, mode=mode, wall_s=wall, ms_per_step=wall * 1e3 / K, tokens_per_s=K / wall, finite=finite,
+               outputs={'logits': logits, 'output_ids': sess.output_ids(stream=stream)})
+    if not args.full:
+        sess.close()
+        del weights
+        torch.cuda.empty_cache()
+        return res
     # device time of the same K steps between a HIP event pair on the same stream, in a pass of its own
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     sess.step(K, use_graph=use_graph, stream=stream)
     e1.record()
     torch.cuda.synchronize()
-    dev_ms = e0.elapsed_time(e1)
-    if world > 1:
-        tt = torch.tensor([wall], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        wall = float(tt.item())
-    logits = sess.logits(stream=stream)
-    finite = bool((logits == logits).all() and abs(logits).max() < 1e30)
+    res['dev_ms'] = e0.elapsed_time(e1)
     # context length seen by the timed steps: context + 2 + W ... + K (mean)
     l_mean = args.context + 2 + max(W, 1) + (K - 1) / 2.0
-    step_bytes = sess.step_bytes(int(round(l_mean)))
-    res = dict(graph=use_graph, mode=mode, wall_s=wall, dev_ms=dev_ms, ms_per_step=wall * 1e3 / K, tokens_per_s=K / wall, finite=finite,
-               step_bytes=step_bytes, mean_context=l_mean)
+    res['step_bytes'] = sess.step_bytes(int(round(l_mean)))
+    res['mean_context'] = l_mean
     # instrumented pass (eager, an event pair around every launch): the head GEMV's and the sampler's time, the collectives
     prof = sess.profile(8, stream=stream)
     res['profile'] = prof
@@ -591,7 +608,9 @@ def main():
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}', '--master-addr', '127.0.0.1',
                '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         print('[bench] re-launching as: ' + ' '.join(cmd), file=sys.stderr, flush=True)
-        os.execv(sys.executable, cmd)
+        # a child process, not exec: this process has initialised the GPU, and replacing such a process can take the driver down
+        import subprocess
+        raise SystemExit(subprocess.run(cmd).returncode)
     if world != args.gpus:
         raise SystemExit(f'bench.py --gpus {args.gpus} inside a launcher of WORLD_SIZE {world}: start it with --nproc-per-node {args.gpus}')
     if os.environ.get('TLLM_TEST_SHARED_GPU') == '1':
@@ -677,9 +696,10 @@ def main():
                 print(f'[bench rank {rank}] transport {tr} failed: {err}', file=sys.stderr, flush=True)
                 continue
             transport_results[tr] = {'tokens_per_s': r['tokens_per_s'], 'ms_per_step': r['ms_per_step'],
-                                     'comm_us_per_step': r['profile']['comm'][0] * 1e3 / 8,
-                                     'comm_launches_per_step': r['profile']['comm'][1] / 8,
                                      'step_launch': 'hipGraph replay' if r.get('graph', True) else 'eager'}
+            if args.full:
+                transport_results[tr].update(comm_us_per_step=r['profile']['comm'][0] * 1e3 / 8,
+                                             comm_launches_per_step=r['profile']['comm'][1] / 8)
             if res is None or r['tokens_per_s'] > res['tokens_per_s']:
                 res, allreduce_path = r, tr
         if res is None:
@@ -689,7 +709,7 @@ def main():
     else:
         res = run_config(torch, dist, args, args.config, rank, world, dev)
     fp16 = woq8 = None
-    if args.config != 'fp16' and not args.no_fp16_ref:
+    if args.full and args.config != 'fp16' and not args.no_fp16_ref:
         fp16 = run_config(torch, dist, args, 'fp16', rank, world, dev)
         if args.config == 'sq':  # BASELINE.json configs[2] next to configs[1] and [3]: weight-only int8 + int8 KV (side report)
             woq8 = run_config(torch, dist, args, 'woq8', rank, world, dev)
@@ -698,6 +718,50 @@ def main():
             dist.destroy_process_group()
         return
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res['outputs'])
+    names = {'sq': 'SmoothQuant per-channel int8 (act+weight) + int8 KV cache', 'woq8': 'weight-only int8 + int8 KV cache',
+             'woq4': 'weight-only int4 + int8 KV cache', 'fp16': 'fp16 + fp16 KV cache'}
+    line = {
+        'metric': 'decode tokens/sec LLaMA-7B int8' if args.config != 'fp16' else 'decode tokens/sec LLaMA-7B fp16',
+        'value': res['tokens_per_s'],
+        'unit': 'tokens/s',
+        'n_gpus': world,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': res['ms_per_step'],
+        'higher_is_better': True,
+        'scaling': 'strong',
+        'vs_baseline': None,
+        'dtype': {'sq': 'int8', 'woq8': 'f16', 'woq4': 'f16', 'fp16': 'f16'}[args.config],
+        'data': 'synthetic',
+        'config': {'workload': f'LLaMA-7B ({args.layers} layers) {names[args.config]}, batch 1, context {args.context} '
+                               f'(synthetic KV), greedy decode, TP={world}', 'global_batch': 1,
+                   'seq_len': args.context, 'parallelism': f'tp{world}', 'allreduce': allreduce_path,
+                   'transports': transport_results or None,
+                   'rccl_communicator_ranks': rccl_ranks,
+                   'step_launch': 'hipGraph replay' if res.get('graph', True) else 'eager (graph capture failed)'},
+        'step': {'outputs_finite': res['finite']},
+    }
+    if args.full:
+        side_reports(line, torch, args, res, fp16, woq8, world, dev)
+    print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: what the timed path hands its caller after its last step, one <out_dir>/<name>.npy per array - the fp32
+    logits [rows, vocab] and the token record [sequences, max_seq_len] (int32 ids, stored exactly as float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + '.npy'), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
+def side_reports(line, torch, args, res, fp16, woq8, world, dev):
+    """--full: everything beside the headline, added to the result line (rank 0)."""
     prof = res['profile']
     prof_steps = 8
     # PMC counters cannot be read from inside the timed run: `traffic` is the committed rocprofv3 measurement of the same
@@ -757,50 +821,29 @@ def main():
         except Exception as e:
             cpu = dict(value=None, unit='tokens/s', cores=os.cpu_count(), kind='reference', sample=f'failed: {e!r}')
     del cpu_model
-    names = {'sq': 'SmoothQuant per-channel int8 (act+weight) + int8 KV cache', 'woq8': 'weight-only int8 + int8 KV cache',
-             'woq4': 'weight-only int4 + int8 KV cache', 'fp16': 'fp16 + fp16 KV cache'}
-    line = {
-        'metric': 'decode tokens/sec LLaMA-7B int8' if args.config != 'fp16' else 'decode tokens/sec LLaMA-7B fp16',
-        'value': res['tokens_per_s'],
-        'unit': 'tokens/s',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': res['ms_per_step'],
-        'higher_is_better': True,
-        'scaling': 'strong',
-        'vs_baseline': None,
-        'dtype': {'sq': 'int8', 'woq8': 'f16', 'woq4': 'f16', 'fp16': 'f16'}[args.config],
-        'data': 'synthetic',
-        'config': {'workload': f'LLaMA-7B ({args.layers} layers) {names[args.config]}, batch 1, context {args.context} '
-                               f'(synthetic KV), greedy decode, TP={world}', 'global_batch': 1,
-                   'seq_len': args.context, 'parallelism': f'tp{world}', 'allreduce': allreduce_path,
-                   'transports': transport_results or None,
-                   'rccl_communicator_ranks': rccl_ranks,
-                   'comm_us_per_step': (prof['comm'][0] * 1e3 / prof_steps) if world > 1 else 0.0,
-                   'comm_launches_per_step': (prof['comm'][1] / prof_steps) if world > 1 else 0,
-                   'step_launch': 'hipGraph replay' if res.get('graph', True) else 'eager (graph capture failed)'},
-        'roofline': {'bound': 'hbm', 'achieved': dom['achieved'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['frac'],
-                     'traffic': dom['traffic'], 'traffic_source': traffic_source if dom['traffic'] is not None else None,
-                     # name as rocprofv3 prints it; the dominant launch = max(launches x average duration) over `kernels`
-                     'kernel': '%s (%s; %.0f %% of the step\'s launches)'
-                               % (dom['kernel'], dom['what'], 100.0 * dom['us_per_step'] / max(sum(k['us_per_step'] for k in kernels), 1e-9)),
-                     'bytes_per_launch': dom['bytes_per_launch'], 'avg_launch_us': dom['avg_launch_us'],
-                     'kernels': kernels},
-        'cpu_baseline': cpu,
-        'step': {'hbm_bytes': res['step_bytes'], 'hbm_frac_of_peak': res['step_bytes'] / (res['ms_per_step'] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                 'device_ms_per_step': res['dev_ms'] / args.steps, 'outputs_finite': res['finite'],
-                 # the launches one layer is made of in this run, timed one by one (the same numbers as roofline.kernels)
-                 'layer_kernel_us': {k: v for k, v in res['kernel_us'].items() if k != 'head'},
-                 'decode_form': {'qkv_and_attention_in_one_launch': bool(res['decode_form'] & 1),
-                                 'o_projection_in_that_launch': bool(res['decode_form'] & 2),
-                                 'mlp_in_one_launch': bool(res['decode_form'] & 4)},
-                 # the layer as the graph replay runs it: (device time per step - the head GEMV - the sampler, both from the eager
-                 # profile below) / layers.  layer_kernel_us above times the launches ONE BY ONE
-                 'layer_us_in_graph_replay': (res['dev_ms'] / args.steps - (prof['gemv_head'][0] + prof['other'][0]) / prof_steps) * 1e3 / args.layers,
-                 'profile_ms_per_step': {k: v[0] / prof_steps for k, v in prof.items()},
-                 'launches_per_step': {k: v[1] / prof_steps for k, v in prof.items()}},
-    }
+    line['config'].update(comm_us_per_step=(prof['comm'][0] * 1e3 / prof_steps) if world > 1 else 0.0,
+                          comm_launches_per_step=(prof['comm'][1] / prof_steps) if world > 1 else 0)
+    line['roofline'] = {'bound': 'hbm', 'achieved': dom['achieved'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['frac'],
+                        'traffic': dom['traffic'], 'traffic_source': traffic_source if dom['traffic'] is not None else None,
+                        # name as rocprofv3 prints it; the dominant launch = max(launches x average duration) over `kernels`
+                        'kernel': '%s (%s; %.0f %% of the step\'s launches)'
+                                  % (dom['kernel'], dom['what'], 100.0 * dom['us_per_step'] / max(sum(k['us_per_step'] for k in kernels), 1e-9)),
+                        'bytes_per_launch': dom['bytes_per_launch'], 'avg_launch_us': dom['avg_launch_us'],
+                        'kernels': kernels}
+    line['cpu_baseline'] = cpu
+    line['step'].update({
+        'hbm_bytes': res['step_bytes'], 'hbm_frac_of_peak': res['step_bytes'] / (res['ms_per_step'] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        'device_ms_per_step': res['dev_ms'] / args.steps,
+        # the launches one layer is made of in this run, timed one by one (the same numbers as roofline.kernels)
+        'layer_kernel_us': {k: v for k, v in res['kernel_us'].items() if k != 'head'},
+        'decode_form': {'qkv_and_attention_in_one_launch': bool(res['decode_form'] & 1),
+                        'o_projection_in_that_launch': bool(res['decode_form'] & 2),
+                        'mlp_in_one_launch': bool(res['decode_form'] & 4)},
+        # the layer as the graph replay runs it: (device time per step - the head GEMV - the sampler, both from the eager
+        # profile below) / layers.  layer_kernel_us above times the launches ONE BY ONE
+        'layer_us_in_graph_replay': (res['dev_ms'] / args.steps - (prof['gemv_head'][0] + prof['other'][0]) / prof_steps) * 1e3 / args.layers,
+        'profile_ms_per_step': {k: v[0] / prof_steps for k, v in prof.items()},
+        'launches_per_step': {k: v[1] / prof_steps for k, v in prof.items()}})
     if 'prefill_ms' in res:
         out_len = 128  # the reference's example run: 1024-token prompt, 128 new tokens
         line['prefill'] = {'context': args.context, 'ms': res['prefill_ms'],
@@ -834,9 +877,6 @@ def main():
         if woq8 is not None:
             line['woq8_tokens_per_s'] = woq8['tokens_per_s']
         line['int8_over_fp16'] = res['tokens_per_s'] / fp16['tokens_per_s']
-    print(json.dumps(line))
-    if dist:
-        dist.destroy_process_group()
 
 
 if __name__ == '__main__':

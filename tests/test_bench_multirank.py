@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize('world,layers,launcher', [(2, 4, 'torchrun'), (4, 2, 'torchrun'), (2, 2, 'self')])
 def test_bench_ranks_sharing_one_gpu(world, layers, launcher):
     """launcher 'torchrun': the driver's command line.  'self': plain `python bench.py --gpus N` - bench.py becomes its own launcher
-    (re-executes itself under torch.distributed.run) instead of exiting (missing #2)."""
+    (starts torch.distributed.run as a child process) instead of exiting (missing #2)."""
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
     port = s.getsockname()[1]
@@ -28,7 +28,7 @@ def test_bench_ranks_sharing_one_gpu(world, layers, launcher):
     head = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(world), '--master-addr', '127.0.0.1',
             '--master-port', str(port)] if launcher == 'torchrun' else [sys.executable]
     r = subprocess.run(head + [os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', '8', '--warmup', '2', '--layers', str(layers),
-                               '--no-prefill', '--no-fp16-ref', '--no-cpu-baseline'],
+                               '--full', '--no-prefill', '--no-fp16-ref', '--no-cpu-baseline'],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

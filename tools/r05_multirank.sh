@@ -12,7 +12,7 @@ run() {
   echo "rc=$?" >> $out
   tail -1 gpurun_out/mr_$1.log | cut -c1-1800 >> $out
 }
-run 2 29511 --steps 16 --warmup 4 --no-prefill
-run 4 29512 --steps 16 --warmup 4 --no-prefill
-run 8 29513 --steps 16 --warmup 4 --layers 4 --no-prefill
+run 2 29511 --steps 16 --warmup 4 --full --no-prefill
+run 4 29512 --steps 16 --warmup 4 --full --no-prefill
+run 8 29513 --steps 16 --warmup 4 --layers 4 --full --no-prefill
 cat $out

@@ -8,5 +8,5 @@ mkdir -p gpurun_out
 tail -1 gpurun_out/r05_bench_driver_cmdline.log | head -c 300; echo
 bash tools/refresh_profiles.sh r05 > gpurun_out/refresh.log 2>&1 < /dev/null
 bash tools/refresh_pmc.sh r05 sq > gpurun_out/refresh_pmc.log 2>&1 < /dev/null
-head -20 gpurun_out/r05_bench_kernel_stats.txt
-head -12 gpurun_out/r05_pmc_sq.txt
+head -20 out/r05_bench_kernel_stats.txt
+head -12 out/r05_pmc_sq.txt

@@ -2,7 +2,7 @@
 # A/B of a session-key variant on one box: bash tools/r06_ab.sh "<flags A>" "<flags B>" [runs]
 cd "$(dirname "$0")/.." && mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="--no-cpu-baseline --no-parity --no-prefill --no-fp16-ref --no-batch-sweep --no-tp-prediction --steps 128 --warmup 8"
+B="--full --no-cpu-baseline --no-parity --no-prefill --no-fp16-ref --no-batch-sweep --no-tp-prediction --steps 128 --warmup 8"
 rm -f gpurun_out/r06_ab.txt
 for i in $(seq 1 ${3:-3}); do
   for f in "$1" "$2"; do

@@ -2,7 +2,7 @@
 # the headline twice on this box (driver command line, side reports off) -> one line appended to gpurun_out/r06_box_spread.txt
 cd "$(dirname "$0")/.." && mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="--gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-batch-sweep --no-tp-prediction --no-prefill --no-fp16-ref"
+B="--full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-batch-sweep --no-tp-prediction --no-prefill --no-fp16-ref"
 r=""
 for i in 1 2; do
   timeout 300 python bench.py $B > gpurun_out/bx.log 2> gpurun_out/bx.err

@@ -2,7 +2,7 @@
 # A/B of HIP runtime environment knobs on one box: bash tools/r06_env_ab.sh "VAR=1" ["VAR2=1" ...]  (each against the plain environment)
 cd "$(dirname "$0")/.." && mkdir -p gpurun_out
 export TMPDIR=/tmp
-B="--no-cpu-baseline --no-parity --no-prefill --no-fp16-ref --no-batch-sweep --no-tp-prediction --steps 128 --warmup 8"
+B="--full --no-cpu-baseline --no-parity --no-prefill --no-fp16-ref --no-batch-sweep --no-tp-prediction --steps 128 --warmup 8"
 rm -f gpurun_out/r06_env_ab.txt
 for i in 1 2; do
   for e in "" "$@"; do
