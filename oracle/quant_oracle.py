@@ -64,16 +64,20 @@ class _Linear:
         return O.sq_gemm(xq, self.w_i8, tok, self.per_channel_scale)
 
 
-def _forward(model, ids, lens, n_new, feed_ids=None, capture=None, taps=None, reference_rounding=False, start_caches=None):
+def _forward(model, ids, lens, n_new, feed_ids=None, capture=None, taps=None, reference_rounding=False, start_caches=None,
+             exact_kv_dequant=False):
     """Context step + n_new-1 generation steps.  Returns ([logits per step], greedy ids [B, n_new]).
-    `start_caches` (one [B, 2, H, S + n_new, Dh] array per layer, with `feed_ids`): the context step is skipped and generation
+    `start_caches` (one [B, 2, H, C, Dh] array per layer, with `feed_ids`): the context step is skipped and generation
     starts from these cache contents at length S - parity tests of the generation kernels at long contexts seed both sides with
-    the same cache bytes instead of running two prefills; logits[0] is then None.
+    the same cache bytes instead of running two prefills; logits[0] is then None.  The capacity C may exceed what the steps
+    use (a session set up for a long max_new_tokens budget): the caches are cut to the slots the n_new - 1 steps read and
+    write, C >= S + n_new - 1 (the last step may write the cache's last slot).
     `taps` (a dict) receives 'caches' (the per-layer KV caches, live objects: their state after the last step),
     'caches_after_context' (copies), 'attn_ctx' = [step][layer] attention output [B, H*Dh] of every generation step
     (the O-projection's input before its quantiser) and 'gemm_in' = [step][layer] dict(qkv_in, o_in, mlp_in, proj_in): the
     operand of each of the layer's four GEMMs in that generation step - int8 behind its quantiser for SmoothQuant
-    (K/quantization.cu:31-118), the fp16 activation otherwise.  `reference_rounding`: see llama_oracle.mmha_decode / woq_matmul."""
+    (K/quantization.cu:31-118), the fp16 activation otherwise.  `reference_rounding`, `exact_kv_dequant`: see
+    llama_oracle.mmha_decode / woq_matmul."""
     cfg = model['cfg']
     B, S = ids.shape
     H, D = cfg['num_heads'], cfg['hidden_size']
@@ -138,8 +142,9 @@ def _forward(model, ids, lens, n_new, feed_ids=None, capture=None, taps=None, re
 
     if start_caches is not None:
         assert feed_ids is not None and len(start_caches) == L
-        caches = [np.array(c, copy=True) for c in start_caches]
-        assert all(c.shape == (B, 2, H, smax, Dh) for c in caches)
+        used = S + n_new - 1  # slots 0 .. S + n_new - 2: the context and what the generation steps append
+        assert all(c.shape[:3] == (B, 2, H) and c.shape[4] == Dh and c.shape[3] >= used for c in start_caches)
+        caches = [np.array(c[:, :, :, :used], copy=True) for c in start_caches]
     # ---- context
     x = O.f16(model['emb'][ids]).reshape(B * S, D)
     valid = np.concatenate([np.arange(S) < lens[b] for b in range(B)])
@@ -174,7 +179,7 @@ def _forward(model, ids, lens, n_new, feed_ids=None, capture=None, taps=None, re
 
         def dec_attn(qkv, cache, lw):
             c = O.mmha_decode(qkv, cache, [tl] * B, lens, S, tl, H, Dh, Dh, True, 1.0, masked, lw.get('kv_oq'),
-                              lw.get('kv_qo'), reference_rounding=reference_rounding)
+                              lw.get('kv_qo'), reference_rounding=reference_rounding, exact_kv_dequant=exact_kv_dequant)
             if taps is not None:
                 taps['attn_ctx'][-1].append(c.copy())
             return c
@@ -203,13 +208,14 @@ def run_fp16_model(cfg, w, ids, lens, n_new, feed_ids=None):
     return _forward(_fp16_model(cfg, w), ids, lens, n_new, feed_ids)
 
 
-def run_model(qmodel, ids, lens, n_new, feed_ids=None, taps=None, reference_rounding=False, start_caches=None):
+def run_model(qmodel, ids, lens, n_new, feed_ids=None, taps=None, reference_rounding=False, start_caches=None, exact_kv_dequant=False):
     m = qmodel['oracle']
     for lw in m['layers']:
         for n in LINEARS:
             if lw[n].kind == 'woq':
                 lw[n].reference_rounding = reference_rounding
-    return _forward(m, ids, lens, n_new, feed_ids, taps=taps, reference_rounding=reference_rounding, start_caches=start_caches)
+    return _forward(m, ids, lens, n_new, feed_ids, taps=taps, reference_rounding=reference_rounding, start_caches=start_caches,
+                    exact_kv_dequant=exact_kv_dequant)
 
 
 def quantise_model(cfg, w, mode, int8_kv, calib_ids, calib_lens, alpha=0.5):

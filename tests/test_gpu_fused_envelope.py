@@ -62,20 +62,42 @@ def test_general_launches_at_batch_1_vs_oracle():
     run_cases('sq_static_pc', 1, [(49, 40), (2300, 2300)], one_launch=False)
 
 
-def run_cases(mode, int8_kv, shapes, one_launch):
-    cfg, qmodel = model(mode, int8_kv)
+def lsb_stats(got, want):
+    """signed int8 differences got - want pooled over a case: (worst |d|, fraction that differs, sum d, sqrt(sum d^2))"""
+    d = np.concatenate([(g.astype(np.int64) - w.astype(np.int64)).ravel() for g, w in zip(got, want)])
+    return int(np.abs(d).max()), float(np.mean(d != 0)), int(d.sum()), float(np.sqrt(float((d * d).sum())))
+
+
+def assert_unbiased(tag, name, stats):
+    """Flips at rounding boundaries are sign-symmetric, a biased quantiser is not: |sum d| <= 3 sqrt(sum d^2) + 3 over the steps
+    of a case (a systematic one-LSB bias fits inside the max / fraction bounds, not inside this one)"""
+    _, _, sd, rd = stats
+    assert abs(sd) <= 3 * rd + 3, (tag, name, 'signed LSB differences are biased', sd, rd)
+
+
+def run_cases(mode, int8_kv, shapes, one_launch, fuse_o=-1, built=None, exact_dequant=False):
+    """Per shape (max_input_len, length) - capacity max_input_len + STEPS + 1, STEPS steps - or (max_input_len, length, capacity,
+    steps, decode_form) (tests/fused_cases.py): one session, setup per shape, everything below against the oracle.  `built`:
+    (cfg, quantised model) instead of model(mode, int8_kv).  `exact_dequant`: the oracle reads the int8 cache without the
+    reference's fp16 rounding of every dequantised element, as the HIP kernels do (llama_oracle.kv_load).  Returns per shape the
+    taps, the appended cache rows, the logits and the tokens."""
+    cfg, qmodel = built or model(mode, int8_kv)
     sq = mode.startswith('sq')
     lw = qmodel['oracle']['layers'][0]
-    s = NativeSession(dict(cfg, quant_mode=qmodel['quant_mode'], debug_taps=1, fuse_qkv_attention=-1 if one_launch else 0))
+    s = NativeSession(dict(cfg, quant_mode=qmodel['quant_mode'], debug_taps=1, fuse_qkv_attention=-1 if one_launch else 0,
+                           fuse_o_projection=fuse_o))
     for k, v in qmodel['engine_tensors'].items():
         s.set_tensor(k, v)
     s.finalize()
     kv_dtype = np.int8 if int8_kv else np.float16
-    for S, length in shapes:
-        NEW = STEPS + 1
-        smax = S + NEW
-        s.setup(1, S, NEW)
-        if one_launch:
+    results = []
+    for shape in shapes:
+        S, length = shape[:2]
+        smax, steps, form = shape[2:] if len(shape) > 2 else (S + STEPS + 1, STEPS, None)
+        s.setup(1, S, smax - S)
+        if form is not None:
+            assert s.decode_form() == form, (mode, int8_kv, S, smax, 'decode form', s.decode_form(), 'expected', form)
+        elif one_launch:
             assert s.decode_form() & 1, 'this geometry must take the one-launch projection + attention'
             if mode == 'sq_static_pc' or mode == 'woq8':
                 assert s.decode_form() & 2, 'static SmoothQuant / weight-only int8: the O-projection stage must be on'
@@ -91,22 +113,26 @@ def run_cases(mode, int8_kv, shapes, one_launch):
         # relative 2^-11 per term that does not average out over a 3-token context
         vmax = max(1.0, float(np.abs(start[:, 1, :, :S].astype(np.float32)).max()) * (float(lw['kv_qo']) if int8_kv else 1.0))
         got_logits, got_taps = [], []
-        for i in range(STEPS):
+        for i in range(steps):
             s.step(1, use_graph=(i >= 2))
             got_logits.append(s.logits())
             got_taps.append({n: s.tap(0, n, {'qkv_in': D, 'o_in': D, 'mlp_in': D, 'proj_in': I}[n], quantised=sq)
                              for n in ('qkv_in', 'o_in', 'mlp_in', 'proj_in')})
         out = s.output_ids()
         end = read_cache(s, 0, (1, 2, H, smax, DH), kv_dtype)
-        # ---- oracle from the same cache bytes, fed the session's own tokens (step 0 consumes the synthetic context's token 3)
-        feed = np.concatenate([np.full((1, 1), 3, np.int32), out[:, S + 1:S + STEPS]], axis=1)
+        # ---- oracle from the same cache bytes, fed the session's own tokens (step 0 consumes the synthetic context's token 3);
+        # it runs the compared steps only and reads the slots they use (the token of a step that writes the last slot has no
+        # place in output_ids and is not needed)
+        feed = np.concatenate([np.full((1, 1), 3, np.int32), out[:, S + 1:S + steps]], axis=1)
         ids = np.full((1, S), 3, np.int32)
         lens = np.array([length], np.int32)
         taps = {}
-        ref, _ = QO.run_model(qmodel, ids, lens, NEW, feed_ids=feed, taps=taps, start_caches=[start])
+        ref, _ = QO.run_model(qmodel, ids, lens, steps + 1, feed_ids=feed, taps=taps, start_caches=[start], exact_kv_dequant=exact_dequant)
         scale = max(max(np.abs(r).max() for r in ref[1:]), 1.0)
-        for i in range(STEPS):
-            tag = f'[{mode} kv{"8" if int8_kv else "16"} S={S} len={length}] step {i}'
+        tag = f'[{mode}{"+o" if fuse_o > 0 else ""} kv{"8" if int8_kv else "16"} S={S} len={length} cap={smax}{" exact-dequant" if exact_dequant else ""}]'
+        ctx_err = 0.0
+        for i in range(steps):
+            stag = f'{tag} step {i}'
             oin = taps['gemm_in'][i][0]
             for n in ('qkv_in', 'o_in', 'mlp_in', 'proj_in'):
                 g, w_ = got_taps[i][n][0], oin[n][0]
@@ -119,10 +145,10 @@ def run_cases(mode, int8_kv, shapes, one_launch):
                     # 5 - 10 % of post_layernorm's quantiser step: more flips, never more than one LSB
                     # (proj_in: one fp16 ulp of silu(fc) * gate near its largest values spans two steps of the SwiGLU quantiser)
                     floor = dict(qkv_in=1.0, o_in=0.95, mlp_in=0.85, proj_in=0.85)[n]
-                    assert d.max() <= dict(qkv_in=0, o_in=1, mlp_in=1, proj_in=2)[n] and same >= floor, (tag, n, int(d.max()), same)
+                    assert d.max() <= dict(qkv_in=0, o_in=1, mlp_in=1, proj_in=2)[n] and same >= floor, (stag, n, int(d.max()), same)
                 else:
                     tol = dict(qkv_in=(1e-3, 1e-3), o_in=(2e-3 * vmax, 1e-3), mlp_in=(8e-3 * vmax, 4e-3), proj_in=(8e-3 * vmax, 8e-3))[n]
-                    np.testing.assert_allclose(g.astype(np.float32), w_.astype(np.float32), atol=tol[0], rtol=tol[1], err_msg=f'{tag} {n}')
+                    np.testing.assert_allclose(g.astype(np.float32), w_.astype(np.float32), atol=tol[0], rtol=tol[1], err_msg=f'{stag} {n}')
             # the attention context before the O-projection's quantiser
             octx = taps['attn_ctx'][i][0][0]
             if sq:
@@ -130,23 +156,38 @@ def run_cases(mode, int8_kv, shapes, one_launch):
                     oq = QO.O.quantize_per_token(octx[None])[0][0].astype(np.int32)
                 else:
                     oq = QO.O.quantize_tensor(octx, lw['attn_qscale']).astype(np.int32)
-                assert np.abs(got_taps[i]['o_in'][0].astype(np.int32) - oq).max() <= 1, tag
+                assert np.abs(got_taps[i]['o_in'][0].astype(np.int32) - oq).max() <= 1, stag
+            else:  # in fp16 ulps of the context's largest element
+                ulp = 2.0 ** (np.floor(np.log2(max(float(np.abs(octx).max()), 2.0 ** -14))) - 10)
+                ctx_err = max(ctx_err, float(np.abs(got_taps[i]['o_in'][0].astype(np.float64) - octx).max()) / ulp)
             dl = np.abs(got_logits[i] - ref[i + 1])
-            assert np.isfinite(got_logits[i]).all(), tag
-            np.testing.assert_allclose(got_logits[i], ref[i + 1], atol=(5e-2 if sq else 5e-3) * scale, err_msg=tag)
-            assert dl.mean() < (1.2e-2 if sq else 1e-3) * scale, (tag, float(dl.mean()))
-        # ---- the cache: nothing but slots S .. S + STEPS - 1 changed, and those hold what the oracle's quantiser stored
+            assert np.isfinite(got_logits[i]).all(), stag
+            np.testing.assert_allclose(got_logits[i], ref[i + 1], atol=(5e-2 if sq else 5e-3) * scale, err_msg=stag)
+            assert dl.mean() < (1.2e-2 if sq else 1e-3) * scale, (stag, float(dl.mean()))
+        # ---- the cache: nothing but slots S .. S + steps - 1 changed (every other slot of the capacity, the random bytes past the
+        # context included), and those hold what the oracle's quantiser stored
         ocache = taps['caches'][0]
         keep = np.ones(smax, bool)
-        keep[S:S + STEPS] = False
+        keep[S:S + steps] = False
         np.testing.assert_array_equal(end[:, :, :, keep], start[:, :, :, keep])
-        got = end[:, :, :, S:S + STEPS].astype(np.float32)
-        want = ocache[:, :, :, S:S + STEPS].astype(np.float32)
+        got = end[:, :, :, S:S + steps]
+        want = ocache[:, :, :, S:S + steps]
+        stats = {}
         if int8_kv:
-            d = np.abs(got - want)
-            assert d.max() <= 1 and np.mean(d == 0) > 0.97, (mode, S, float(d.max()), float(np.mean(d == 0)))
+            d = np.abs(got.astype(np.float32) - want.astype(np.float32))
+            assert d.max() <= 1 and np.mean(d == 0) > 0.97, (tag, float(d.max()), float(np.mean(d == 0)))
+            stats['kv'] = lsb_stats([got], [want])
         else:
-            np.testing.assert_allclose(got, want, atol=4e-3, rtol=4e-3)
-        print(f'[{mode} kv{"8" if int8_kv else "16"} S={S} len={length}] {STEPS} steps: operands, context, logits (max |d| '
-              f'{max(np.abs(got_logits[i] - ref[i + 1]).max() for i in range(STEPS)):.3g} of scale {scale:.3g}), appended cache rows OK')
+            np.testing.assert_allclose(got.astype(np.float32), want.astype(np.float32), atol=4e-3, rtol=4e-3)
+        if sq:
+            for n in ('o_in', 'mlp_in', 'proj_in'):
+                stats[n] = lsb_stats([got_taps[i][n][0] for i in range(steps)], [taps['gemm_in'][i][0][n][0] for i in range(steps)])
+        for n, st in stats.items():
+            assert_unbiased(tag, n, st)
+        lsb = ', '.join(f'{"o_in (context)" if n == "o_in" else n} max {a} LSB diff {b:.4f} sum {c:+d} (rms-bound {3 * r + 3:.0f})'
+                        for n, (a, b, c, r) in stats.items())
+        print(f'{tag} form {s.decode_form()} {steps} steps: logits max |d| {max(np.abs(got_logits[i] - ref[i + 1]).max() for i in range(steps)):.3g} '
+              f'of scale {scale:.3g}; {lsb}' + ('' if sq else f'; context max |d| {ctx_err:.2f} fp16 ulp'))
+        results.append(dict(taps=got_taps, cache=got.copy(), logits=got_logits, tokens=out[:, S + 1:S + steps].copy()))
     s.close()
+    return results
