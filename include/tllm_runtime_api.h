@@ -144,6 +144,44 @@ int32_t tllm_session_get_step_state(tllm_session_t s, int32_t* sequence_length, 
  * T/tests/model/test_llama.py:300-354).  Does not touch the KV cache or the step counters. */
 int32_t tllm_session_force_tokens(tllm_session_t s, const int32_t* ids, tllm_stream_t stream);
 
+/* Top-k / top-p sampling with temperature, repetition / presence penalty and minimum length, on the device inside the
+ * generation step (the reference's dynamic decoder with beam_width 1: PY/runtime/generation.py:299-345, 949-961 ->
+ * layers/baseSamplingLayer.cpp:171-248, layers/topKSamplingLayer.cu, K/samplingTopKKernels.cu, samplingTopPKernels.cu,
+ * samplingPenaltyKernels.cu).  The rule is stated in trtllm-llama_amd/csrc/kernels/kernels.h (SamplingParams) and restated in
+ * numpy in tensorrt_llm/runtime/sampling_ref.py.  The uniform variate of row b's generated token g is a function of
+ * (random_seed, b, g) alone (Philox4x32-10; the reference's cuRAND sequence is not reproduced) and the weights are summed as
+ * integers, so the tokens are a function of the prompt, the configuration and the seed: the same in every launch, process and
+ * tensor-parallel rank.  Defaults (the greedy configuration): top_k 1, top_p 0, temperature 1, repetition_penalty 1,
+ * presence_penalty 0, min_length 1, random_seed 0. */
+typedef struct
+{
+    int32_t top_k;            /* 0 = no top-k limit (top-p only); clipped to 1024 */
+    float top_p;              /* clipped to [0, 1]; 0 with top_k > 0 means 1, 0 with top_k == 0 means arg-max */
+    float temperature;        /* > 0 */
+    float repetition_penalty; /* > 0; 1 = off.  Mutually exclusive with presence_penalty */
+    float presence_penalty;   /* 0 = off */
+    int32_t min_length;       /* end_id cannot be drawn before this many tokens were generated */
+    uint64_t random_seed;
+} tllm_sampling_config_t;
+/* Valid after tllm_session_setup (which returns the session to greedy), beam_width 1 only (the reference's beam search ignores
+ * these fields too).  Call it between requests: it applies from the next sampler launch on, so the next tllm_session_context /
+ * tllm_session_generate runs under it as a whole.  The session does not track where a request driven through
+ * tllm_session_step ends and therefore does not refuse a call between a context and its steps; the remaining steps of that
+ * request then follow the new rule.  cfg == NULL returns to greedy.  A configuration that is plain arg-max (top_k 1,
+ * temperature 1, no penalty, min_length <= 1) keeps launching the greedy step.  Drops the captured step graph. */
+int32_t tllm_session_set_sampling(tllm_session_t s, const tllm_sampling_config_t* cfg);
+/* Kernel-level entry (parity tests, micro-benchmarks): one draw per row through the launcher the session uses.
+ *   logits         DEVICE f32 [nparts, rows, vocab_part] (vocabulary shards as the all-gather leaves them; id = part * vocab_part + i,
+ *                  ids >= vocab are padding);
+ *   history        DEVICE int32 [rows, history_stride] or NULL when cfg sets no penalty: slots [0, max_input_len) the padded
+ *                  prompt, of which [0, input_lengths[r]) are real (input_lengths DEVICE int32 [rows], NULL = all), behind them
+ *                  the g[r] - 1 tokens generated so far;
+ *   g              DEVICE int32 [rows]: number of the generated token drawn, 1-based;
+ *   out_ids        DEVICE int32 [rows];  u_out  optional DEVICE f32 [rows]: the uniform variate of each draw. */
+int32_t tllm_sample_tokens(const float* logits, int32_t nparts, int32_t rows, int32_t vocab_part, int32_t vocab,
+    const tllm_sampling_config_t* cfg, int32_t end_id, const int32_t* history, int32_t history_stride, const int32_t* input_lengths,
+    int32_t max_input_len, const int32_t* g, int32_t* out_ids, float* u_out, tllm_stream_t stream);
+
 /* Parity-test tap (sessions created with debug_taps=1 only): the input of layer `layer`'s O-projection GEMM as the last
  * generation step computed it - the attention context after the split-KV merge, [B, H/tp * Dh] fp16, or int8 when the
  * O-projection's prologue quantises it (SmoothQuant: sat(rni(ctx * attention.quantization_scaling_factor)), or the
@@ -177,7 +215,9 @@ int32_t tllm_session_time_kernel(tllm_session_t s, int32_t which, int32_t sweeps
     tllm_stream_t stream);
 
 /* Requests tllm_session_generate ran a SECOND time because a bounded in-launch wait of the one-launch projection + attention
- * expired (the session falls back to separate launches and repeats the request: greedy generation is a function of the prompt). */
+ * expired (the session falls back to separate launches and repeats the request: generation is a function of the prompt and,
+ * with sampling on, of the seed - the sampler's random numbers are counter-based and its sums are integer, so the repeat draws
+ * the same tokens). */
 int32_t tllm_session_fused_retries(tllm_session_t s);
 
 /* Which launches a generation step of this session is made of (decided at setup; a time-out of the one-launch form clears it):

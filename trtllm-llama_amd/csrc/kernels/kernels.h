@@ -433,6 +433,45 @@ struct GreedyParams
     uint32_t* step_epoch = nullptr; // optional device word, += 1 per call (tags of the in-launch hand-offs of the next step)
 };
 int launch_greedy_step(const GreedyParams& p, hipStream_t stream);
+
+// One top-k / top-p sampling step with temperature, penalties and minimum length (kernels/sampling.hip), the counterpart of
+// the reference's dynamic decoder with beam_width 1 (layers/baseSamplingLayer.cpp:171-248, layers/topKSamplingLayer.cu,
+// K/samplingTopKKernels.cu, K/samplingTopPKernels.cu, K/samplingPenaltyKernels.cu).  The rule, for row b producing generated
+// token number g (1-based; g = 1 is the token the prompt pass yields) from the raw fp32 logits x[v], v < vocab:
+//   1. temperature: y = x * (1 / (temperature + 1e-6f)) in fp32; skipped when temperature == 1.
+//   2. penalty, applied ONCE to every distinct id that occurs in the row's real prompt tokens [0, input_lengths[b]) or in its
+//      g - 1 generated tokens so far (padding slots [input_lengths[b], max_input_len) are skipped): repetition
+//      (y < 0 ? y * r : y / r, when repetition_penalty != 1) or else presence (y - r, when presence_penalty != 0).
+//   3. minimum length: y[end_id] = -FLT_MAX while g < min_length.  (NaN logits count as -inf, -0 as +0.)
+//   4. candidates: the ids ordered by (y descending, id ascending).  k' = top_k clipped to [1, 1024], or vocab when top_k == 0;
+//      p' = top_p clipped to [0, 1]; top_k == 0 && top_p == 0 -> k' = 1; top_k > 0 && top_p == 0 -> p' = 1.
+//   5. draw: w_i = exp(y_i - y_max) (0 for y_i = -inf, 1 for y_i = y_max) over the first k' ids of that order, S = sum w_i,
+//      target = u * p' * S; the token is the first i whose inclusive prefix sum reaches target, else the last of the k'.
+//      A row whose y are all -inf yields the first id of the order.
+//   6. the bookkeeping of launch_greedy_step (finished rows keep emitting end_id, finished |= id == end_id, out_ids, cur_ids,
+//      seq_len, next RoPE row and position, step_epoch, the next step's embedding row).
+// u in (0, 1] is a function of (random_seed, b, g) and nothing else: Philox4x32-10 (Salmon et al., SC'11) with key = (low, high
+// half of random_seed), counter = (b, g, 0, 0), u = ((word0 >> 8) + 1) * 2^-24.  No state is advanced by the host or by an
+// earlier launch, so a replayed graph needs no new arguments; the reference's cuRAND sequence is NOT reproduced.
+// The weights are accumulated as integers (w * 2^40, truncated): integer sums do not depend on the order of the LDS atomics,
+// so the same logits, history and (seed, b, g) give the same id in every launch, process and tensor-parallel rank.  What is
+// rounded away are ids of probability below 1e-12.  The logits are not modified in memory.
+struct SamplingParams
+{
+    GreedyParams g;             // logits, shapes and bookkeeping, exactly as the greedy step; g.out_ids may be NULL (no record)
+    const int32_t* history = nullptr; // int32 [batch, history_stride]: prompt slots [0, max_input_len), generated tokens behind;
+    int32_t history_stride = 0;       // the session passes out_ids.  May be NULL when no penalty is set.
+    int32_t g_base = 0;         // g = seq_len[b] + advance - g_base + 1 (the session: max_input_len)
+    int32_t top_k = 1;
+    float top_p = 0.f, temperature = 1.f, repetition_penalty = 1.f, presence_penalty = 0.f;
+    int32_t min_length = 1;
+    uint64_t random_seed = 0;
+    float* u_out = nullptr;     // optional f32 [batch]: the uniform variate of each row (tests)
+};
+int launch_sampling_step(const SamplingParams& p, hipStream_t stream);
+// true when the configuration is the plain arg-max the greedy step computes (top_k == 1, no penalty, min_length <= 1)
+bool sampling_is_greedy(const SamplingParams& p);
+
 // teacher forcing for parity tests: overwrite the sampler's last choice (output slot seq_len[b], step input id, next input row)
 int launch_force_token(const int32_t* ids_dev, int32_t* cur_ids, int32_t* out_ids, int32_t out_stride, const int32_t* seq_len,
     const void* emb, void* x, int32_t batch, int32_t hidden, int32_t vocab, hipStream_t stream);

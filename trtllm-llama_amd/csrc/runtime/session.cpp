@@ -243,6 +243,8 @@ struct tllm_session
     bool fused_timeline = false;
     void* ctx_q8 = nullptr;
     int end_id = -1;
+    bool sampling_on = false;       // tllm_session_set_sampling: run_sampler launches kernels/sampling.hip with `sampling`
+    SamplingParams sampling;        // configuration fields only; pointers and shapes are filled per launch
     hipGraphExec_t graph = nullptr;
     hipStream_t graph_stream = nullptr;
     uint64_t graph_comm_gen = 0;   // comm::p2p::generation() the step graph was captured under
@@ -866,6 +868,16 @@ struct tllm_session
             gp.emb_table = emb; // the sampler leaves the next step's input row in x (run_decode_step skips its embedding launch)
             gp.x_out = x;
             gp.hidden = hidden;
+        }
+        if (sampling_on && !sampling_is_greedy(sampling))
+        {
+            // same logits (gathered shards included), same bookkeeping; every tensor-parallel rank draws the same token
+            SamplingParams sp = sampling;
+            sp.g = gp;
+            sp.history = out_ids;
+            sp.history_stride = Smax;
+            sp.g_base = max_in;
+            return timed(PC_OTHER, st, [&] { return launch_sampling_step(sp, st) ? 1 : 0; });
         }
         return timed(PC_OTHER, st, [&] { return launch_greedy_step(gp, st) ? 1 : 0; });
     }
@@ -1538,6 +1550,7 @@ int32_t tllm_session_setup_beam(tllm_session_t s, int32_t batch_size, int32_t be
         return 1;
     }
     s->free_runtime();
+    s->sampling_on = false; // a sampling configuration is set per setup (tllm_session_set_sampling)
     s->Bc = batch_size;
     s->beam = beam_width;
     s->B = batch_size * beam_width;
@@ -1978,13 +1991,98 @@ int32_t tllm_session_generate(tllm_session_t s, const int32_t* input_ids, const 
     int32_t max_new_tokens, int32_t end_id, int32_t pad_id, int32_t* output_ids, tllm_stream_t stream)
 {
     // A bounded wait of the one-launch projection + attention expired (its grid was not resident at once - another queue's kernels
-    // held CUs): the session has fallen back to the two-launch path, the tokens behind the expired wait are invalid.  Greedy
-    // generation is a function of the prompt alone, every cache slot is rewritten before it is read: run the request again.
+    // held CUs): the session has fallen back to the two-launch path, the tokens behind the expired wait are invalid.  Generation
+    // is a function of the prompt and the seed alone - greedy trivially; the sampler draws u from a counter-based generator keyed
+    // by (seed, row, token number) and sums its weights as integers (kernels/sampling.hip), so it repeats bit for bit - and
+    // every cache slot is rewritten before it is read: run the request again.
     const int32_t rc = generate_once(s, input_ids, input_lengths, max_new_tokens, end_id, pad_id, output_ids, stream);
     if (rc != kFusedTimedOut)
         return rc;
     s->fused_retries += 1;
     return generate_once(s, input_ids, input_lengths, max_new_tokens, end_id, pad_id, output_ids, stream) ? 1 : 0;
+}
+
+static void sampling_from_config(SamplingParams& sp, const tllm_sampling_config_t& c)
+{
+    sp.top_k = c.top_k;
+    sp.top_p = c.top_p;
+    sp.temperature = c.temperature;
+    sp.repetition_penalty = c.repetition_penalty;
+    sp.presence_penalty = c.presence_penalty;
+    sp.min_length = c.min_length;
+    sp.random_seed = c.random_seed;
+}
+
+static int check_sampling_config(const char* who, const tllm_sampling_config_t& c)
+{
+    if (!(c.temperature > 0.f) || c.top_k < 0 || !(c.top_p >= 0.f) || !(c.repetition_penalty > 0.f))
+    {
+        set_error("%s: needs temperature > 0, top_k >= 0, top_p >= 0, repetition_penalty > 0", who);
+        return 1;
+    }
+    if (c.repetition_penalty != 1.f && c.presence_penalty != 0.f)
+    {
+        // layers/baseSamplingLayer.cpp:149-167
+        set_error("%s: repetition_penalty and presence_penalty are mutually exclusive", who);
+        return 1;
+    }
+    return 0;
+}
+
+int32_t tllm_session_set_sampling(tllm_session_t s, const tllm_sampling_config_t* cfg)
+{
+    if (!s || !s->B)
+    {
+        set_error("tllm_session_set_sampling: call tllm_session_setup first");
+        return 1;
+    }
+    if (cfg)
+    {
+        if (s->beam > 1)
+        {
+            set_error("tllm_session_set_sampling: beam_width 1 only (beam search does not sample)");
+            return 1;
+        }
+        RUN(check_sampling_config("tllm_session_set_sampling", *cfg));
+        sampling_from_config(s->sampling, *cfg);
+    }
+    s->sampling_on = cfg != nullptr;
+    if (s->graph)
+    {
+        // the configuration is baked into the captured sampler node, as end_id is
+        (void) hipGraphExecDestroy(s->graph);
+        s->graph = nullptr;
+    }
+    return 0;
+}
+
+int32_t tllm_sample_tokens(const float* logits, int32_t nparts, int32_t rows, int32_t vocab_part, int32_t vocab,
+    const tllm_sampling_config_t* cfg, int32_t end_id, const int32_t* history, int32_t history_stride, const int32_t* input_lengths,
+    int32_t max_input_len, const int32_t* g, int32_t* out_ids, float* u_out, tllm_stream_t stream)
+{
+    if (!logits || !cfg || !g || !out_ids || rows < 1 || max_input_len < 0)
+    {
+        set_error("tllm_sample_tokens: bad arguments");
+        return 1;
+    }
+    RUN(check_sampling_config("tllm_sample_tokens", *cfg));
+    SamplingParams sp;
+    sampling_from_config(sp, *cfg);
+    sp.g.logits = logits;
+    sp.g.batch = rows;
+    sp.g.vocab_part = vocab_part;
+    sp.g.nparts = nparts;
+    sp.g.vocab = vocab;
+    sp.g.cur_ids = out_ids;
+    sp.g.seq_len = const_cast<int32_t*>(g); // advance = 0: read only; with g_base = 1 the token number is g[r] itself
+    sp.g.end_id = end_id;
+    sp.g.input_lengths = input_lengths;
+    sp.g.max_input_len = max_input_len;
+    sp.g_base = 1;
+    sp.history = history;
+    sp.history_stride = history_stride;
+    sp.u_out = u_out;
+    return launch_sampling_step(sp, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
 int32_t tllm_session_fused_retries(tllm_session_t s)

@@ -35,6 +35,12 @@ def parse_arguments(args=None):
     p.add_argument('--output_csv', type=str, default=None)
     p.add_argument('--output_npy', type=str, default=None)
     p.add_argument('--num_beams', type=int, default=1)
+    # device-side sampling (num_beams 1); the defaults are greedy decoding
+    p.add_argument('--top_k', type=int, default=1)
+    p.add_argument('--top_p', type=float, default=0.0)
+    p.add_argument('--temperature', type=float, default=1.0)
+    p.add_argument('--repetition_penalty', type=float, default=1.0)
+    p.add_argument('--random_seed', type=int, default=None)
     p.add_argument('--num_runs', type=int, default=55)
     return p.parse_args(args)
 
@@ -66,10 +72,13 @@ def load_session(engine_dir):
 
 
 def generate(max_output_len, log_level='error', engine_dir='llama_outputs', input_text=None, input_file=None,
-             output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55):
+             output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55, top_k=1, top_p=0.0,
+             temperature=1.0, repetition_penalty=1.0, random_seed=None):
     tensorrt_llm.logger.set_level(log_level)
     decoder, runtime_rank = load_session(engine_dir)
-    sampling_config = SamplingConfig(end_id=EOS_TOKEN, pad_id=PAD_TOKEN, num_beams=num_beams)
+    sampling_config = SamplingConfig(end_id=EOS_TOKEN, pad_id=PAD_TOKEN, num_beams=num_beams, top_k=top_k, top_p=top_p,
+                                     temperature=temperature, repetition_penalty=repetition_penalty)
+    sampling_config.random_seed = random_seed
     tokenizer = None
     if input_file is None:
         from transformers import LlamaTokenizer

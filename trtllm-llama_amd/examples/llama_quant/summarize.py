@@ -220,8 +220,10 @@ def main(args):
             ids[i, :len(p)] = p  # right padding + input_lengths, as GenerationSession expects
         decoder.setup(len(batch), max_len, output_len)
         from tensorrt_llm.runtime import SamplingConfig
-        out = np.asarray(decoder.decode(ids, lens, SamplingConfig(end_id=end_id if args.stop_at_eos else -1, pad_id=pad_id,
-                                                                  num_beams=args.num_beams, top_k=args.top_k)))
+        scfg = SamplingConfig(end_id=end_id if args.stop_at_eos else -1, pad_id=pad_id, num_beams=args.num_beams, top_k=args.top_k,
+                              top_p=args.top_p, temperature=args.temperature, repetition_penalty=args.repetition_penalty)
+        scfg.random_seed = args.random_seed
+        out = np.asarray(decoder.decode(ids, lens, scfg))
         # every sequence continues right after its own last prompt token slot max_len (padded layout)
         return [out[i, 0, max_len:max_len + output_len] for i in range(len(batch))]
 
@@ -339,6 +341,10 @@ def parse_arguments(argv=None):
     parser.add_argument('--tensorrt_llm_rouge1_threshold', type=float, default=15.0)
     parser.add_argument('--num_beams', type=int, default=1)
     parser.add_argument('--top_k', type=int, default=1)
+    parser.add_argument('--top_p', type=float, default=0.0)
+    parser.add_argument('--temperature', type=float, default=1.0)
+    parser.add_argument('--repetition_penalty', type=float, default=1.0)
+    parser.add_argument('--random_seed', type=int, default=None)
     # additions for boxes without the dataset / tokenizer
     parser.add_argument('--prompts_npy', type=str, default=None, help='int token-id prompts [n, L] instead of cnn_dailymail')
     parser.add_argument('--prompt_lengths_npy', type=str, default=None, help='int lengths [n] of the (padded) --prompts_npy rows')

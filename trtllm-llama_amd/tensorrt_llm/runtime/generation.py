@@ -45,6 +45,8 @@ class SamplingConfig:
     min_length: int = field(default=1)
     presence_penalty: float = field(default=0.0)
     use_beam_hyps: bool = field(default=True)
+    # set after construction, as the reference (generation.py:136); None -> 0 (layers/baseSamplingLayer.cpp:119-123)
+    random_seed: int = field(init=False, default=None)
 
 
 class GenerationSession(object):
@@ -94,7 +96,9 @@ class GenerationSession(object):
                tasks=None, prompt_vocab_size=None):
         """input_ids: int32 [batch, max_input_length] (torch tensor or ndarray), padded with pad_id.
         Returns int32 [batch, num_beams, max_input_length + max_new_tokens] like the reference (generation.py:991-997):
-        greedy for num_beams == 1, beam search (hypotheses best first, back-tracked by gather_tree) otherwise."""
+        num_beams == 1: top-k / top-p sampling with temperature, penalties and min_length on the device (arg-max with the
+        default fields), reproducible for a fixed sampling_config.random_seed; beam search (hypotheses best first, back-tracked
+        by gather_tree) otherwise."""
         self._check_sampling_config(sampling_config)
         if sampling_config.num_beams != getattr(self, 'beam_width', 1):
             # the reference sizes its beam buffers inside decode() from scfg.num_beams (generation.py:365-411)
@@ -103,6 +107,8 @@ class GenerationSession(object):
         ids = input_ids.cpu().numpy() if is_torch else np.asarray(input_ids)
         lens = input_lengths.cpu().numpy() if hasattr(input_lengths, 'cpu') else np.asarray(input_lengths)
         assert ids.shape == (self.batch_size, self.max_input_length), 'call setup() with matching sizes first'
+        if sampling_config.num_beams == 1:
+            self.runtime.set_sampling(self._native_sampling(sampling_config))
         out = self.runtime.generate(ids.astype(np.int32), lens.astype(np.int32), self.max_new_tokens,
                                     end_id=sampling_config.end_id, pad_id=sampling_config.pad_id)
         out = out.reshape(self.batch_size, sampling_config.num_beams, -1)
@@ -112,27 +118,42 @@ class GenerationSession(object):
         return out
 
     @staticmethod
+    def _native_sampling(scfg: SamplingConfig) -> dict:
+        return dict(top_k=scfg.top_k, top_p=scfg.top_p, temperature=scfg.temperature,
+                    repetition_penalty=scfg.repetition_penalty, presence_penalty=scfg.presence_penalty,
+                    min_length=scfg.min_length, random_seed=scfg.random_seed or 0)
+
+    @staticmethod
     def _check_sampling_config(scfg: SamplingConfig):
         """Only what the device-side sampler honours is accepted; a field that would silently change nothing raises
         instead (the reference feeds all of them to DynamicDecodeOp, generation.py:300-345, 949-961).
-        Greedy (num_beams 1, top_k 1): temperature and top_p cannot change an arg-max and are accepted.
+        num_beams 1: top_k, top_p, temperature, one of repetition_penalty / presence_penalty, min_length and random_seed go
+        to the device sampler (csrc/kernels/sampling.hip).
         Beam search: hypotheses are ranked by the raw cumulative log-probability, as the reference's runtime does without
-        beam_hyps - so temperature must be 1; top_k / top_p play no part in the reference's beam search either."""
-        if scfg.num_beams == 1 and scfg.top_k != 1:
-            raise NotImplementedError('sampling (top_k > 1 / top_p) is not built: greedy or beam search only')
-        if scfg.num_beams == 1 and not scfg.temperature > 0:
-            raise ValueError('temperature must be positive')
+        beam_hyps - so temperature must be 1 and the penalties / min_length, which the beam step does not apply, raise;
+        top_k / top_p play no part in the reference's beam search either."""
+        if scfg.num_beams == 1:
+            if not scfg.temperature > 0:
+                raise ValueError('temperature must be positive')
+            if scfg.top_k < 0 or not scfg.top_p >= 0:
+                raise ValueError('top_k and top_p must not be negative')
+            if not scfg.repetition_penalty > 0:
+                raise ValueError('repetition_penalty must be positive')
+        if scfg.repetition_penalty != 1.0 and scfg.presence_penalty != 0.0:
+            # layers/baseSamplingLayer.cpp:149-167
+            raise ValueError('repetition_penalty and presence_penalty are mutually exclusive')
         bad = []
-        if scfg.repetition_penalty != 1.0:
-            bad.append(f'repetition_penalty={scfg.repetition_penalty}')
-        if scfg.presence_penalty != 0.0:
-            bad.append(f'presence_penalty={scfg.presence_penalty}')
-        if scfg.min_length > 1:
-            bad.append(f'min_length={scfg.min_length}')
-        if scfg.num_beams > 1 and scfg.temperature != 1.0:
-            bad.append(f'temperature={scfg.temperature} with beam search')
-        if scfg.num_beams > 1 and scfg.length_penalty != 1.0:
-            bad.append(f'length_penalty={scfg.length_penalty}')
+        if scfg.num_beams > 1:
+            if scfg.repetition_penalty != 1.0:
+                bad.append(f'repetition_penalty={scfg.repetition_penalty} with beam search')
+            if scfg.presence_penalty != 0.0:
+                bad.append(f'presence_penalty={scfg.presence_penalty} with beam search')
+            if scfg.min_length > 1:
+                bad.append(f'min_length={scfg.min_length} with beam search')
+            if scfg.temperature != 1.0:
+                bad.append(f'temperature={scfg.temperature} with beam search')
+            if scfg.length_penalty != 1.0:
+                bad.append(f'length_penalty={scfg.length_penalty}')
         if bad:
             raise NotImplementedError('SamplingConfig fields the device-side sampler does not honour: ' + ', '.join(bad))
 

@@ -79,8 +79,54 @@ def _lib():
     lib.tllm_session_decode_form.restype = c.c_int32
     lib.tllm_session_destroy.argtypes = [c.c_void_p]
     lib.tllm_session_destroy.restype = None
+    lib.tllm_session_set_sampling.argtypes = [c.c_void_p, c.POINTER(SamplingConfigC)]
+    lib.tllm_session_set_sampling.restype = c.c_int32
+    lib.tllm_sample_tokens.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.POINTER(SamplingConfigC),
+                                       c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
+                                       c.c_void_p, c.c_void_p]
+    lib.tllm_sample_tokens.restype = c.c_int32
     _bound = True
     return lib
+
+
+class SamplingConfigC(ctypes.Structure):
+    """tllm_sampling_config_t"""
+    _fields_ = [('top_k', ctypes.c_int32), ('top_p', ctypes.c_float), ('temperature', ctypes.c_float),
+                ('repetition_penalty', ctypes.c_float), ('presence_penalty', ctypes.c_float), ('min_length', ctypes.c_int32),
+                ('random_seed', ctypes.c_uint64)]
+
+
+def _sampling_config(top_k=1, top_p=0.0, temperature=1.0, repetition_penalty=1.0, presence_penalty=0.0, min_length=1,
+                     random_seed=0) -> SamplingConfigC:
+    return SamplingConfigC(int(top_k), float(top_p), float(temperature), float(repetition_penalty), float(presence_penalty),
+                           int(min_length), int(random_seed or 0) & 0xFFFFFFFFFFFFFFFF)
+
+
+def sample_tokens(logits, g, out_ids, *, vocab=None, end_id=-1, history=None, input_lengths=None, max_input_len=0, u_out=None,
+                  stream: int = 0, **config):
+    """tllm_sample_tokens on torch cuda tensors: logits f32 [rows, vocab] or [nparts, rows, vocab_part] (then `vocab` = the
+    real vocabulary size), g int32 [rows] (1-based number of the token drawn), out_ids int32 [rows]; history int32
+    [rows, stride] and input_lengths int32 [rows] as the header describes; u_out optional f32 [rows].  **config: the fields of
+    tllm_sampling_config_t.  Asynchronous on `stream`."""
+    import torch
+    if logits.dim() == 2:
+        logits = logits.unsqueeze(0)
+    nparts, rows, vpart = logits.shape
+    assert logits.is_cuda and logits.is_contiguous() and logits.dtype == torch.float32
+    for t, n in ((g, rows), (out_ids, rows), (input_lengths, rows), (u_out, rows)):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() == n)
+    for t in (g, out_ids, input_lengths, history):
+        assert t is None or t.dtype == torch.int32
+    assert u_out is None or u_out.dtype == torch.float32
+    stride = 0
+    if history is not None:
+        assert history.is_cuda and history.is_contiguous() and history.dim() == 2 and history.shape[0] == rows
+        stride = history.shape[1]
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    cfg = _sampling_config(**config)
+    _check(_lib().tllm_sample_tokens(logits.data_ptr(), nparts, rows, vpart, vocab or nparts * vpart, ctypes.byref(cfg), end_id,
+                                     ptr(history), stride, ptr(input_lengths), max_input_len, g.data_ptr(), out_ids.data_ptr(),
+                                     ptr(u_out), stream), 'sample_tokens')
 
 
 def _check(rc: int, what: str):
@@ -129,6 +175,19 @@ class NativeSession:
         """batch prompts x beam_width hypotheses (beam search when > 1, beam_width <= 8; beyond 8 sequences the generation GEMVs run in slabs of 8 rows)."""
         _check(_lib().tllm_session_setup_beam(self._h, batch, beam_width, max_input_len, max_new_tokens), 'setup')
         self.batch, self.max_in, self.max_new, self.beam = batch, max_input_len, max_new_tokens, beam_width
+
+    def set_sampling(self, config: Optional[Dict] = None, **fields):
+        """Top-k / top-p sampling for the requests that follow (after setup(), before context() / generate(); beam_width 1):
+        fields of tllm_sampling_config_t - top_k, top_p, temperature, repetition_penalty, presence_penalty, min_length,
+        random_seed - as a dict or keywords.  set_sampling(None) with no fields returns to greedy."""
+        fields = dict(config or {}, **fields)
+        if config is None and not fields:
+            _check(_lib().tllm_session_set_sampling(self._h, None), 'set_sampling')
+            return
+        cfg = _sampling_config(**fields)
+        _check(_lib().tllm_session_set_sampling(self._h, ctypes.byref(cfg)), 'set_sampling')
+
+    sample_tokens = staticmethod(sample_tokens)
 
     @staticmethod
     def _i32(a) -> np.ndarray:
