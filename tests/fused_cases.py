@@ -25,7 +25,7 @@ MODES = {
 
 NITS = (1, 2, 3, 4, 6, 8)
 STEPS = 4
-# the O-projection stage as the session serves it by default (session.cpp: o_fused), measured resident on an MI355X for every
+# the O-projection stage as the session serves it by default (session_setup.cpp decide_decode_form: o_fused), measured resident on an MI355X for every
 # instance below (96 KB of dynamic LDS next to the kernel's own; 256 workgroups, one per CU)
 FORM = {'sq_static_pc': 3, 'sq_dyn_pc': 1, 'woq8': 3, 'woq4': 1, 'woq4+o': 3, 'fp16': 1}
 

@@ -183,7 +183,7 @@ def test_a_timed_out_wait_is_sticky_and_leaves_the_buffer_alone():
     """a flag wait that expires must not be followed by a sum over a stale inbox.  Rank 1 skips an
     all-reduce: rank 0's launch gives up after its bounded spin, raises the error flag, leaves x as it was and does not
     advance the epoch; every later launch returns immediately (the session turns the flag into a failed call:
-    runtime/session.cpp check_comm)."""
+    runtime/session_setup.cpp check_comm)."""
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     q = ctx.Queue()

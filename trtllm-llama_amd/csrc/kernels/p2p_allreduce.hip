@@ -32,7 +32,7 @@
 // its own error word too: a rank that never timed out itself learns within one launch that the group is broken, instead of
 // carrying on peer-to-peer while the rank that timed out has gone back to RCCL.  Once the error word is set, this launch and
 // every later one (the rest of a replayed step graph) leave their buffers alone and return at once; the host sees the word at its
-// next synchronisation point, fails the call and takes the transport out of service on every rank (runtime/session.cpp
+// next synchronisation point, fails the call and takes the transport out of service on every rank (runtime/session_setup.cpp
 // check_comm; comm::p2p::disable_after_error clears the words, destroy + create + attach starts afresh).
 #include "dev_utils.h"
 #include "kernels.h"

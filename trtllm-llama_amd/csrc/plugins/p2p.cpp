@@ -27,10 +27,10 @@ struct State
     int max_spins = 0;
 };
 // Bumped by every change of what a captured step graph may contain (create, enable on / off, fused on / off, time-out): a
-// session compares it with the value it captured its graph under and re-captures on a difference (session.cpp).
+// session compares it with the value it captured its graph under and re-captures on a difference (runtime/session.cpp tllm_session_step).
 uint64_t g_generation = 1;
 // Bumped by disable_after_error only: a session whose last check saw an older value has work in flight (or in a captured
-// graph) that ran against the broken group, and must fail that call (session.cpp check_comm).
+// graph) that ran against the broken group, and must fail that call (runtime/session_setup.cpp check_comm).
 uint64_t g_error_generation = 0;
 std::mutex g_mu;
 State g;

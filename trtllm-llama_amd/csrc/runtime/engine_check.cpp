@@ -372,7 +372,7 @@ int verify_network(const std::string& network_json, const ScheduleDesc& d, std::
             }
     }
 
-    // ---- the schedule this runtime executes (runtime/session.cpp run_context / run_decode_step), as expressions
+    // ---- the schedule this runtime executes (runtime/session_context.cpp run_context / runtime/session_decode.cpp run_decode_step), as expressions
     Dag g;
     Expected E{g, {}, {}};
     auto in = [&](const std::string& n) { return g.leaf_input(n); };

@@ -1,0 +1,223 @@
+// The entry points of include/tllm_runtime_api.h that need no session: single GEMV / GEMM launches, the prefill GEMM tactic
+// table, the kernels' tuning hooks and the stand-alone sampler (tests, microbenchmarks, the Python builder's profile).
+#include "../../../include/tllm_runtime_api.h"
+#include "../kernels/kernels.h"
+#include "../plugins/plugin_base.h"
+#include "sampling_config.h"
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+using namespace tllm;
+using namespace tllm::kernels;
+using namespace tllm::runtime;
+
+namespace tllm
+{
+namespace kernels
+{
+extern int gemv_tune_blocks_per_cu;
+extern int gemv_mfma_min_rows;
+extern int gemm_tune_cfg;
+extern int gemm_woq_tune_cfg;
+extern bool gemm_swiglu_one_tile; // gemm_sqp.hip: A/B hook
+extern void* gemm_clock_probe;
+}
+} // namespace tllm
+
+static GemmParams gemm_params(const tllm_gemm_params_t* q)
+{
+    GemmParams g;
+    g.wtype = q->wtype;
+    g.out_dtype = q->out_dtype;
+    g.M = q->M;
+    g.N = q->N;
+    g.K = q->K;
+    g.a = q->a;
+    g.lda = q->lda;
+    g.w = q->w;
+    g.ldw = q->ldw;
+    g.scale_col = q->scale_col;
+    g.scale_row = q->scale_row;
+    g.per_channel = q->per_channel;
+    g.per_token = q->per_token;
+    g.c = q->c;
+    g.ldc = q->ldc;
+    return g;
+}
+
+extern "C" {
+
+int32_t tllm_gemv(const tllm_gemv_params_t* q, tllm_stream_t stream)
+{
+    if (!q)
+        return 1;
+    GemvParams p;
+    p.wtype = q->wtype;
+    p.pro = q->pro;
+    p.epi = q->epi;
+    p.out_dtype = q->out_dtype;
+    p.M = q->M;
+    p.N = q->N;
+    p.K = q->K;
+    p.x = q->x;
+    p.ldx = q->ldx;
+    p.w = q->w;
+    p.ldw = q->ldw;
+    p.scale_col = q->scale_col;
+    p.scale_row = q->scale_row;
+    p.per_channel = q->per_channel;
+    p.per_token = q->per_token;
+    p.gamma = q->gamma;
+    p.eps = q->eps;
+    p.act_scale = q->act_scale;
+    p.dyn_scale_out = q->dyn_scale_out;
+    p.x_pro_out = q->x_pro_out;
+    p.residual = q->residual;
+    p.epi_scale = q->epi_scale;
+    p.y = q->y;
+    p.ldy = q->ldy;
+    return launch_gemv(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gemm(const tllm_gemm_params_t* q, tllm_stream_t stream)
+{
+    if (!q)
+        return 1;
+    return launch_gemm(gemm_params(q), reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gemm_residual(const tllm_gemm_params_t* q, const void* residual, tllm_stream_t stream)
+{
+    if (!q || !residual || q->out_dtype != DT_HALF)
+    {
+        set_error("tllm_gemm_residual: needs a residual and fp16 output");
+        return 1;
+    }
+    GemmParams g = gemm_params(q);
+    g.residual = residual;
+    return launch_gemm(g, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gemm_profile(int32_t wtype, int32_t M, int32_t N, int32_t K, int32_t* best_cfg, float* best_us, tllm_stream_t stream)
+{
+    int cfg = 0;
+    float us = 0.f;
+    if (gemm_profile(wtype, M, N, K, &cfg, &us, reinterpret_cast<hipStream_t>(stream)))
+        return 1;
+    if (best_cfg)
+        *best_cfg = cfg;
+    if (best_us)
+        *best_us = us;
+    return 0;
+}
+
+int64_t tllm_gemm_tactics_export(char* buf, int64_t capacity)
+{
+    const std::string t = gemm_tactics_export();
+    if (buf && capacity > 0)
+    {
+        const size_t n = std::min((size_t) capacity - 1, t.size());
+        memcpy(buf, t.data(), n);
+        buf[n] = 0;
+    }
+    return (int64_t) t.size() + 1;
+}
+
+int32_t tllm_gemm_tactics_import(const char* text)
+{
+    return gemm_tactics_import(text) < 0 ? 1 : 0;
+}
+
+void tllm_gemm_tactics_clear(void)
+{
+    gemm_tactics_clear();
+}
+
+int32_t tllm_gemm_tactic_lookup(int32_t wtype, int32_t M, int32_t N, int32_t K)
+{
+    return gemm_tactic_lookup(wtype, M, N, K);
+}
+
+void tllm_gemv_set_blocks_per_cu(int32_t n)
+{
+    tllm::kernels::gemv_tune_blocks_per_cu = n;
+}
+
+void tllm_gemv_set_mfma_rows(int32_t n)
+{
+    tllm::kernels::gemv_mfma_min_rows = n;
+}
+
+int32_t tllm_gemm_swiglu_quant(const tllm_gemm_params_t* q, const void* w_up, const void* scale_col_up, const float* quant_scale,
+    tllm_stream_t stream)
+{
+    if (!q || !w_up || !scale_col_up || !quant_scale)
+    {
+        set_error("tllm_gemm_swiglu_quant: null argument");
+        return 1;
+    }
+    GemmParams g = gemm_params(q);
+    g.out_dtype = DT_INT8;
+    g.w2 = w_up;
+    g.scale_col2 = scale_col_up;
+    g.swiglu_qscale = quant_scale;
+    const int rc = tllm::kernels::launch_gemm_swiglu(g, reinterpret_cast<hipStream_t>(stream));
+    if (rc == 1)
+        set_error("tllm_gemm_swiglu_quant: problem not served by the fused kernel (SmoothQuant static, K %% 128 == 0, M >= 32, 16-byte aligned operands)");
+    return rc ? 1 : 0;
+}
+
+void tllm_gemm_set_clock_probe(void* device_buffer)
+{
+    tllm::kernels::gemm_clock_probe = device_buffer;
+}
+
+void tllm_gemm_set_tile_cfg(int32_t cfg)
+{
+    // 0 resets both tables; 101.. select the tile shape of the weight-only main-loop-dequantising GEMM (gemm_woq.hip: 101 = 256 x 192,
+    // 102 = 128 x 128, 103 = 256 x 192 two stages ahead, 104 = 256 x 192 on 4 waves)
+    // -2: the fused SwiGLU SmoothQuant GEMM in its one-tile-per-workgroup form (A/B against the persistent one; 0 resets)
+    if (cfg == 0 || cfg == -2)
+        tllm::kernels::gemm_swiglu_one_tile = cfg == -2;
+    if (cfg == -2)
+        return;
+    if (cfg == 0 || cfg > 100)
+        tllm::kernels::gemm_woq_tune_cfg = cfg > 100 ? cfg - 100 : 0;
+    if (cfg > 100)
+        return;
+    tllm::kernels::gemm_tune_cfg = cfg;
+}
+
+
+int32_t tllm_sample_tokens(const float* logits, int32_t nparts, int32_t rows, int32_t vocab_part, int32_t vocab,
+    const tllm_sampling_config_t* cfg, int32_t end_id, const int32_t* history, int32_t history_stride, const int32_t* input_lengths,
+    int32_t max_input_len, const int32_t* g, int32_t* out_ids, float* u_out, tllm_stream_t stream)
+{
+    if (!logits || !cfg || !g || !out_ids || rows < 1 || max_input_len < 0)
+    {
+        set_error("tllm_sample_tokens: bad arguments");
+        return 1;
+    }
+    if (const int rc = check_sampling_config("tllm_sample_tokens", *cfg))
+        return rc;
+    SamplingParams sp;
+    sampling_from_config(sp, *cfg);
+    sp.g.logits = logits;
+    sp.g.batch = rows;
+    sp.g.vocab_part = vocab_part;
+    sp.g.nparts = nparts;
+    sp.g.vocab = vocab;
+    sp.g.cur_ids = out_ids;
+    sp.g.seq_len = const_cast<int32_t*>(g); // advance = 0: read only; with g_base = 1 the token number is g[r] itself
+    sp.g.end_id = end_id;
+    sp.g.input_lengths = input_lengths;
+    sp.g.max_input_len = max_input_len;
+    sp.g_base = 1;
+    sp.history = history;
+    sp.history_stride = history_stride;
+    sp.u_out = u_out;
+    return launch_sampling_step(sp, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+} // extern "C"

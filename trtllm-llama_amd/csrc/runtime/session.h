@@ -1,0 +1,336 @@
+// The decode session behind include/tllm_runtime_api.h: its state and the declarations of what runs on it.  Internal to
+// csrc/runtime (not installed).  The definitions live by concern:
+//   session_weights.cpp  configuration text -> fields, named tensors -> Linear / Layer, the engine-file parser
+//   session_setup.cpp    buffer allocation, the decision which decode form runs, check_comm (which withdraws that decision)
+//   session_context.cpp  the prefill schedule
+//   session_decode.cpp   the generation-step schedule, head, sampler, all-reduce
+//   session.cpp          the rest of the C API: prompt upload, graph capture, the generate loop, getters, instrumentation
+#pragma once
+#include "../../../include/tllm_runtime_api.h"
+#include "../kernels/kernels.h"
+#include "../kernels/weight_layout.h"
+#include "../plugins/comm.h"
+#include "../plugins/plugin_base.h"
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+namespace tllm
+{
+namespace runtime
+{
+
+enum QuantBits
+{
+    QM_INT4_WEIGHTS = 1,
+    QM_INT8_WEIGHTS = 2,
+    QM_ACTIVATIONS = 4,
+    QM_PER_CHANNEL = 8,
+    QM_PER_TOKEN = 16,
+    QM_INT8_KV = 32
+};
+
+struct TensorRec
+{
+    int32_t dtype = 0;
+    std::vector<int64_t> dims;
+    void* dev = nullptr;
+    bool owned = false;
+    size_t bytes = 0;
+    int64_t numel() const
+    {
+        int64_t n = 1;
+        for (auto d : dims)
+            n *= d;
+        return n;
+    }
+};
+
+struct Linear
+{
+    int wtype = kernels::W_FP16;
+    const void* w = nullptr;
+    int64_t ldw = 0;
+    int N = 0, K = 0;
+    const void* scale_col = nullptr; // fp16 [N] (weight-only) | f32 [N] or [1] (SmoothQuant)
+    int per_channel = 0;
+    const float* act_scale = nullptr; // SmoothQuant static: dequant scale of the GEMM [1,1]
+};
+
+struct Layer
+{
+    const void* ln1 = nullptr;
+    const void* ln2 = nullptr;
+    const float* ln1_scale = nullptr;  // input_layernorm.scale_to_int (SQ static)
+    const float* ln2_scale = nullptr;  // post_layernorm.scale_to_int
+    const float* attn_qscale = nullptr; // attention.quantization_scaling_factor (ctx -> int8, SQ static)
+    const float* mlp_qscale = nullptr;  // mlp.quantization_scaling_factor (silu*mul -> int8, SQ static)
+    const float* kv_oq = nullptr;
+    const float* kv_qo = nullptr;
+    Linear qkv, dense, fc, gate, proj;
+    void* kv = nullptr;                // linear cache [B, 2, Hr, Smax, Dh], or the block pool [2, blocks, Hr, tokens_per_block, Dh]
+    const int64_t* kv_table = nullptr; // paged: device table int64 [B, 2, max_blocks] of block pointers into `kv`
+};
+
+// A bounded in-launch wait of a fused decode launch expired (tllm_session::check_comm).  Distinct from 1:
+// tllm_session_generate re-runs the request on the launches the session has fallen back to.
+constexpr int kFusedTimedOut = 2;
+
+} // namespace runtime
+} // namespace tllm
+
+#define HIP_OK(expr)                                                                                                   \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        hipError_t _e = (expr);                                                                                        \
+        if (_e != hipSuccess)                                                                                          \
+        {                                                                                                              \
+            set_error("%s failed: %s", #expr, hipGetErrorString(_e));                                                  \
+            return 1;                                                                                                  \
+        }                                                                                                              \
+    } while (0)
+
+#define RUN(expr)                                                                                                      \
+    do                                                                                                                 \
+    {                                                                                                                  \
+        const int _rc = (expr); /* (the callee's code travels up: kFusedTimedOut is told apart from a plain failure) */   \
+        if (_rc != 0)                                                                                                  \
+            return _rc;                                                                                                \
+    } while (0)
+
+struct tllm_session
+{
+    using TensorRec = tllm::runtime::TensorRec;
+    using Linear = tllm::runtime::Linear;
+    using Layer = tllm::runtime::Layer;
+
+    // ---- configuration
+    int num_layers = 0, num_heads = 0, hidden = 0, inter = 0, vocab = 0, max_pos = 2048;
+    int tp = 1, rank = 0;
+    int quant_mode = 0;
+    int neox = 1;
+    float eps = 1e-6f;
+    std::string wo_precision = "int8";
+    std::string network_json; // the traced network an engine file carries (Builder.build_engine), verified by load_engine
+    // derived
+    int Hr = 0, Dh = 0, Dr = 0, Ir = 0, Vr = 0;
+    bool sq = false, woq = false, int8_kv = false, per_token = false, per_channel = false;
+    int wtype = tllm::kernels::W_FP16; // of every layer's five projections (lm_head stays fp16)
+
+    std::map<std::string, TensorRec> tensors;
+    std::vector<Layer> layers;
+    const void* emb = nullptr;
+    const void* lnf = nullptr;
+    Linear head;
+    bool finalized = false;
+    std::vector<int32_t> group;
+    bool packed = false;       // remove_input_padding: the context phase runs on the real tokens only
+    int ctx_tokens = 0;        // ... their number in the current prompt batch
+    int32_t* cu_dev = nullptr;    // [B + 1] exclusive prefix sum of the input lengths
+    int32_t* last_rows = nullptr; // [B] packed row of every sequence's last prompt token
+    // paged KV cache (plugin field paged_kv_cache; K/kvCacheUtils.h KVBlockArray, PY/runtime/kv_cache_manager.py): the session
+    // owns the pool and hands every sequence its blocks at setup - the whole table is known then, so the generation graph
+    // needs no host-side block allocation between steps
+    bool paged_kv = false;
+    int tokens_per_block = 64, max_blocks = 0;
+    size_t kv_elems = 0; // elements of one layer's cache / pool
+    bool force_comm = false; // tests: run the TP collectives on a 1-rank communicator too (RCCL inside the captured graph)
+    // session key no_comm = 1: a rank's launches WITHOUT its collectives (all-reduces and the logits all-gather are skipped, nothing
+    // else changes) - the per-rank step time of a tensor-parallel shard on one GPU, bench.py's prediction for the first multi-GPU
+    // run.  TIMING ONLY: hidden states are one rank's partial sums.
+    bool no_comm = false;
+    bool debug_taps = false; // tests: keep every layer's GEMV inputs of the last generation step (tllm_session_get_tap[_ex])
+    // tap w of layer li: the activation exactly as GEMV w consumes it, behind its prologue (RMSNorm / split merge / quantiser):
+    //   0 QKV input [B, D]   1 O-projection input [B, Dr]   2 gate|up input [B, D]   3 down-projection input [B, Ir]
+    // fp16, or s8 where the path quantises (SmoothQuant) - the four quantisers of the SmoothQuant layer;
+    //   4 the layer's input row of the residual stream [B, D], always fp16 (tap 4 of layer num_layers - 1 + 1 does not exist:
+    //     the last layer's output is what the head consumes)
+    static constexpr int kTaps = 5;
+    char* tap_buf[kTaps] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // each [num_layers][B][width] x 2 bytes
+    int tap_width(int which) const { return which == 1 ? Dr : (which == 3 ? Ir : hidden); }
+    char* tap_ptr(int which, int li) const { return tap_buf[which] + (size_t) li * B * tap_width(which) * 2; }
+
+    // ---- runtime state (setup)
+    int B = 0, max_in = 0, max_new = 0, Smax = 0;
+    // beam search: Bc prompts, `beam` hypotheses each; B = Bc * beam sequences in the generation phase (B == Bc otherwise)
+    int Bc = 0, beam = 1;
+    int logit_rows = 0; // rows of the last head launch (Bc after the prompt, B after a generation step)
+    float* cum_log_probs = nullptr; // [B]
+    int32_t *parent_ids = nullptr, *cache_ind = nullptr, *in_len_ctx = nullptr; // [B, Smax], [B, Smax], [Bc]
+    std::vector<void*> allocs;
+    void *x = nullptr, *qkv = nullptr, *ctx = nullptr, *g = nullptr, *u = nullptr, *inter_buf = nullptr, *tmp = nullptr;
+    int8_t* q8 = nullptr;   // quantised activations (context path) [B*S, max(D, I)]
+    float* qscale = nullptr; // per-token scales [B*S]
+    float* logits = nullptr; // [B, V] (or gathered [tp, B, Vr])
+    float* logits_local = nullptr;
+    void* last_hidden = nullptr;
+    // tensor-parallel decode with the fused peer-to-peer seam (kernels/p2p_allreduce.hip): this rank's partial projection
+    // output, the normalised (+ quantised) row the next GEMV consumes, its per-token scales
+    void* ar_partial = nullptr; // [B, D] fp16
+    void* ar_norm = nullptr;    // [B, D] fp16 | s8
+    float* ar_scale = nullptr;  // [B]
+    void* mmha_ws = nullptr;
+    void* ctx_ws = nullptr; // V^T scratch of the MFMA context attention
+    int32_t *ids_in = nullptr, *cur_ids = nullptr, *out_ids = nullptr, *seq_len = nullptr, *in_len = nullptr,
+            *masked = nullptr, *finished = nullptr, *last_tok = nullptr;
+    const float* rope = nullptr;
+    int rope_len = 0;
+    float* rope_row = nullptr; // [B, Dh/2, 2]: cos/sin row of the next generation step (written by the sampler)
+    int32_t* rope_pos = nullptr; // [B]: the position that row belongs to (tllm_session_get_step_state)
+    int attn_nit = 4, attn_tchunk = 0, attn_ns = 0;
+    size_t attn_o_off = 0;
+    // the last split of a head to arrive merges inside the attention launch (mmha_decode.hip step 6); beyond 16 partials the finest
+    // split runs with its own combine launch
+    bool attn_tail = false;
+    uint32_t* attn_tickets = nullptr;
+    // r05: batch-1 greedy decode of a SmoothQuant engine runs the QKV projection, RoPE, the cache append and the attention of a head
+    // in ONE launch (kernels/qkv_attn_fused.hip); session key fuse_qkv_attention = 0 keeps the two launches (A/B, parity tests)
+    int fuse_qkv_cfg = -1;          // -1 auto, 0 off
+    bool qkv_attn_fused = false;    // decided at setup
+    // ... and the O-projection + residual of the layer as a third stage of that launch (static SmoothQuant: the context row
+    // travels as its int8 image); session key fuse_o_projection = 0 keeps the GEMV launch
+    int fuse_o_cfg = -1;
+    int fused_retries = 0;          // requests tllm_session_generate ran a second time behind an expired in-launch wait
+    int dual_mlp_cfg = -1;          // session key dual_mlp_gemm = 0: prefill fc / gate as two GEMMs + the SwiGLU-quantiser pass (A/B)
+    int fused_max_spins = -1;       // session key fused_max_spins: bound of the in-launch waits (tests: 0 = the first miss times out)
+    bool o_fused = false;
+    uint64_t* fused_xchg = nullptr; // granule exchange, shared by all layers
+    uint32_t* step_epoch = nullptr; // advanced by the sampler once per generation step (the granule tags derive from it)
+    uint32_t* fused_err = nullptr;  // raised by a bounded wait that expired
+    uint32_t timing_tag = 0;        // explicit tags of eager launches outside a step (tllm_session_time_kernel)
+    // r06: the gated MLP of a decode step (gate|up GEMV + down GEMV) in ONE launch (kernels/mlp_fused.hip): batch 1, tp 1, static
+    // SmoothQuant, the 7B extents.  Bit-identical to the two GEMV launches but measured 1 us per layer SLOWER (26.4 against
+    // 16.4 + 9.0 us, profiles/r06_mlp_one_launch.txt), so it runs only when asked for: session key fuse_mlp = 1
+    int fuse_mlp_cfg = 0;
+    bool mlp_fused_dec = false;  // decided at setup
+    uint8_t* mlp_flags = nullptr; // one byte per workgroup (shared by all layers), zero before the first launch and after a failed one
+    uint64_t* mlp_timing = nullptr;
+    uint64_t* fused_timing = nullptr; // session key fused_timeline = 1: stage clock of the fused launch, [Hr * 8][16] ticks
+    bool fused_timeline = false;
+    void* ctx_q8 = nullptr;
+    int end_id = -1;
+    bool sampling_on = false;       // tllm_session_set_sampling: run_sampler launches kernels/sampling.hip with `sampling`
+    tllm::kernels::SamplingParams sampling; // configuration fields only; pointers and shapes are filled per launch
+    hipGraphExec_t graph = nullptr;
+    hipStream_t graph_stream = nullptr;
+    uint64_t graph_comm_gen = 0;   // comm::p2p::generation() the step graph was captured under
+    uint64_t comm_err_seen = 0;    // comm::p2p::error_generation() at this session's last check_comm
+    hipStream_t own_stream = nullptr; // used when the caller passes the NULL stream (it cannot be captured)
+
+    // ---- optional per-launch instrumentation (tllm_session_profile): event pairs around every launch class
+    enum ProfClass
+    {
+        PC_GEMV_LAYER = 0,
+        PC_GEMV_HEAD = 1,
+        PC_ATTENTION = 2,
+        PC_OTHER = 3,
+        PC_COMM = 4,
+        PC_COUNT = 5
+    };
+    bool profiling = false;
+    // tllm_session_time_kernel: launch just stage <only_kernel> of every layer (DecodeStep says which launch sites an id means)
+    int only_kernel = -1;
+    int gemv_cls = PC_GEMV_LAYER;
+    struct ProfRec
+    {
+        hipEvent_t a, b;
+        int cls;
+    };
+    std::vector<ProfRec> prof;
+
+    hipStream_t pick(tllm_stream_t stream)
+    {
+        if (stream)
+            return reinterpret_cast<hipStream_t>(stream);
+        if (!own_stream)
+            (void) hipStreamCreate(&own_stream);
+        return own_stream;
+    }
+
+    ~tllm_session(); // session.cpp
+
+    // ---- session_weights.cpp
+    const TensorRec* find(const std::string& name, bool required = true);
+    int want(const TensorRec* t, const std::string& name, int32_t dtype, int64_t numel);
+    // resolve one linear layer "prefix" with logical shape [N, K] for this session's quantisation mode
+    int resolve_linear(const std::string& prefix, int N, int K, Linear& L, bool force_fp16 = false);
+    int scalar_f32(const std::string& name, const float** out);
+
+    // ---- session_setup.cpp
+    template <typename T>
+    int dalloc(T** p, size_t bytes); // device memory the session owns until free_runtime (defined below the struct)
+    void free_runtime();
+    void drop_graph(); // the captured step no longer matches what an eager step would issue
+    int alloc_buffers();
+    int decide_decode_form();       // attention split layout, qkv_attn_fused / o_fused / mlp_fused_dec
+    int alloc_decode_form_buffers(); // what the forms decide_decode_form chose need
+    // After a stream synchronisation: did a fused decode launch or a peer-to-peer collective of this session time out?  Fails
+    // the call then, and withdraws the decode form / the transport that timed out.
+    int check_comm();
+
+    // ---- session_context.cpp
+    // context: plain GEMM on M rows (activation already in the operand type; per-token SmoothQuant: its scales are in qscale)
+    int gemm(const Linear& L, int M, const void* a, void* c, int out_dtype, hipStream_t st, const void* residual = nullptr,
+        const void* silu_gate = nullptr);
+    int profile_prefill_gemms(int M);
+    int context_norm(int M, const void* gamma, const float* static_scale, hipStream_t st);
+    int context_attention(const Layer& L, bool q_in_attn, hipStream_t st);
+    int context_gate_up(const Layer& L, int M, const void* a_in, const void** p_in, hipStream_t st);
+    int context_proj_residual(const Linear& L, int M, const void* in, bool fuse_res, hipStream_t st);
+    int run_context(hipStream_t st);
+
+    // ---- session_decode.cpp
+    template <typename F>
+    int timed(int cls, hipStream_t st, F&& f); // f(), between an event pair of class cls while profiling (defined below the struct)
+    // decode: fused skinny GEMM.  `tap`: where the launch leaves its prologue's result (x_pro_out), or nullptr
+    int gemv(const Linear& L, int M, int pro, int epi, const void* xin, int64_t ldx, const void* gamma, const float* in_qscale,
+        const void* residual, const float* epi_scale, void* y, int64_t ldy, int out_dtype, const Linear* up, hipStream_t st,
+        const float* row_scales = nullptr, void* tap = nullptr);
+    int allreduce(void* buf, int64_t n, hipStream_t st);
+    int run_head(const void* h, int rows, hipStream_t st, bool normalised = false);
+    int run_sampler(int advance, hipStream_t st);
+    struct DecodeStep; // what is fixed for one generation step (session_decode.cpp)
+    DecodeStep plan_decode_step(hipStream_t st);
+    int tap_copy(const DecodeStep& ds, int which, int li, const void* src, int elem_bytes);
+    int stage_front(const DecodeStep& ds, int li);
+    int stage_qkv(const DecodeStep& ds, int li);
+    int stage_attention(const DecodeStep& ds, int li);
+    int stage_o_proj(const DecodeStep& ds, int li);
+    int stage_seam(const DecodeStep& ds, const void* gamma, const float* quant_scale, int quant);
+    int stage_mlp_one(const DecodeStep& ds, int li);
+    int stage_gate_up(const DecodeStep& ds, int li);
+    int stage_down(const DecodeStep& ds, int li);
+    int run_decode_step(hipStream_t st);
+};
+
+// The two member templates: every unit that uses one must see its body, so they are here and not in a .cpp file.
+template <typename T>
+int tllm_session::dalloc(T** p, size_t bytes)
+{
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes ? bytes : 16) != hipSuccess)
+    {
+        tllm::set_error("session: hipMalloc(%zu) failed", bytes);
+        return 1;
+    }
+    allocs.push_back(d);
+    *p = static_cast<T*>(d);
+    return 0;
+}
+
+template <typename F>
+int tllm_session::timed(int cls, hipStream_t st, F&& f)
+{
+    if (!profiling)
+        return f();
+    ProfRec r;
+    r.cls = cls;
+    (void) hipEventCreate(&r.a);
+    (void) hipEventCreate(&r.b);
+    (void) hipEventRecord(r.a, st);
+    const int rc = f();
+    (void) hipEventRecord(r.b, st);
+    prof.push_back(r);
+    return rc;
+}

@@ -1,0 +1,238 @@
+// The prefill schedule: the whole prompt batch through every layer as GEMMs on M = tokens rows, then the head on every
+// sequence's last token.  Layer graph = Q/llama_model.py:78-119 (LLaMADecoderLayer.forward); head = :253-287.
+//   RMSNorm (+ quantiser) -> QKV GEMM -> context attention (RoPE, cache fill) -> (quantiser) -> O GEMM + residual
+//   RMSNorm (+ quantiser) -> fc / gate GEMMs + SwiGLU (+ quantiser), in as few launches as the mode allows -> down GEMM + residual
+// SmoothQuant block template: SURVEY Appendix A.4 (the reference's SmoothQuant-LLaMA never ran; designed by analogy to
+// PY/quantization/layer.py:385-439,596-852).
+#include "session.h"
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+using namespace tllm;
+using namespace tllm::kernels;
+using namespace tllm::runtime;
+
+int tllm_session::gemm(const Linear& L, int M, const void* a, void* c, int out_dtype, hipStream_t st, const void* residual,
+    const void* silu_gate)
+{
+    const bool dyn = sq && per_token; // the activation's quantiser left one scale per row in qscale
+    GemmParams g;
+    g.residual = residual;
+    g.silu_gate = silu_gate;
+    g.wtype = L.wtype;
+    g.out_dtype = out_dtype;
+    g.M = M;
+    g.N = L.N;
+    g.K = L.K;
+    g.a = a;
+    g.lda = L.K;
+    g.w = L.w;
+    g.ldw = L.ldw;
+    g.scale_col = L.scale_col;
+    g.scale_row = dyn ? qscale : L.act_scale;
+    g.per_channel = L.per_channel;
+    g.per_token = dyn;
+    g.c = c;
+    g.ldc = L.N;
+    return launch_gemm(g, st) ? 1 : 0;
+}
+
+// On-device tactic selection (kernels/gemm_tactics.hip; reference: int8_gemm_template.h:372-457, stored per M bucket in the
+// plugin, smoothQuantGemmPlugin.cpp:253-282): the MFMA kernel of each prefill GEMM shape of this model at M rows is the one
+// that measured fastest on THIS device - timed once per process and shape unless the engine file brought the choice along.
+// TLLM_GEMM_TACTICS=off keeps the static rule.
+int tllm_session::profile_prefill_gemms(int M)
+{
+    static const bool off = [] {
+        const char* e = getenv("TLLM_GEMM_TACTICS");
+        return e && (!strcmp(e, "off") || !strcmp(e, "0"));
+    }();
+    if (off || layers.empty() || packed) // packed inputs: M varies with the prompt batch, the nearest bucket entry serves
+        return 0;
+    const Layer& L = layers[0];
+    // weight-only prefill runs gemm_woq.hip (one kernel per shape class, no tactic table)
+    if (L.qkv.wtype == W_INT8_WOQ || L.qkv.wtype == W_INT4_WOQ)
+        return 0;
+    for (const Linear* l : {&L.qkv, &L.dense, &L.fc, &L.proj})
+    {
+        const int wt = l->wtype == W_INT8_SQ ? W_INT8_SQ : W_FP16;
+        // an entry of the same power-of-two M bucket (what the engine file brought along, Builder._profile_gemm_tactics)
+        // serves: the launcher would use it for this M anyway
+        if (gemm_tactic_lookup(wt, M, l->N, l->K) > 0)
+            continue;
+        int cfg = 0;
+        float us = 0.f;
+        // best effort: a profile that cannot run (no memory left for its operands next to a large session) leaves the shape
+        // to the static rule - it must not fail the set-up, nor leave its message behind for a later, unrelated failure
+        if (gemm_profile(wt, M, l->N, l->K, &cfg, &us, nullptr))
+        {
+            set_error("%s", "");
+            break;
+        }
+    }
+    return 0;
+}
+
+// x -> RMSNorm(x) * gamma as the next GEMM's operand: fp16 in tmp, or (SmoothQuant) int8 in q8 with the static scale or one
+// scale per row in qscale
+int tllm_session::context_norm(int M, const void* gamma, const float* static_scale, hipStream_t st)
+{
+    RmsnormParams r;
+    r.M = M;
+    r.N = hidden;
+    r.x = x;
+    r.gamma = gamma;
+    r.eps = eps;
+    if (sq)
+    {
+        r.q = q8;
+        if (per_token)
+            r.dyn_scale_out = qscale;
+        else
+            r.static_scale = static_scale;
+    }
+    else
+        r.y = tmp;
+    return launch_rmsnorm(r, st);
+}
+
+int tllm_session::context_attention(const Layer& L, bool q_in_attn, hipStream_t st)
+{
+    ContextAttnParams c;
+    c.batch = Bc;
+    c.seq = max_in;
+    c.num_heads = Hr;
+    c.head_size = Dh;
+    c.rotary_dim = Dh;
+    c.neox = neox;
+    c.inv_sqrt_dh = 1.f / sqrtf((float) Dh);
+    c.int8_kv = int8_kv;
+    c.max_seq_len = Smax;
+    c.qkv = qkv;
+    c.kv_cache = L.kv;
+    c.input_lengths = in_len_ctx;
+    c.cache_seq_stride = beam;
+    c.block_pointers = L.kv_table;
+    c.tokens_per_block = tokens_per_block;
+    c.max_blocks_per_seq = max_blocks;
+    c.kv_scale_orig_quant = L.kv_oq;
+    c.rope_table = rope;
+    c.rope_table_len = rope_len;
+    c.out = ctx;
+    c.workspace = ctx_ws;
+    c.cu_seqlens = packed ? cu_dev : nullptr;
+    if (q_in_attn)
+    {
+        c.out_q8 = q8;
+        c.out_q_scale = L.attn_qscale;
+    }
+    return launch_context_attention(c, st);
+}
+
+// fc and gate on a_in, SwiGLU, and the down-projection's quantiser where the mode has one.  *p_in: where the result is
+int tllm_session::context_gate_up(const Layer& L, int M, const void* a_in, const void** p_in, hipStream_t st)
+{
+    *p_in = inter_buf;
+    if (sq && !per_token && M >= 32 && dual_mlp_cfg != 0)
+    {
+        // fc and gate in one kernel with SwiGLU + the static quantiser in its epilogue (gemm_sqp.hip, DUAL): the two fp16
+        // [M, Ir] intermediates and the pointwise pass between the GEMMs disappear.  The int8 result goes to inter_buf
+        // (q8 is this kernel's INPUT)
+        GemmParams d;
+        d.wtype = L.fc.wtype;
+        d.out_dtype = DT_INT8;
+        d.M = M;
+        d.N = L.fc.N;
+        d.K = L.fc.K;
+        d.a = a_in;
+        d.lda = L.fc.K;
+        d.w = L.fc.w;
+        d.ldw = L.fc.ldw;
+        d.scale_col = L.fc.scale_col;
+        d.scale_row = L.fc.act_scale;
+        d.per_channel = L.fc.per_channel;
+        d.per_token = 0;
+        d.c = inter_buf;
+        d.ldc = L.fc.N;
+        d.w2 = L.gate.w;
+        d.scale_col2 = L.gate.scale_col;
+        d.scale_row2 = L.gate.act_scale;
+        d.swiglu_qscale = L.mlp_qscale;
+        if (L.gate.ldw == L.fc.ldw && L.gate.per_channel == L.fc.per_channel && L.gate.N == L.fc.N && L.gate.K == L.fc.K)
+        {
+            const int rc = launch_gemm_swiglu(d, st);
+            if (rc < 0)
+                return 1;
+            if (rc == 0)
+                return 0;
+        }
+    }
+    RUN(gemm(L.fc, M, a_in, g, DT_HALF, st));
+    if (!sq)
+    {
+        // fp16 / weight-only: SwiGLU folded into the second projection's epilogue (g is read there instead of in a pass of
+        // its own; same rounding points) - one launch and a [M, Ir] write + read fewer per layer
+        return gemm(L.gate, M, a_in, inter_buf, DT_HALF, st, nullptr, g);
+    }
+    RUN(gemm(L.gate, M, a_in, u, DT_HALF, st));
+    *p_in = q8;
+    if (!per_token)
+        return launch_swiglu_quant(q8, g, u, (int64_t) M * Ir, L.mlp_qscale, st); // SwiGLU and its quantiser in one pass
+    RUN(launch_swiglu(inter_buf, g, u, (int64_t) M * Ir, st));
+    return launch_quantize_per_token(q8, inter_buf, DT_HALF, M, Ir, qscale, st);
+}
+
+// x <- x + L(in): the residual rides in the GEMM's epilogue (same rounding: fp16(gemm) then fp16(sum)), or - tensor parallel,
+// or a shape the epilogue does not serve - the partial sums go to tmp, through the all-reduce, and are added by a pass of its own
+int tllm_session::context_proj_residual(const Linear& L, int M, const void* in, bool fuse_res, hipStream_t st)
+{
+    if (fuse_res)
+        return gemm(L, M, in, x, DT_HALF, st, x);
+    RUN(gemm(L, M, in, tmp, DT_HALF, st));
+    RUN(allreduce(tmp, (int64_t) M * hidden, st));
+    return launch_add(x, x, tmp, (int64_t) M * hidden, st);
+}
+
+// ------------------------------------------------------------------------------------------ context step
+int tllm_session::run_context(hipStream_t st)
+{
+    const int S = max_in, M = packed ? ctx_tokens : Bc * S, D = hidden;
+    const void* a_in = sq ? (const void*) q8 : tmp; // what context_norm leaves
+    RUN(launch_embedding(x, ids_in, emb, M, D, vocab, st));
+    for (int li = 0; li < num_layers; ++li)
+    {
+        Layer& L = layers[li];
+        // (weight-only: gemm_woq.hip adds the residual in its epilogue too - same two roundings; its own serve conditions)
+        const bool woq_w = L.dense.wtype == W_INT8_WOQ || L.dense.wtype == W_INT4_WOQ;
+        const bool fuse_res = tp == 1 && !force_comm && M >= 32 && D % 8 == 0
+            && (woq_w ? (L.dense.K % 64 == 0 && L.proj.K % 64 == 0)
+                      : ((L.dense.wtype == W_INT8_SQ || L.dense.wtype == W_FP16)
+                          && (L.dense.K * (L.dense.wtype == W_FP16 ? 2 : 1)) % 128 == 0
+                          && (L.proj.K * (L.proj.wtype == W_FP16 ? 2 : 1)) % 128 == 0));
+        // --- attention block
+        RUN(context_norm(M, L.ln1, L.ln1_scale, st));
+        RUN(gemm(L.qkv, M, a_in, qkv, DT_HALF, st));
+        // SmoothQuant static: the O-projection's input quantiser rides in the attention's epilogue (padded inputs; with
+        // packed inputs M counts real tokens only and the pass below covers exactly those)
+        const bool q_in_attn = sq && !per_token && !packed;
+        RUN(context_attention(L, q_in_attn, st));
+        if (sq && per_token)
+            RUN(launch_quantize_per_token(q8, ctx, DT_HALF, M, Dr, qscale, st));
+        else if (sq && !q_in_attn)
+            RUN(launch_quantize_tensor(q8, ctx, DT_HALF, (int64_t) M * Dr, L.attn_qscale, st));
+        RUN(context_proj_residual(L.dense, M, sq ? (const void*) q8 : ctx, fuse_res, st));
+        // --- MLP block
+        RUN(context_norm(M, L.ln2, L.ln2_scale, st));
+        const void* p_in = nullptr; // inter_buf or q8, as the path through gate|up leaves it
+        RUN(context_gate_up(L, M, a_in, &p_in, st));
+        RUN(context_proj_residual(L.proj, M, p_in, fuse_res, st));
+    }
+    // head: last real token of every sequence -> ln_f -> lm_head -> fp32 logits  (Q/llama_model.py:272-279)
+    if (packed)
+        RUN(launch_gather_rows(last_hidden, x, last_rows, Bc, D, st));
+    else
+        RUN(launch_gather_last_token(last_hidden, x, last_tok, Bc, S, D, st));
+    RUN(run_head(last_hidden, Bc, st));
+    return 0;
+}

@@ -1,0 +1,356 @@
+// tllm_session_setup[_beam]: the buffers of a (batch, beam, lengths) shape, and the decision which form of the decode
+// layer runs on them.  check_comm, the only code that withdraws that decision again, sits next to it.
+#include "session.h"
+#include <algorithm>
+
+using namespace tllm;
+using namespace tllm::kernels;
+using namespace tllm::runtime;
+
+void tllm_session::drop_graph()
+{
+    if (graph)
+    {
+        (void) hipGraphExecDestroy(graph);
+        graph = nullptr;
+    }
+}
+
+void tllm_session::free_runtime()
+{
+    drop_graph();
+    for (auto p : allocs)
+        (void) hipFree(p);
+    allocs.clear();
+}
+
+// ------------------------------------------------------------------------------------------ buffers
+int tllm_session::alloc_buffers()
+{
+    const int S = max_in, D = hidden;
+    const size_t M = std::max((size_t) Bc * S, (size_t) B); // prompt rows; the generation phase needs B
+    const size_t kv_esz = int8_kv ? 1 : 2;
+    size_t kv_bytes = (size_t) B * 2 * Hr * Smax * Dh * kv_esz;
+    const int T = tokens_per_block;
+    max_blocks = paged_kv ? (Smax + T - 1) / T : 0;
+    const size_t nblocks = (size_t) B * max_blocks, blk_bytes = (size_t) Hr * T * Dh * kv_esz;
+    if (paged_kv)
+        kv_bytes = 2 * nblocks * blk_bytes;
+    kv_elems = kv_bytes / kv_esz;
+    for (auto& L : layers)
+    {
+        RUN(dalloc(&L.kv, kv_bytes));
+        HIP_OK(hipMemset(L.kv, 0, kv_bytes));
+        L.kv_table = nullptr;
+        if (paged_kv)
+        {
+            // pool [2, blocks, Hr, T, Dh] (K half then V half, like the reference's BlocksManager:
+            // kv_cache_manager.py:84-96); logical block j of sequence bb is pool block j * B + bb, so consecutive time
+            // blocks of one sequence are NOT contiguous
+            std::vector<int64_t> table((size_t) B * 2 * max_blocks);
+            const int64_t base = reinterpret_cast<int64_t>(L.kv);
+            for (int bb = 0; bb < B; ++bb)
+                for (int j = 0; j < max_blocks; ++j)
+                {
+                    const int64_t blk = (int64_t) j * B + bb;
+                    table[((size_t) bb * 2 + 0) * max_blocks + j] = base + blk * (int64_t) blk_bytes;
+                    table[((size_t) bb * 2 + 1) * max_blocks + j] = base + ((int64_t) nblocks + blk) * (int64_t) blk_bytes;
+                }
+            int64_t* dev = nullptr;
+            RUN(dalloc(&dev, table.size() * 8));
+            HIP_OK(hipMemcpy(dev, table.data(), table.size() * 8, hipMemcpyHostToDevice));
+            L.kv_table = dev;
+        }
+    }
+    RUN(dalloc(&x, M * D * 2));
+    RUN(dalloc(&tmp, M * D * 2));
+    RUN(dalloc(&qkv, M * 3 * Dr * 2));
+    RUN(dalloc(&ctx, M * Dr * 2));
+    RUN(dalloc(&g, M * Ir * 2));
+    RUN(dalloc(&u, M * Ir * 2));
+    RUN(dalloc(&inter_buf, M * Ir * 2));
+    RUN(dalloc(&q8, M * (size_t) std::max(D, Ir)));
+    RUN(dalloc(&qscale, M * 4));
+    RUN(dalloc(&logits_local, (size_t) B * Vr * 4));
+    RUN(dalloc(&logits, (size_t) B * Vr * tp * 4));
+    RUN(dalloc(&last_hidden, (size_t) B * D * 2));
+    RUN(dalloc(&ctx_ws, context_attention_workspace_size(Bc, Hr, Dh, S) + 256));
+    if ((size_t) Bc * S >= 32)
+        RUN(profile_prefill_gemms(Bc * S));
+    RUN(dalloc(&ar_partial, (size_t) B * D * 2));
+    RUN(dalloc(&ar_norm, (size_t) B * D * 2));
+    RUN(dalloc(&ar_scale, (size_t) B * 4));
+    for (int w = 0; w < tllm_session::kTaps; ++w)
+    {
+        tap_buf[w] = nullptr;
+        if (debug_taps)
+        {
+            const size_t nb = (size_t) num_layers * B * tap_width(w) * 2;
+            RUN(dalloc(&tap_buf[w], nb));
+            HIP_OK(hipMemset(tap_buf[w], 0, nb));
+        }
+    }
+    RUN(dalloc(&cu_dev, (size_t) (Bc + 1) * 4));
+    RUN(dalloc(&last_rows, (size_t) Bc * 4));
+    RUN(dalloc(&mmha_ws, mmha_workspace_size(B, Hr, Dh, Smax) + 256));
+    HIP_OK(hipMemset(mmha_ws, 0, mmha_workspace_size(B, Hr, Dh, Smax) + 256));
+    RUN(dalloc(&ids_in, M * 4));
+    RUN(dalloc(&cur_ids, (size_t) B * 4));
+    RUN(dalloc(&out_ids, (size_t) B * Smax * 4));
+    RUN(dalloc(&seq_len, (size_t) B * 4));
+    RUN(dalloc(&in_len, (size_t) B * 4));
+    RUN(dalloc(&last_tok, (size_t) Bc * 4));
+    RUN(dalloc(&in_len_ctx, (size_t) Bc * 4));
+    cum_log_probs = nullptr;
+    parent_ids = cache_ind = nullptr;
+    if (beam > 1)
+    {
+        RUN(dalloc(&cum_log_probs, (size_t) B * 4));
+        RUN(dalloc(&parent_ids, (size_t) B * Smax * 4));
+        RUN(dalloc(&cache_ind, (size_t) B * Smax * 4));
+    }
+    RUN(dalloc(&finished, (size_t) B * 4));
+    RUN(dalloc(&masked, (size_t) B * Smax * 4));
+    rope = plugins::rope_table(Dh, Smax > max_pos ? Smax : max_pos, &rope_len);
+    if (!rope)
+        return 1;
+    RUN(dalloc(&rope_row, (size_t) B * Dh * sizeof(float)));
+    HIP_OK(hipMemset(rope_row, 0, (size_t) B * Dh * sizeof(float)));
+    RUN(dalloc(&rope_pos, (size_t) B * 4));
+    HIP_OK(hipMemset(rope_pos, 0, (size_t) B * 4));
+    RUN(dalloc(&step_epoch, 64));
+    HIP_OK(hipMemset(step_epoch, 0, 64));
+    fused_err = step_epoch + 8;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ decode form
+// Which launches a generation step of this session consists of.  Decides, allocates nothing:
+//   attn_tail / attn_nit / attn_tchunk / attn_ns / attn_o_off   the split-KV layout of the attention
+//   qkv_attn_fused   QKV projection + RoPE + cache append + attention in one launch (kernels/qkv_attn_fused.hip)
+//   o_fused          ... with the O-projection + residual as its third stage
+//   mlp_fused_dec    gate|up + down in one launch (kernels/mlp_fused.hip)
+int tllm_session::decide_decode_form()
+{
+    const int D = hidden;
+    // The split-KV merge runs inside the attention launch, by the last split of a head to arrive (mmha_decode.hip step 6; up to
+    // 16 partials: 16-row splits cover 4096 cache slots at head size 128); 12 rows per lane group while that needs <= 8 partials
+    // (7 x 32 instead of 5 x 32 workgroups at the 1024-token bench context).  Beyond 16 partials: the finest split with its own
+    // combine launch.
+    int tc = 0, ns = 0;
+    size_t off = 0;
+    attn_tail = false;
+    attn_nit = 4;
+    if (mmha_split_layout(Dh, Smax, 16, B, Hr, &tc, &ns, &off) == 0 && ns <= 16)
+    {
+        attn_nit = 16;
+        if (mmha_split_layout(Dh, Smax, 12, B, Hr, &tc, &ns, &off) == 0 && ns <= 8)
+            attn_nit = 12;
+        attn_tail = true;
+    }
+    if (mmha_split_layout(Dh, Smax, attn_nit, B, Hr, &tc, &ns, &off))
+    {
+        set_error("session: unsupported head size %d", Dh);
+        return 1;
+    }
+    attn_tchunk = tc;
+    attn_ns = ns;
+    attn_o_off = off;
+
+    qkv_attn_fused = false;
+    o_fused = false;
+    mlp_fused_dec = false;
+    if (layers.empty())
+        return 0;
+    // the one-launch MLP: batch 1, tp 1, static SmoothQuant, only when asked for
+    if (fuse_mlp_cfg > 0 && B == 1 && beam == 1 && tp == 1 && sq && !per_token && mlp_fused_serves(D, Ir, D))
+    {
+        bool ok = true;
+        for (auto& L : layers)
+            ok = ok && L.fc.wtype == W_INT8_SQ && L.gate.wtype == W_INT8_SQ && L.proj.wtype == W_INT8_SQ && L.fc.K == D && L.gate.K == D
+                && L.fc.N == Ir && L.gate.N == Ir && L.fc.ldw == L.gate.ldw && L.fc.per_channel == L.gate.per_channel
+                && L.proj.N == D && L.proj.K == Ir && L.fc.scale_col && L.gate.scale_col && L.proj.scale_col && L.fc.act_scale
+                && L.proj.act_scale && L.ln2 && L.ln2_scale && L.mlp_qscale && L.fc.ldw % 16 == 0 && L.proj.ldw % 16 == 0;
+        mlp_fused_dec = ok;
+    }
+    // the one-launch QKV projection + attention: batch 1, greedy, linear cache, the geometry the kernel is built for (K = 4096,
+    // head size 128, heads x 8 workgroups = one per CU), NeoX rotary over the whole head.  Weights: SmoothQuant, or - r05 -
+    // weight-only int8 (the same 4 KB weight rows against the normalised fp16 row), or - r06 - fp16 (rows of 8 KB, two tiles
+    // per row pair; BASELINE.json configs[1]), or weight-only int4.  Every projection of a session has the session's weight type
+    // (resolve_linear), so that type is the kind of all layers.
+    const bool fp16_w = wtype == W_FP16, woq4 = wtype == W_INT4_WOQ;
+    const int wkind = wtype == W_INT8_SQ ? 0 : (wtype == W_INT8_WOQ ? 1 : (fp16_w ? 2 : 3)); // qkv_attn_fused_serves' weight_kind
+    const int kv8 = int8_kv ? 1 : 0;
+    if (fuse_qkv_cfg == 0 || !attn_tail || B != 1 || beam != 1 || paged_kv || tp != 1 || !neox
+        || !qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0))
+        return 0;
+    for (auto& L : layers)
+        if (!(L.qkv.wtype == wtype && L.qkv.K == D && L.qkv.ldw == (fp16_w ? 2 * D : (woq4 ? D / 2 : D)) && L.qkv.N == 3 * Dr
+                && (L.qkv.scale_col || fp16_w)))
+            return 0;
+    qkv_attn_fused = true;
+    // (tp == 1 here: no all-reduce behind the projection.  Weight-only int8: the context row travels as fp16)
+    // (int4: the stage is built and bit-identical but measures at par with the GEMV launch it replaces - 724 vs 721 - 735 tokens/s -
+    //  so it is on only when asked for: fuse_o_projection = 1)
+    o_fused = fuse_o_cfg != 0 && !fp16_w && (woq4 ? fuse_o_cfg > 0 : true) && (sq ? !per_token : true);
+    for (auto& L : layers)
+        o_fused = o_fused && L.dense.N == D && L.dense.scale_col && L.dense.wtype == wtype
+            && (sq ? (L.dense.act_scale && L.attn_qscale) : true)
+            && qkv_attn_fused_serves_o(Hr, Dh, L.dense.N, L.dense.K, L.dense.ldw, wkind);
+    // ... and the instance that will run must be resident as a whole (occupancy query x CUs of this device >= its grid)
+    if (!qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, o_fused ? 1 : 0))
+    {
+        o_fused = false;
+        qkv_attn_fused = qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0);
+    }
+    return 0;
+}
+
+int tllm_session::alloc_decode_form_buffers()
+{
+    attn_tickets = nullptr;
+    ctx_q8 = nullptr;
+    fused_xchg = nullptr;
+    fused_timing = nullptr;
+    mlp_flags = nullptr;
+    mlp_timing = nullptr;
+    if (attn_tail)
+    {
+        RUN(dalloc(reinterpret_cast<void**>(&attn_tickets), (size_t) B * Hr * 4));
+        HIP_OK(hipMemset(attn_tickets, 0, (size_t) B * Hr * 4));
+        RUN(dalloc(&ctx_q8, (size_t) B * Dr));
+    }
+    if (mlp_fused_dec)
+    {
+        RUN(dalloc(&mlp_flags, mlp_fused_flag_bytes()));
+        HIP_OK(hipMemset(mlp_flags, 0, mlp_fused_flag_bytes()));
+        if (fused_timeline)
+        {
+            RUN(dalloc(&mlp_timing, (size_t) 256 * 16 * 8));
+            HIP_OK(hipMemset(mlp_timing, 0, (size_t) 256 * 16 * 8));
+        }
+    }
+    if (qkv_attn_fused)
+    {
+        const size_t xb = qkv_attn_fused_xchg_bytes(Hr);
+        RUN(dalloc(&fused_xchg, xb));
+        HIP_OK(hipMemset(fused_xchg, 0, xb));
+        if (fused_timeline)
+        {
+            RUN(dalloc(&fused_timing, (size_t) Hr * 8 * 16 * 8));
+            HIP_OK(hipMemset(fused_timing, 0, (size_t) Hr * 8 * 16 * 8));
+        }
+    }
+    return 0;
+}
+
+// After a stream synchronisation: did a fused decode launch, or a peer-to-peer collective of this tensor-parallel session,
+// time out?  (The kernels never hang: a bounded wait that expires raises a device flag and every later launch backs off, p2p_allreduce.hip.)  Then
+// the hidden states / logits behind this point are not sums over all ranks: fail the call and take the transport out of
+// service, so that later sessions of this process fall back to RCCL.
+int tllm_session::check_comm()
+{
+    if ((qkv_attn_fused || mlp_fused_dec) && fused_err)
+    {
+        // the fused projection + attention launch waits (bounded) for sibling workgroups of the same launch; an expired wait means
+        // the grid was not resident at once - the rows behind it are not attention outputs
+        uint32_t e = 0;
+        if (hipMemcpy(&e, fused_err, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        {
+            set_error("session: cannot read the fused-attention error word");
+            return 1;
+        }
+        if (e)
+        {
+            (void) hipMemset(fused_err, 0, 4);
+            qkv_attn_fused = false; // later steps take the two-launch path
+            o_fused = false;
+            mlp_fused_dec = false;  // ... and the two GEMV launches of the MLP
+            drop_graph();
+            set_error("session: a fused decode launch (QKV + attention: codes 1 - 8, MLP: 16) timed out waiting for a sibling workgroup "
+                      "(code %u); the results of this call are invalid, later steps run the unfused launches", e);
+            return kFusedTimedOut;
+        }
+    }
+    // only while the transport is IN SERVICE: once a time-out has taken it out (below), later calls run over RCCL and the
+    // words that recorded the failure must not fail them (disable_after_error clears them as well)
+    if (tp == 1 && !force_comm)
+        return 0;
+    // A time-out detected through ANOTHER live session of this process took the transport out of service (and cleared the
+    // words) since this session last looked: the launches this call replayed from its captured graph ran against the broken
+    // group - they spun to their time-out and left x / ar_norm untouched.  Fail this call too and drop the graph.
+    const uint64_t eg = comm::p2p::error_generation();
+    if (eg != comm_err_seen)
+    {
+        comm_err_seen = eg;
+        if (graph && graph_comm_gen != comm::p2p::generation())
+        {
+            drop_graph();
+            set_error("session: the peer-to-peer transport timed out (seen by another session of this process) while this "
+                      "session's captured step still used it; the results of this call are invalid, later calls use RCCL");
+            return 1;
+        }
+    }
+    if (!comm::p2p::enabled())
+        return 0;
+    uint32_t e = 0;
+    if (comm::p2p::error_flag(&e) != 0)
+    {
+        set_error("session: cannot read the peer-to-peer error flag");
+        return 1;
+    }
+    if (e)
+    {
+        comm::p2p::disable_after_error();
+        comm_err_seen = comm::p2p::error_generation();
+        drop_graph(); // the captured step holds the peer-to-peer launches
+        set_error("session: a peer-to-peer all-reduce timed out waiting for a rank (%s, epoch %u); the results of this call are "
+                  "invalid and the peer-to-peer transport is out of service on every rank of the group (later calls use RCCL)",
+            (e & 0x80000000u) ? "reported by a peer" : "on this rank", e & 0x7fffffffu);
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" {
+
+int32_t tllm_session_setup(tllm_session_t s, int32_t batch_size, int32_t max_input_len, int32_t max_new_tokens)
+{
+    return tllm_session_setup_beam(s, batch_size, 1, max_input_len, max_new_tokens);
+}
+
+int32_t tllm_session_setup_beam(tllm_session_t s, int32_t batch_size, int32_t beam_width, int32_t max_input_len,
+    int32_t max_new_tokens)
+{
+    if (!s || !s->finalized)
+    {
+        set_error("tllm_session_setup: session not finalized");
+        return 1;
+    }
+    if (batch_size < 1 || max_input_len < 1 || max_new_tokens < 0 || beam_width < 1 || beam_width > 8)
+    {
+        set_error("tllm_session_setup: bad sizes (batch %d, beam width %d in [1, 8], input %d, new %d)", batch_size, beam_width,
+            max_input_len, max_new_tokens);
+        return 1;
+    }
+    if (beam_width > 1 && (size_t) beam_width * (max_input_len + max_new_tokens) * sizeof(int32_t) > 96 * 1024)
+    {
+        // the device-side beam step stages the cache-indirection rows it re-parents in LDS (pointwise.hip beam_step_kernel)
+        set_error("tllm_session_setup: beam_width %d x max_seq_len %d exceeds the beam step's LDS staging (24576 int32)", beam_width,
+            max_input_len + max_new_tokens);
+        return 1;
+    }
+    s->free_runtime();
+    s->sampling_on = false; // a sampling configuration is set per setup (tllm_session_set_sampling)
+    s->Bc = batch_size;
+    s->beam = beam_width;
+    s->B = batch_size * beam_width;
+    s->max_in = max_input_len;
+    s->max_new = max_new_tokens;
+    s->Smax = max_input_len + max_new_tokens; // generation.py:450-461
+    RUN(s->alloc_buffers());
+    RUN(s->decide_decode_form());
+    return s->alloc_decode_form_buffers();
+}
+
+} // extern "C"

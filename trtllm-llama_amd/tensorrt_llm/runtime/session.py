@@ -1,7 +1,7 @@
 """`Session` (T/tensorrt_llm/runtime/session.py:37-160): the reference's generic engine runner - deserialise an engine, query
 its I/O, run it on a stream.  Kept because user code imports it (`from tensorrt_llm.runtime import Session`,
 `Session.from_serialized_engine`); there is no TensorRT here, so the engine is the traced LLaMA network of builder.py and the
-one thing a Session can run is that network's context phase through the C++ session (csrc/runtime/session.cpp) -
+one thing a Session can run is that network's context phase through the C++ session (csrc/runtime/session_context.cpp) -
 GenerationSession is the decode loop."""
 from dataclasses import dataclass
 from typing import Any, Dict, List
