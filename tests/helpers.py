@@ -1,4 +1,6 @@
 """Test-side helpers: call the plugin C-ABI with torch tensors (torch only owns the device memory)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -76,3 +78,13 @@ def h(x):
 
 def as_f32(t: torch.Tensor) -> np.ndarray:
     return t.detach().float().cpu().numpy()
+
+
+class GemvParams(ctypes.Structure):
+    """tllm_gemv_params_t (include/tllm_runtime_api.h): the decode GEMV's C-ABI argument"""
+    _fields_ = [('wtype', ctypes.c_int32), ('pro', ctypes.c_int32), ('epi', ctypes.c_int32), ('out_dtype', ctypes.c_int32),
+                ('M', ctypes.c_int32), ('N', ctypes.c_int32), ('K', ctypes.c_int32), ('x', ctypes.c_void_p), ('ldx', ctypes.c_int64),
+                ('w', ctypes.c_void_p), ('ldw', ctypes.c_int64), ('scale_col', ctypes.c_void_p), ('scale_row', ctypes.c_void_p),
+                ('per_channel', ctypes.c_int32), ('per_token', ctypes.c_int32), ('gamma', ctypes.c_void_p), ('eps', ctypes.c_float),
+                ('act_scale', ctypes.c_void_p), ('dyn_scale_out', ctypes.c_void_p), ('x_pro_out', ctypes.c_void_p),
+                ('residual', ctypes.c_void_p), ('epi_scale', ctypes.c_void_p), ('y', ctypes.c_void_p), ('ldy', ctypes.c_int64)]

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import GemvParams as _GemvParams
 from helpers import HostTensor, as_f32, f32, h, i8, i32, make_plugin, run_plugin
 from oracle import llama_oracle as O
 from tensorrt_llm.plugin import capi
@@ -751,15 +752,6 @@ def test_gemm_clock_probe_reports_a_plausible_shader_clock():
 
 
 # ---------------------------------------------------------------------------------------------- decode GEMM on the matrix pipe
-class _GemvParams(ctypes.Structure):
-    _fields_ = [('wtype', ctypes.c_int32), ('pro', ctypes.c_int32), ('epi', ctypes.c_int32), ('out_dtype', ctypes.c_int32),
-                ('M', ctypes.c_int32), ('N', ctypes.c_int32), ('K', ctypes.c_int32), ('x', ctypes.c_void_p), ('ldx', ctypes.c_int64),
-                ('w', ctypes.c_void_p), ('ldw', ctypes.c_int64), ('scale_col', ctypes.c_void_p), ('scale_row', ctypes.c_void_p),
-                ('per_channel', ctypes.c_int32), ('per_token', ctypes.c_int32), ('gamma', ctypes.c_void_p), ('eps', ctypes.c_float),
-                ('act_scale', ctypes.c_void_p), ('dyn_scale_out', ctypes.c_void_p), ('x_pro_out', ctypes.c_void_p),
-                ('residual', ctypes.c_void_p), ('epi_scale', ctypes.c_void_p), ('y', ctypes.c_void_p), ('ldy', ctypes.c_int64)]
-
-
 @pytest.mark.parametrize('per_channel', [1, 0])
 @pytest.mark.parametrize('m,n,k,pro,epi', [
     (8, 12288, 4096, 2, 0),    # RMSNorm + static quantiser -> QKV

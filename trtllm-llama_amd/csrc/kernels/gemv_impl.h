@@ -178,7 +178,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     const char* wbase = reinterpret_cast<const char*>(p.w);
     const char* wup = p.w_up ? reinterpret_cast<const char*>(p.w_up) : wbase + (int64_t) p.N * p.ldw;
     const int lane_kbyte = lane * 16;
-    const int64_t last_vec = p.ldw - 16;
+    // the last 16 bytes of the ROW, not of its stride: what lies between the two is the caller's (fp16 NaN bits there times a
+    // zeroed activation would still be NaN)
+    const int64_t last_vec = (int64_t) Kp * 16 / VEC - 16;
     auto rows_of_group = [&](int g, const char* (&rowptr)[R]) {
         if constexpr (SWIGLU)
         {
