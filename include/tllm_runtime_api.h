@@ -301,6 +301,21 @@ int32_t tllm_gemm(const tllm_gemm_params_t* p, tllm_stream_t stream);
  * (the `hidden_states = residual + attention_output` / `+ mlp_output` of Q/llama_model.py:78-86, which the prefill runs inside its
  * O- and down-projection GEMMs).  fp16 output only; parity tests of the multi-tile (persistent) kernels' residual path. */
 int32_t tllm_gemm_residual(const tllm_gemm_params_t* p, const void* residual, tllm_stream_t stream);
+/* tllm_gemm with either optional epilogue operand (both fp16 [M, ldc], fp16 output, not together): residual as above; silu_gate:
+ * c = fp16(fp16(silu(gate)) * fp16(epi(A W^T))), the gate half of SwiGLU that the fp16 / weight-only prefill runs inside its
+ * up-projection GEMM.  Whatever kernel the dispatch picks, including the passes behind the kernels that fuse neither. */
+int32_t tllm_gemm_epi(const tllm_gemm_params_t* p, const void* residual, const void* silu_gate, tllm_stream_t stream);
+/* EXACTLY this kernel or nothing (parity tests: a forced id that refuses the problem must not fall back silently).  Returns 0
+ * when the kernel was launched, 1 when it does not serve the problem (reason in the last-error string, c not written), a
+ * negative value on a launch error.  kernel_id: 1..65 as tllm_gemm_set_tile_cfg takes them (the ablations 21..27 / 31..33 are
+ * refused), 101..106 the weight-only kernel of kernels/gemm_woq.hip with that tile shape, TLLM_GEMM_KERNEL_REGISTER_STAGED the
+ * 128 x 128 register-staged kernel of kernels/gemm_mfma.hip (every weight type; fuses neither residual nor gate: refused). */
+#define TLLM_GEMM_KERNEL_REGISTER_STAGED 200
+int32_t tllm_gemm_kernel(const tllm_gemm_params_t* p, const void* residual, const void* silu_gate, int32_t kernel_id,
+    tllm_stream_t stream);
+/* The kernel id the static rule picks for the problem on this device when the tactic table has no entry (0: none of the
+ * LDS-DMA kernels serves it). */
+int32_t tllm_gemm_static_cfg(const tllm_gemm_params_t* p);
 /* The SmoothQuant MLP's fc and gate projections in one launch (static activation scales): c = int8 [M, ldc] =
  * sat(rni(fp16(silu16(fp16(A W^T s)) * fp16(A W_up^T s_up)) * quant_scale[0])) - the rounding points of GEMM + GEMM + SwiGLU +
  * quantiser run separately (PY/layers/mlp.py:68-73 with K/quantization.cu's static quantiser), which it replaces in the

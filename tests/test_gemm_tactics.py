@@ -48,6 +48,40 @@ def test_tactic_table_text_round_trip_and_bucket_lookup():
     lib.tllm_gemm_tactics_clear()
 
 
+def test_the_table_takes_only_ids_the_profile_can_report():
+    """host only: an imported table (the `gemm_tactics=` line of an engine header is a file from disk) is launched as it stands,
+    so it may only name what tllm_gemm_profile could have recorded for the weight type: its candidate lists and the static rule's
+    answers.  The ablation ids of gemm_sqp.hip (21-27, 31-33: wrong results on purpose) and ids of the other weight type or of no
+    kernel fail the import like a malformed line; so does a session created with such a line."""
+    import gemm_cases as GC
+    from tensorrt_llm.runtime.native import NativeSession
+    lib = _lib()
+    lib.tllm_gemm_tactics_clear()
+    ok = {3: set(GC.SQ_CANDIDATES) | set(GC.SQ_STATIC), 0: set(GC.FP16_CANDIDATES) | set(GC.FP16_STATIC)}
+    assert not (ok[3] | ok[0]) & set(GC.ABLATIONS)
+    for wt in (0, 1, 2, 3):
+        for cfg in range(1, 110):
+            rc = lib.tllm_gemm_tactics_import(f'{wt}:1024:4096:4096:{cfg}:40.00;'.encode())
+            if cfg in ok.get(wt, ()):
+                assert rc == 0 and lib.tllm_gemm_tactic_lookup(wt, 1024, 4096, 4096) == cfg, (wt, cfg)
+            else:
+                assert rc != 0 and 'parse' in capi.last_error() and f'kernel id {cfg}' in capi.last_error(), (wt, cfg)
+            lib.tllm_gemm_tactics_clear()
+    # an entry without a kernel (cfg 0: "nothing profiled") is skipped as before
+    assert lib.tllm_gemm_tactics_import(b'3:1024:4096:4096:0:0.00;') == 0 and _export(lib) == ''
+    cfg = dict(num_layers=1, num_heads=2, hidden_size=64, inter_size=24, vocab_size=128, quant_mode=0)
+    for bad in ('3:1024:12288:4096:22:45.10;', '0:256:192:256:8:11.50;0:1024:4096:4096:63:40.00;'):
+        with pytest.raises(RuntimeError, match='parse'):
+            NativeSession(dict(cfg, gemm_tactics=bad))
+    lib.tllm_gemm_tactics_clear()
+    # the same ids through the kernel-level entry: refused before anything is launched
+    lib.tllm_gemm_kernel.restype = ctypes.c_int32
+    lib.tllm_gemm_kernel.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    q = (ctypes.c_int32 * 24)(3, 1, 300, 456, 1152)  # tllm_gemm_params_t: wtype, out_dtype, M, N, K, null pointers
+    for cfg in GC.ABLATIONS:
+        assert lib.tllm_gemm_kernel(q, None, None, cfg, None) == 1 and 'ablation' in capi.last_error()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('wtype,m,n,k', [(3, 1024, 4096, 4096), (3, 300, 456, 1152), (0, 256, 1024, 512)])
 def test_profile_picks_a_kernel_and_the_gemm_stays_exact(wtype, m, n, k):

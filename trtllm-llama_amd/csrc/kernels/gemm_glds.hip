@@ -594,10 +594,10 @@ int gemm_static_cfg(const GemmParams& p)
     if (!glds_serves(p))
         return 0;
     const int cfg = static_shape_cfg(p);
-    // (SmoothQuant: the persistent forms 62 / 63 of gemm_sqp.hip serve fp16 output on 16-byte rows; launch_gemm_glds falls back
-    // to the one-tile-per-workgroup forms 42 / 20 for the rest)
+    // (the persistent forms 62 / 63 and 56 / 55 of gemm_sqp.hip serve fp16 output on 16-byte rows from two K-tiles on - K >= 256
+    // SmoothQuant, K >= 128 fp16; launch_gemm_glds falls back to the one-tile-per-workgroup forms 42 / 20, 54 / 50 for the rest)
     const bool persist = p.out_dtype == DT_HALF && !(p.ldc & 7) && !(p.N & 7) && !(reinterpret_cast<uintptr_t>(p.c) & 15)
-        && p.K >= 256;
+        && p.K >= (p.wtype == W_INT8_SQ ? 256 : 128);
     if (cfg == kPhased256x128)
         return p.wtype == W_INT8_SQ ? (persist ? 62 : 42) : (persist ? 56 : 54);
     // the 256 x 192 tile runs its phased sibling (gemm_sqp.hip)

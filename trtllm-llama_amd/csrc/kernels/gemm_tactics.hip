@@ -43,6 +43,22 @@ std::map<Key, Entry> g_table;
 const int kSqCandidates[] = {63, 20, 8, 62, 64, 65, 42, 6, 15, 18, 1, 3, 2, 4}; // 64 / 65: split-K-2 of the 256 x 128 / 128 x 128 tile (r06)
 const int kFp16Candidates[] = {55, 6, 8, 50, 56, 57, 58, 54, 51, 52, 53, 1, 3, 2, 4, 5, 7}; // 50..: the phased pipeline on fp16 operands (gemm_sqp.hip)
 
+// what gemm_static_cfg (gemm_glds.hip) can return: the incumbent is timed and may win without being a candidate
+const int kSqStatic[] = {8, 2, 4, 63, 20, 62, 42};
+const int kFp16Static[] = {8, 2, 4, 55, 50, 56, 54};
+
+// an id gemm_profile could have recorded for this weight type; anything else in an imported table (the engine header is a file
+// from disk) would be launched by launch_gemm_glds as it stands - the ablation ids of gemm_sqp.hip give wrong results on purpose
+bool tactic_id_ok(int wtype, int cfg)
+{
+    auto in = [cfg](const int* v, size_t n) { return std::find(v, v + n, cfg) != v + n; };
+    if (wtype == W_INT8_SQ)
+        return in(kSqCandidates, sizeof(kSqCandidates) / sizeof(int)) || in(kSqStatic, sizeof(kSqStatic) / sizeof(int));
+    if (wtype == W_FP16)
+        return in(kFp16Candidates, sizeof(kFp16Candidates) / sizeof(int)) || in(kFp16Static, sizeof(kFp16Static) / sizeof(int));
+    return false;
+}
+
 __global__ void fill_random_kernel(uint32_t* p, size_t n_words, uint32_t seed, int fp16)
 {
     for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (size_t) gridDim.x * blockDim.x)
@@ -132,6 +148,11 @@ int gemm_tactics_import(const char* text)
         }
         if (cfg > 0 && M > 0 && N > 0 && K > 0)
         {
+            if (!tactic_id_ok(wt, cfg))
+            {
+                set_error("gemm tactics: cannot parse '%.40s': kernel id %d is not one the profile reports for weight type %d", p, cfg, wt);
+                return -1;
+            }
             g_table[Key(wt, M, N, K)] = Entry{cfg, us};
             ++n;
         }

@@ -356,23 +356,40 @@ int launch_woq_bits(const GemmParams& p, int cfg, hipStream_t stream)
 
 int gemm_woq_tune_cfg = 0; // test / bench override (tllm_gemm_set_tile_cfg 101..106 -> 1..6)
 
-// returns 0 on success, -1 on a launch error, 1 when the problem is not served (caller falls back to the expanded path)
-int launch_gemm_woq(const GemmParams& p, hipStream_t stream)
+// the problems this kernel takes, whatever the tile shape
+static bool woq_serves(const GemmParams& p)
 {
     const bool w8 = p.wtype == W_INT8_WOQ, w4 = p.wtype == W_INT4_WOQ;
     if (!w8 && !w4)
-        return 1;
+        return false;
     if ((reinterpret_cast<uintptr_t>(p.a) & 15) || ((p.lda * 2) & 15) || (reinterpret_cast<uintptr_t>(p.w) & 15) || (p.ldw & 15)
         || (p.K % 64) || p.K <= 0 || p.M < 32 || !p.scale_col)
-        return 1;
+        return false;
     if (p.out_dtype != DT_HALF && p.out_dtype != DT_FLOAT)
-        return 1;
+        return false;
     if (p.residual && (p.out_dtype != DT_HALF))
-        return 1;
+        return false;
     if (p.silu_gate
         && (p.residual || p.out_dtype != DT_HALF || (p.ldc & 7) || (p.N & 7) || (reinterpret_cast<uintptr_t>(p.c) & 15)
             || (reinterpret_cast<uintptr_t>(p.silu_gate) & 15)))
-        return 1; // the fused SwiGLU gate lives in the vector epilogue
+        return false; // the fused SwiGLU gate lives in the vector epilogue
+    return true;
+}
+
+// exactly tile shape `cfg` (1..6), no fall-back: 0 launched, -1 launch error, 1 not served (tllm_gemm_kernel ids 101..106)
+int launch_gemm_woq_cfg(const GemmParams& p, int cfg, hipStream_t stream)
+{
+    if (cfg < 1 || cfg > 6 || !woq_serves(p))
+        return 1;
+    return p.wtype == W_INT8_WOQ ? launch_woq_bits<8>(p, cfg, stream) : launch_woq_bits<4>(p, cfg, stream);
+}
+
+// returns 0 on success, -1 on a launch error, 1 when the problem is not served (caller falls back to the expanded path)
+int launch_gemm_woq(const GemmParams& p, hipStream_t stream)
+{
+    const bool w8 = p.wtype == W_INT8_WOQ;
+    if (!woq_serves(p))
+        return 1;
     int cfg = gemm_woq_tune_cfg;
     if (cfg <= 0)
     {

@@ -22,6 +22,10 @@ extern int gemm_tune_cfg;
 extern int gemm_woq_tune_cfg;
 extern bool gemm_swiglu_one_tile; // gemm_sqp.hip: A/B hook
 extern void* gemm_clock_probe;
+int launch_gemm_cfg(const GemmParams& p, int cfg, hipStream_t stream);     // gemm_glds.hip: exactly this kernel id, 1 = not served
+int gemm_static_cfg(const GemmParams& p);                                    // gemm_glds.hip
+int launch_gemm_woq_cfg(const GemmParams& p, int cfg, hipStream_t stream); // gemm_woq.hip: exactly this tile shape, 1 = not served
+int launch_gemm_mfma(const GemmParams& p, hipStream_t stream);             // gemm_mfma.hip
 }
 } // namespace tllm
 
@@ -97,6 +101,61 @@ int32_t tllm_gemm_residual(const tllm_gemm_params_t* q, const void* residual, tl
     GemmParams g = gemm_params(q);
     g.residual = residual;
     return launch_gemm(g, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gemm_epi(const tllm_gemm_params_t* q, const void* residual, const void* silu_gate, tllm_stream_t stream)
+{
+    if (!q)
+        return 1;
+    GemmParams g = gemm_params(q);
+    g.residual = residual;
+    g.silu_gate = silu_gate;
+    return launch_gemm(g, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gemm_kernel(const tllm_gemm_params_t* q, const void* residual, const void* silu_gate, int32_t kernel_id,
+    tllm_stream_t stream)
+{
+    if (!q)
+    {
+        set_error("tllm_gemm_kernel: null argument");
+        return 1;
+    }
+    GemmParams g = gemm_params(q);
+    g.residual = residual;
+    g.silu_gate = silu_gate;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = 1;
+    const char* why = "this kernel does not take the problem (weight type, alignment, K, M, output type or epilogue)";
+    if (g.M <= 0 || g.N <= 0 || g.K <= 0)
+        why = "empty problem";
+    else if (residual && silu_gate)
+        why = "the residual and the SwiGLU gate exclude each other";
+    else if ((kernel_id >= 21 && kernel_id <= 27) || (kernel_id >= 31 && kernel_id <= 33))
+        why = "an ablation of the phased pipeline (wrong results on purpose): microbench only";
+    else if (kernel_id >= 1 && kernel_id <= 65)
+        rc = launch_gemm_cfg(g, kernel_id, s);
+    else if (kernel_id >= 101 && kernel_id <= 106)
+        rc = launch_gemm_woq_cfg(g, kernel_id - 100, s);
+    else if (kernel_id == TLLM_GEMM_KERNEL_REGISTER_STAGED)
+    {
+        if (residual || silu_gate)
+            why = "the register-staged kernel fuses neither the residual nor the SwiGLU gate";
+        else if ((g.wtype == W_INT8_WOQ || g.wtype == W_INT4_WOQ) && !g.scale_col)
+            why = "weight-only weights need their scales";
+        else
+            rc = launch_gemm_mfma(g, s);
+    }
+    else
+        why = "no such kernel id";
+    if (rc > 0)
+        set_error("tllm_gemm_kernel: kernel id %d refuses %d x %d x %d (wtype %d): %s", kernel_id, g.M, g.N, g.K, g.wtype, why);
+    return rc;
+}
+
+int32_t tllm_gemm_static_cfg(const tllm_gemm_params_t* q)
+{
+    return q ? gemm_static_cfg(gemm_params(q)) : 0;
 }
 
 int32_t tllm_gemm_profile(int32_t wtype, int32_t M, int32_t N, int32_t K, int32_t* best_cfg, float* best_us, tllm_stream_t stream)
