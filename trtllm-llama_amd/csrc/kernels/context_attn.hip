@@ -14,6 +14,7 @@
 #include "dev_utils.h"
 #include "kernels.h"
 #include "launch_util.h"
+#include "lds_dma.h"
 #include <atomic>
 #include <cstdlib>
 
@@ -25,34 +26,6 @@ using namespace dev;
 
 namespace
 {
-
-__device__ __forceinline__ void h8_to_f(const uint4& v, float* f)
-{
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-    {
-        h2_t h = u32_as_h2(w[j]);
-        f[2 * j] = (float) h.x;
-        f[2 * j + 1] = (float) h.y;
-    }
-}
-
-__device__ __forceinline__ uint4 f_to_h8(const float* f)
-{
-    return make_uint4(pack_h2(f[0], f[1]), pack_h2(f[2], f[3]), pack_h2(f[4], f[5]), pack_h2(f[6], f[7]));
-}
-
-__device__ __forceinline__ uint2 quant8(const uint4& v, float s)
-{
-    float f[8];
-    h8_to_f(v, f);
-    uint32_t o[2] = {0, 0};
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        o[j >> 2] |= ((uint32_t) (uint8_t) f2i8_rni_sat(f[j] * s)) << (8 * (j & 3));
-    return make_uint2(o[0], o[1]);
-}
 
 // first row of sequence b in the (padded or packed) token-major buffers
 __device__ __forceinline__ int64_t seq_row0(const ContextAttnParams& p, int b)
@@ -375,18 +348,6 @@ __global__ __launch_bounds__(256) void context_attn_kernel(const ContextAttnPara
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void glds16(const void* gptr, uint32_t lds_byte)
-{
-    // inline asm on purpose: see gemm_glds.hip (the builtin makes hipcc drain the DMA before the next ds_read)
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(gptr), "s"(lds_byte) : "memory");
-}
-
-__device__ __forceinline__ int swz128(int row, int c16)
-{
-    return row * 128 + ((c16 ^ ((row >> 1) & 7)) << 4);
-}
-
 
 // The MFMA kernel launch_dh uses (key-split; r01's 4 compute + 4 loader wave form was removed in r05): 2 NQ compute waves (NQ = 4: two per SIMD), no loader waves.
 // Waves w and w + NQ serve the same 32 queries and split every 64-key block between them (keys 32 kh .. 32 kh + 31, kh = w / NQ):
@@ -578,7 +539,7 @@ __global__ __launch_bounds__(128 * NQ) void context_attn_mfma_ks_kernel(const Co
         uint4 kfr[KST];
 #pragma unroll
         for (int s = 0; s < KST; ++s)
-            kfr[s] = *reinterpret_cast<const uint4*>(Ks + (s >> 2) * (64 * 128) + swz128(kh * 32 + krow, (2 * s + hf) & 7));
+            kfr[s] = *reinterpret_cast<const uint4*>(Ks + (s >> 2) * (64 * 128) + swz<128>(kh * 32 + krow, (2 * s + hf) & 7));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < KST; ++s)
@@ -597,7 +558,7 @@ __global__ __launch_bounds__(128 * NQ) void context_attn_mfma_ks_kernel(const Co
         for (int s2l = 0; s2l < 2; ++s2l)
 #pragma unroll
             for (int i = 0; i < DT; ++i)
-                vfr[s2l][i] = *reinterpret_cast<const uint4*>(Vs + swz128(i * 32 + ql, 2 * (2 * kh + s2l) + hf));
+                vfr[s2l][i] = *reinterpret_cast<const uint4*>(Vs + swz<128>(i * 32 + ql, 2 * (2 * kh + s2l) + hf));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
@@ -789,13 +750,7 @@ int launch_dh(const ContextAttnParams& p, hipStream_t stream)
                 return -1;
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("context attention launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("context attention");
 }
 
 } // namespace

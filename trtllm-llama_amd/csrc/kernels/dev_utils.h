@@ -78,6 +78,18 @@ __device__ __forceinline__ uint4 epi_silu_gate8(const uint4& u, const uint4& g)
     return make_uint4(o4[0], o4[1], o4[2], o4[3]);
 }
 
+// SwiGLU on two fp32 GEMV results, in the epilogue of the launch that computed both (gemv_impl.h, gemv_mfma_sq.hip, mlp_fused.hip:
+// their bit-identity claims rest on this being one function)
+__device__ __forceinline__ float silu_mul_fp16(float g, float u)
+{
+    // fp16 rounding points of the reference graph: inter = fc(x) (fp16) ; a = inter * sigmoid(inter) (fp16) ;
+    // out = a * gate(x) (fp16)   (PY/layers/mlp.py:68-73, PY/functional.py:521-532)
+    const float g16 = h2f(f2h(g));
+    const float u16 = h2f(f2h(u));
+    const float a = h2f(f2h(g16 / (1.f + __expf(-g16))));
+    return h2f(f2h(a * u16));
+}
+
 __device__ __forceinline__ h2_t u32_as_h2(uint32_t u)
 {
     h2_t r;
@@ -98,6 +110,48 @@ __device__ __forceinline__ uint32_t pack_h2(float lo, float hi)
     r.x = (_Float16) lo;
     r.y = (_Float16) hi;
     return h2_as_u32(r);
+}
+
+// 8 fp16 (16 bytes) <-> 8 floats
+__device__ __forceinline__ void h8_to_f(const uint4& v, float* f)
+{
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+    {
+        h2_t h = u32_as_h2(w[j]);
+        f[2 * j] = (float) h.x;
+        f[2 * j + 1] = (float) h.y;
+    }
+}
+
+__device__ __forceinline__ uint4 f_to_h8(const float* f)
+{
+    return make_uint4(pack_h2(f[0], f[1]), pack_h2(f[2], f[3]), pack_h2(f[4], f[5]), pack_h2(f[6], f[7]));
+}
+
+// 8 fp16 -> 8 int8 of the KV cache: sat(rni(float(x16) * s))   (…Utils.h:2383-2390, 2276-2286)
+__device__ __forceinline__ uint2 quant8(const uint4& v, float s)
+{
+    float f[8];
+    h8_to_f(v, f);
+    uint32_t o[2] = {0, 0};
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        o[j >> 2] |= ((uint32_t) (uint8_t) f2i8_rni_sat(f[j] * s)) << (8 * (j & 3));
+    return make_uint2(o[0], o[1]);
+}
+
+// LDS image [row][BKB bytes], BKB = 128 or 64: byte offset of 16-byte piece c16 of tile row `row`, XOR-swizzled so that the 16
+// lanes of a ds_read_b128 phase (16 consecutive rows, same k-piece) hit 16 different 16-byte bank groups
+template <int BKB>
+__device__ __forceinline__ int swz(int row, int c16)
+{
+    static_assert(BKB == 128 || BKB == 64, "rows of 128 or 64 bytes");
+    if constexpr (BKB == 128)
+        return row * 128 + ((c16 ^ ((row >> 1) & 7)) << 4);
+    else
+        return row * 64 + ((c16 ^ ((row >> 2) & 3)) << 4);
 }
 
 // fp32 += a.lo*b.lo + a.hi*b.hi with fp16 operands (v_dot2_f32_f16: exact products, fp32 accumulate).

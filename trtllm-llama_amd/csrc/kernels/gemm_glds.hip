@@ -20,6 +20,7 @@
 #include "dev_utils.h"
 #include "kernels.h"
 #include "launch_util.h"
+#include "lds_dma.h"
 #include <atomic>
 #include <map>
 
@@ -45,42 +46,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void gbl_void_t;
-
-// One LDS-DMA instruction: 64 lanes x 16 bytes from per-lane global addresses to LDS [m0 + lane * 16].
-// Issued from inline asm ON PURPOSE: for the builtin hipcc places `s_waitcnt vmcnt(0)` in front of the next ds_read (it
-// cannot prove the DMA targets the other buffer), which serialises the DMA of tile t+1 with the MFMAs of tile t.  With
-// the asm form the compiler sees no outstanding VMEM operation; the kernel waits by hand (vmcnt(0) before the barrier
-// that publishes the tile).
-__device__ __forceinline__ void glds16(const void* gptr, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(gptr), "s"(lds_byte) : "memory");
-}
-
-// the same from a wave-uniform base + a per-lane 32-bit offset
-__device__ __forceinline__ void glds16s(const char* base, uint32_t off, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(off), "s"(base), "s"(lds_byte) : "memory");
-}
-
-// byte offset of 16-byte piece c16 of tile row `row`: XOR swizzle so that the 16 lanes of a ds_read_b128 phase
-// (16 consecutive rows, same k-piece) hit 16 different 16-byte bank groups
-template <int BKB>
-__device__ __forceinline__ int swz(int row, int c16)
-{
-    if constexpr (BKB == 128)
-        return row * 128 + ((c16 ^ ((row >> 1) & 7)) << 4);
-    else
-        return row * 64 + ((c16 ^ ((row >> 2) & 3)) << 4);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // LW > 0: LW extra waves that do nothing but issue the LDS-DMA.  One wave sustains about one LDS-DMA instruction per ~150
 // cycles whatever else it does (the instruction holds its issuer for 100 - 185 cycles), which in the 8-wave 256 x 192 shape is a
@@ -487,13 +452,7 @@ int launch_cfg(const GemmParams& p, hipStream_t stream)
     launch_util::ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), smem);
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     hipLaunchKernelGGL(kfn, dim3(tiles), dim3(64 * (WM * WN * KG + LW)), smem, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("gemm_glds launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("gemm_glds");
 }
 
 // production tile shapes: id -> (BM, BN); the ids index launch_wt's table, the other ids there are the measured

@@ -14,6 +14,7 @@
 // K-slab's 32-byte half; C/D: col = l & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5).
 #include "dev_utils.h"
 #include "kernels.h"
+#include "launch_util.h"
 #include "weight_layout.h"
 
 namespace tllm
@@ -31,13 +32,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BM = 128, BN = 128, BKB = 64; // BKB: bytes of K per operand row per slab (in the LDS image)
-
-// byte offset of 16-byte chunk `c` (0..3) of row `r` inside a [128][64 B] tile, XOR-swizzled so that 16 lanes
-// reading the same chunk of 16 consecutive rows hit 16 different 16-byte bank groups
-__device__ __forceinline__ int swz(int r, int c)
-{
-    return r * BKB + ((c ^ ((r >> 2) & 3)) << 4);
-}
 
 // u8 (q + 128) x16 -> 16 fp16 (q exactly), two uint4
 __device__ __forceinline__ void dequant_u8x16(const uint4& w, uint4& lo, uint4& hi)
@@ -135,29 +129,29 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(const GemmParams p)
         char* Bs = lds[buf][1];
 #pragma unroll
         for (int h = 0; h < 2; ++h)
-            *reinterpret_cast<uint4*>(As + swz(lr + h * 64, lc)) = ra[h];
+            *reinterpret_cast<uint4*>(As + swz<BKB>(lr + h * 64, lc)) = ra[h];
         if constexpr (WT == W_INT8_SQ || WT == W_FP16)
         {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                *reinterpret_cast<uint4*>(Bs + swz(lr + h * 64, lc)) = rb[h];
+                *reinterpret_cast<uint4*>(Bs + swz<BKB>(lr + h * 64, lc)) = rb[h];
         }
         else if constexpr (WT == W_INT8_WOQ)
         {
             const int r = tid >> 1, hf = tid & 1;
             uint4 lo, hi;
             dequant_u8x16(rb[0], lo, hi);
-            *reinterpret_cast<uint4*>(Bs + swz(r, hf * 2)) = lo;
-            *reinterpret_cast<uint4*>(Bs + swz(r, hf * 2 + 1)) = hi;
+            *reinterpret_cast<uint4*>(Bs + swz<BKB>(r, hf * 2)) = lo;
+            *reinterpret_cast<uint4*>(Bs + swz<BKB>(r, hf * 2 + 1)) = hi;
         }
         else
         {
             if (tid < BN)
             {
-                *reinterpret_cast<uint4*>(Bs + swz(tid, 0)) = dequant_u4x8(rb[0].x);
-                *reinterpret_cast<uint4*>(Bs + swz(tid, 1)) = dequant_u4x8(rb[0].y);
-                *reinterpret_cast<uint4*>(Bs + swz(tid, 2)) = dequant_u4x8(rb[0].z);
-                *reinterpret_cast<uint4*>(Bs + swz(tid, 3)) = dequant_u4x8(rb[0].w);
+                *reinterpret_cast<uint4*>(Bs + swz<BKB>(tid, 0)) = dequant_u4x8(rb[0].x);
+                *reinterpret_cast<uint4*>(Bs + swz<BKB>(tid, 1)) = dequant_u4x8(rb[0].y);
+                *reinterpret_cast<uint4*>(Bs + swz<BKB>(tid, 2)) = dequant_u4x8(rb[0].z);
+                *reinterpret_cast<uint4*>(Bs + swz<BKB>(tid, 3)) = dequant_u4x8(rb[0].w);
             }
         }
     };
@@ -190,8 +184,8 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(const GemmParams p)
 #pragma unroll
             for (int i = 0; i < 2; ++i)
             {
-                af[i] = *reinterpret_cast<const uint4*>(As + swz(wm * 64 + i * 32 + fr, ks * 2 + fk));
-                bf[i] = *reinterpret_cast<const uint4*>(Bs + swz(wn * 64 + i * 32 + fr, ks * 2 + fk));
+                af[i] = *reinterpret_cast<const uint4*>(As + swz<BKB>(wm * 64 + i * 32 + fr, ks * 2 + fk));
+                bf[i] = *reinterpret_cast<const uint4*>(Bs + swz<BKB>(wn * 64 + i * 32 + fr, ks * 2 + fk));
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -273,13 +267,7 @@ int launch_wt(const GemmParams& p, hipStream_t stream)
 {
     dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM);
     hipLaunchKernelGGL((gemm_mfma_kernel<WT>), grid, dim3(256), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("gemm_mfma launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("gemm_mfma");
 }
 
 } // namespace

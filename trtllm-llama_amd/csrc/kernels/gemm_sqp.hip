@@ -24,6 +24,7 @@
 #include "dev_utils.h"
 #include "kernels.h"
 #include "launch_util.h"
+#include "lds_dma.h"
 #include <atomic>
 #include <cstdlib>
 #include <map>
@@ -44,27 +45,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) unsigned gu32;
 constexpr int kKsplitFlagBytes = 8192; // split-K: two flag words per tile at the head of the workspace (<= 1024 tiles)
-
-// one LDS-DMA instruction: 64 lanes x 16 bytes, global (wave-uniform base + per-lane 32-bit offset) -> LDS [m0 + lane * 16]
-__device__ __forceinline__ void glds16s(const char* base, uint32_t off, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(off), "s"(base), "s"(lds_byte) : "memory");
-}
-
-// 4 bytes per lane from per-lane 64-bit addresses (scales of two different tensors in one chunk)
-__device__ __forceinline__ void glds4v(const void* gptr, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(gptr), "s"(lds_byte) : "memory");
-}
-
-// the same with 4 bytes per lane (scales)
-__device__ __forceinline__ void glds4s(const char* base, uint32_t off, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(off), "s"(base), "s"(lds_byte) : "memory");
-}
 
 __device__ __forceinline__ int swz_g(int row)
 {
@@ -1003,13 +983,7 @@ int launch_sqp(const GemmParams& pin, hipStream_t stream)
         }
     }
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * WR * WC), smem, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("gemm_sqp launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("gemm_sqp");
 }
 
 } // namespace

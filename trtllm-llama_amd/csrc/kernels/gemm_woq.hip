@@ -28,6 +28,7 @@
 #include "dev_utils.h"
 #include "kernels.h"
 #include "launch_util.h"
+#include "lds_dma.h"
 #include <atomic>
 
 namespace tllm
@@ -42,19 +43,6 @@ namespace
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void_t;
-
-__device__ __forceinline__ void glds16(const void* gptr, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(gptr), "s"(lds_byte) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // 4 bytes u = q + 128 -> 4 fp16 q (two words), exactly: 0x6400 | u = 1024 + u, minus 1152
 __device__ __forceinline__ void deq_u8x4(uint32_t w, uint32_t& lo, uint32_t& hi)
@@ -329,13 +317,7 @@ int launch_woq_cfg(const GemmParams& p, hipStream_t stream)
     launch_util::ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), smem);
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     hipLaunchKernelGGL(kfn, dim3(tiles), dim3(64 * WM * WN), smem, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("gemm_woq launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("gemm_woq");
 }
 
 template <int BITS>

@@ -131,16 +131,6 @@ __device__ __forceinline__ int dot_sq(const uint4& w, const uint4& x, int acc)
     return acc;
 }
 
-__device__ __forceinline__ float silu_mul_fp16(float g, float u)
-{
-    // fp16 rounding points of the reference graph: inter = fc(x) (fp16) ; a = inter * sigmoid(inter) (fp16) ;
-    // out = a * gate(x) (fp16)   (PY/layers/mlp.py:68-73, PY/functional.py:521-532)
-    const float g16 = h2f(f2h(g));
-    const float u16 = h2f(f2h(u));
-    const float a = h2f(f2h(g16 / (1.f + __expf(-g16))));
-    return h2f(f2h(a * u16));
-}
-
 // ---- the kernel --------------------------------------------------------------------------------
 // LDS map: [0,256) reduction scratch | MB rows of Kp activations (fp16, or s8 for SmoothQuant)
 //
@@ -705,13 +695,7 @@ int launch_inst(const GemvArgs& a, hipStream_t stream)
         blocks = (a.ngroups + 4 * groups_per_wave - 1) / (4 * groups_per_wave);
     }
     hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), smem, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("gemv launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("gemv");
 }
 
 template <int WT, int PK, int EK, int NXV>

@@ -180,13 +180,7 @@ int launch_gemv_ksplit(const GemvArgs& a, hipStream_t stream)
     case W_INT4_WOQ: launch_nc<W_INT4_WOQ, KSplit<W_INT4_WOQ>::NCMAX>(a, per_wave, stream); break;
     default: launch_nc<W_INT8_SQ, KSplit<W_INT8_SQ>::NCMAX>(a, per_wave, stream); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("gemv (k-split) launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("gemv (k-split)");
 }
 
 } // namespace kernels

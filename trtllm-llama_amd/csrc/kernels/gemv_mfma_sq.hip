@@ -27,6 +27,7 @@
 #include "gemv_args.h"
 #include "kernels.h"
 #include "launch_util.h"
+#include "lds_dma.h"
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
@@ -41,22 +42,6 @@ namespace
 {
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int kRows = 8; // activation rows in LDS; row kRows is all zeros
-
-__device__ __forceinline__ float silu_mul_fp16_(float g, float u)
-{
-    // fp16 rounding points of the reference graph (gemv_impl.h silu_mul_fp16; PY/layers/mlp.py:68-73)
-    const float g16 = h2f(f2h(g));
-    const float u16 = h2f(f2h(u));
-    const float a = h2f(f2h(g16 / (1.f + __expf(-g16))));
-    return h2f(f2h(a * u16));
-}
-
-// one LDS-DMA instruction: 64 lanes x 16 bytes, global (wave-uniform base + per-lane 32-bit offset) -> LDS [lds_byte + lane * 16]
-__device__ __forceinline__ void glds16(const char* base, uint32_t off, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(off), "s"(base), "s"(lds_byte) : "memory");
-}
 
 // NXV = 0: int8 activations as given (PRO_NONE); else RMSNorm + static quantiser, a thread keeps NXV 16-byte vectors of a row.
 // D = slots of a wave's weight ring.  A slot = one 256-byte K block of the wave's 16 rows (4 KB; SwiGLU: gate + up, 8 KB), filled by
@@ -102,12 +87,12 @@ __global__ __launch_bounds__(256) void gemv_mfma_sq_kernel(const GemvParams p, i
         const uint32_t slot = ring + (uint32_t) (q % D) * SLOT;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            glds16(wbase + goff, dma_off[i], slot + i * 1024);
+            glds16s_nt(wbase + goff, dma_off[i], slot + i * 1024);
         if constexpr (SWIGLU)
         {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                glds16(ubase + goff, dma_off[i], slot + 4096 + i * 1024);
+                glds16s_nt(ubase + goff, dma_off[i], slot + 4096 + i * 1024);
         }
     };
     for (int q = 0; q < D - 1 && q < total; ++q)
@@ -278,7 +263,7 @@ __global__ __launch_bounds__(256) void gemv_mfma_sq_kernel(const GemvParams p, i
                 for (int e = 0; e < 4; ++e)
                 {
                     const float s1 = su ? su[p.per_channel ? n0 + e : 0] : sc[p.per_channel ? p.N + n0 + e : 0];
-                    o16[e] = silu_mul_fp16_(r0[e], (float) vu[e] * (s1 * rsu));
+                    o16[e] = silu_mul_fp16(r0[e], (float) vu[e] * (s1 * rsu));
                 }
                 if (p.epi == EPI_SWIGLU)
                     *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(p.y) + o) = make_uint2(
@@ -369,13 +354,7 @@ int launch_inst(const GemvParams& p, int pitch, int ngroups, int grid, size_t sm
         attr_set.store(smem);
     }
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), smem, stream, p, pitch, ngroups);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("gemv_mfma_sq launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("gemv_mfma_sq");
 }
 
 template <int NXV, bool SWIGLU>

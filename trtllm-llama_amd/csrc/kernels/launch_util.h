@@ -1,7 +1,9 @@
 // Host-side launch state keyed by DEVICE (a process may hold sessions on devices with different CU counts, and a
 // function attribute raised on one device says nothing about another): CU count, "dynamic-LDS attribute raised for this kernel on
 // this device", occupancy of an instance.  Header-only; the statics of an inline function are one object per shared library.
+// And the check every launcher ends with.
 #pragma once
+#include "kernels.h"
 #include <hip/hip_runtime.h>
 #include <map>
 #include <mutex>
@@ -69,6 +71,17 @@ inline int blocks_per_cu(const void* kfn, int threads, size_t dyn_lds)
         it = cache.emplace(key, nb).first;
     }
     return it->second;
+}
+// after hipLaunchKernelGGL: 0, or -1 with "<what> launch failed: <hip string>" as the error
+inline int check_launch(const char* what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+    {
+        set_error("%s launch failed: %s", what, hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
 }
 } // namespace launch_util
 } // namespace kernels

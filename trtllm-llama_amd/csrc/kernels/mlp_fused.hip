@@ -57,15 +57,6 @@ constexpr int kKC = 4;         // K = 4096 int8 = 4 x 1 KiB chunks per gate|up r
 constexpr int kRowsPerWg = 16; // down-projection rows per workgroup (one per wave)
 constexpr int kMaxPairs = 4;   // gate|up row pairs per wave at most (2 or 3 here)
 
-__device__ __forceinline__ float silu_mul_fp16_m(float g, float u)
-{
-    // fp16 rounding points of the reference graph (gemv_impl.h silu_mul_fp16: PY/layers/mlp.py:68-73, PY/functional.py:521-532)
-    const float g16 = h2f(f2h(g));
-    const float u16 = h2f(f2h(u));
-    const float a = h2f(f2h(g16 / (1.f + __expf(-g16))));
-    return h2f(f2h(a * u16));
-}
-
 // Bounded wait until word 0 of all 16 lines at g carries `tag` (false: gave up).  Agent-scope VECTOR loads, 16 lanes, one line
 // each: they return in this wave's own order (behind ITS rows, ~1 us), not behind the whole CU's.  (The scalar path - s_load_dword
 // glc x 16 - answers in ~1.5 us in a probe, tools/scalar_poll_probe.cpp, but here made the launch 50 - 70 us: the leader saw its
@@ -251,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void mlp_fused_kernel(const FusedMlpParam
         a1 = wave_sum(a1);
         // epilogue of gemv_impl.h (EPI_SWIGLU_QSTATIC): fp16 rounding points of the reference graph, then the static quantiser
         const float r0 = (float) a0 * (s0 * rs_fc);
-        const float o16 = silu_mul_fp16_m(r0, (float) a1 * (s1 * rs_gate));
+        const float o16 = silu_mul_fp16(r0, (float) a1 * (s1 * rs_gate));
         if (lane == 0)
             obuf[n - pair0] = (char) f2i8_rni_sat(o16 * epi_q);
     };

@@ -32,6 +32,7 @@
 //   element (b, kv, h, t, d) at ((b*2 + kv)*H + h)*Smax*Dh + t*Dh + d.
 #include "dev_utils.h"
 #include "kernels.h"
+#include "launch_util.h"
 #include <math.h>
 
 namespace tllm
@@ -55,23 +56,6 @@ struct MmhaGeom
     static constexpr int TCHUNK = NGRP * NIT; // timesteps per workgroup (NIT rows of K and of V per lane group)
 };
 
-__device__ __forceinline__ void h8_to_f(const uint4& v, float* f)
-{
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-    {
-        h2_t h = u32_as_h2(w[j]);
-        f[2 * j] = (float) h.x;
-        f[2 * j + 1] = (float) h.y;
-    }
-}
-
-__device__ __forceinline__ uint4 f_to_h8(const float* f)
-{
-    return make_uint4(pack_h2(f[0], f[1]), pack_h2(f[2], f[3]), pack_h2(f[4], f[5]), pack_h2(f[6], f[7]));
-}
-
 // 8 cached int8 -> 8 fp16: fp16(float(q) * s)   (…Utils.h:2358-2365)
 __device__ __forceinline__ uint4 dequant8(const uint2& q, float s)
 {
@@ -85,18 +69,6 @@ __device__ __forceinline__ uint4 dequant8(const uint2& q, float s)
         f[4 + j] = fmaf((float) ((b >> (8 * j)) & 0xffu), s, nb);
     }
     return f_to_h8(f);
-}
-
-// 8 fp16 -> 8 int8: sat(rni(float(x16) * s))   (…Utils.h:2383-2390, 2276-2286)
-__device__ __forceinline__ uint2 quant8(const uint4& v, float s)
-{
-    float f[8];
-    h8_to_f(v, f);
-    uint32_t o[2] = {0, 0};
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        o[j >> 2] |= ((uint32_t) (uint8_t) f2i8_rni_sat(f[j] * s)) << (8 * (j & 3));
-    return make_uint2(o[0], o[1]);
 }
 
 // ---- kernel 1: one workgroup per (split, head, batch) -> partial {max, sum, out[DH]} in the workspace
@@ -632,13 +604,7 @@ int launch_nit(const MmhaParams& p, hipStream_t stream)
 #undef TLLM_MMHA_LAUNCH
     if (!p.tail_tickets)
         hipLaunchKernelGGL((mmha_combine_kernel<DH, NIT>), dim3(p.num_heads, p.batch), dim3(256), 0, stream, p, ws_ml, ws_o, ns);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("mmha launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("mmha");
 }
 
 template <int DH>

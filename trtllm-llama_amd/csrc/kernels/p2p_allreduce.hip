@@ -36,6 +36,7 @@
 // check_comm; comm::p2p::disable_after_error clears the words, destroy + create + attach starts afresh).
 #include "dev_utils.h"
 #include "kernels.h"
+#include "launch_util.h"
 
 namespace tllm
 {
@@ -326,13 +327,7 @@ int launch_p2p_allreduce(const P2PParams& p, hipStream_t stream)
     }
     const int threads = p.n16 >= 1024 ? 1024 : (p.n16 >= 512 ? 512 : 256);
     hipLaunchKernelGGL(p2p_allreduce_kernel, dim3(1), dim3(threads), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("p2p all-reduce launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("p2p all-reduce");
 }
 
 } // namespace kernels

@@ -38,10 +38,9 @@
 // fp32 merge, nothing else.
 #include "dev_utils.h"
 #include "kernels.h"
-#include <atomic>
-#include <map>
+#include "launch_util.h"
+#include "lds_dma.h"
 #include <math.h>
-#include <mutex>
 #include <type_traits>
 
 namespace tllm
@@ -72,15 +71,6 @@ __device__ __forceinline__ void st_granule(gu64* g, uint32_t tag, uint32_t value
 __device__ __forceinline__ unsigned long long ld_granule(const gu64* g)
 {
     return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// one LDS-DMA instruction: 64 lanes x 16 bytes, global (per-lane address) -> LDS [lds_byte + lane * 16].  (M0 cannot go on the
-// clobber list - hipcc: "reserved register, may not be preserved" - and __builtin_amdgcn_global_load_lds would hand the waits
-// to the compiler's own vmcnt accounting: the statement saves M0 and puts it back itself)
-__device__ __forceinline__ void glds16(const void* gptr, uint32_t lds_byte)
-{
-    uint32_t m0_keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(gptr), "s"(lds_byte) : "memory");
 }
 
 // RoPE (NeoX pairs (d, d + 64)) of the element pair (2l, 2l + 1) this lane of the sweeping wave holds: the partner pair sits in
@@ -1137,55 +1127,6 @@ const void* fused_kernel(int nit, bool int8_kv, int wk)
     }
 }
 
-// Per-DEVICE launch state (a process may hold sessions on devices with different CU counts): the CU count, which
-// instances have had their dynamic-LDS attribute raised, and how many workgroups of an instance one CU admits.
-struct FusedDevState
-{
-    int cus = 0;
-    std::map<const void*, bool> attr_done;
-    std::map<std::pair<const void*, size_t>, int> per_cu;
-};
-std::mutex fused_mu;
-std::map<int, FusedDevState> fused_dev;
-
-FusedDevState& dev_state_locked()
-{
-    int dev = 0;
-    (void) hipGetDevice(&dev);
-    FusedDevState& d = fused_dev[dev];
-    if (!d.cus && (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || d.cus <= 0))
-        d.cus = 1;
-    return d;
-}
-
-// workgroups of this instance the whole chip admits at once (the occupancy query x CUs; 0 when the query fails)
-int resident_capacity(const void* kfn, size_t dyn)
-{
-    std::lock_guard<std::mutex> lock(fused_mu);
-    FusedDevState& d = dev_state_locked();
-    if (dyn && !d.attr_done[kfn])
-    {
-        (void) hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn);
-        d.attr_done[kfn] = true;
-    }
-    auto key = std::make_pair(kfn, dyn);
-    auto it = d.per_cu.find(key);
-    if (it == d.per_cu.end())
-    {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 64 * kWavesF, dyn) != hipSuccess)
-            nb = 0;
-        it = d.per_cu.emplace(key, nb).first;
-    }
-    return it->second * d.cus;
-}
-
-int device_cus()
-{
-    std::lock_guard<std::mutex> lock(fused_mu);
-    return dev_state_locked().cus;
-}
-
 size_t fused_dyn_lds(bool o_stage)
 {
     // O-projection stage: the row worker's rows of the dense projection live in dynamic LDS (<= 24 rows x K bytes)
@@ -1235,11 +1176,15 @@ bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int3
     // RESIDENT AT ONCE.  The occupancy query (this instance's registers, its dynamic LDS) x the CU count of THIS device must cover
     // the grid; and the launch only pays when it fills most of the chip.  (What the query cannot see - another queue's kernels
     // holding CUs - is what the bounded waits and the session's fall-back + retry are for.)
-    const int cus = device_cus();
+    // A device that cannot be described is refused: launch_util assumes 256 CUs when the CU-count query fails, and the verdict
+    // then rests on the occupancy query, which gives 0 when it fails.
+    const int cus = launch_util::device_cus();
     const int grid = num_heads * kMembers;
     if (grid > cus || grid * 4 < cus * 3)
         return false;
-    return resident_capacity(kfn, fused_dyn_lds(o_stage != 0)) >= grid;
+    const size_t dyn = fused_dyn_lds(o_stage != 0);
+    launch_util::ensure_dynamic_lds(kfn, dyn); // before the occupancy query, which counts the dynamic LDS
+    return launch_util::blocks_per_cu(kfn, 64 * kWavesF, dyn) * cus >= grid;
 }
 
 int launch_qkv_attn_fused(const FusedQkvAttnParams& p, hipStream_t stream)

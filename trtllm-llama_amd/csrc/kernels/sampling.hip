@@ -395,7 +395,8 @@ __global__ __launch_bounds__(kThreads) void sampling_step_kernel(const SampleArg
         }
     }
 
-    // ---- bookkeeping, as greedy_step_kernel
+    // ---- bookkeeping: a second copy of greedy_step_kernel's (decode_step.hip), not shared code - the RoPE row above, the commit,
+    // step_epoch and the next input row below must be edited in both kernels together
     __syncthreads();
     if (tid == 0)
     {
@@ -503,13 +504,7 @@ int launch_sampling_step(const SamplingParams& p, hipStream_t stream)
     if (dyn > 64 * 1024)
         launch_util::ensure_dynamic_lds(kfn, kDynLdsBudget);
     hipLaunchKernelGGL(sampling_step_kernel, dim3(g.batch), dim3(kThreads), dyn, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-    {
-        set_error("sampling_step launch failed: %s", hipGetErrorString(e));
-        return -1;
-    }
-    return 0;
+    return launch_util::check_launch("sampling_step");
 }
 
 } // namespace kernels

@@ -335,7 +335,7 @@ int32_t tllm_session_setup_beam(tllm_session_t s, int32_t batch_size, int32_t be
     }
     if (beam_width > 1 && (size_t) beam_width * (max_input_len + max_new_tokens) * sizeof(int32_t) > 96 * 1024)
     {
-        // the device-side beam step stages the cache-indirection rows it re-parents in LDS (pointwise.hip beam_step_kernel)
+        // the device-side beam step stages the cache-indirection rows it re-parents in LDS (decode_step.hip beam_step_kernel)
         set_error("tllm_session_setup: beam_width %d x max_seq_len %d exceeds the beam step's LDS staging (24576 int32)", beam_width,
             max_input_len + max_new_tokens);
         return 1;
