@@ -112,6 +112,19 @@ int32_t tllm_session_generate(tllm_session_t s, const int32_t* input_ids, const 
 int32_t tllm_session_context(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
     tllm_stream_t stream);
 int32_t tllm_session_step(tllm_session_t s, int32_t n_steps, int32_t use_graph, tllm_stream_t stream);
+/* tllm_session_context + the log-probability of every prompt token given the tokens before it.
+ *   log_probs HOST float [B, max_input_len]: log_probs[b][t] = log softmax(logits after ids[b][0..t-1])[ids[b][t]] for
+ *             1 <= t < input_lengths[b]; 0 at t = 0 and at t >= input_lengths[b];
+ *   top1_ids  HOST int32 [B, max_input_len] or NULL: the arg-max of that same distribution (ties -> lowest id); -1 where log_probs is 0 by definition.
+ * Leaves the session in exactly the state tllm_session_context leaves it in (cache, last-token logits, first sampled token, step state):
+ * generation can continue from it.  beam_width 1 only.  Synchronises the stream.
+ * The final hidden rows that have a next token go through ln_f and lm_head in chunks of rows (fp32 logits of one chunk at a
+ * time: as many rows as fit 64 MiB, a multiple of 32; session key score_chunk_rows overrides) and a streaming kernel reduces
+ * every row to (log-sum-exp, target logit, arg-max): the [tokens, vocab] logits never reach the host.  Tensor parallel: every
+ * rank reduces its own vocabulary shard, the 32-byte records are all-gathered and merged; every rank returns the same values.
+ * A token id outside [0, vocab_size) scores 0.  The buffers are allocated by the first call after a setup. */
+int32_t tllm_session_score(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths, float* log_probs,
+    int32_t* top1_ids, tllm_stream_t stream);
 /* Fill the KV cache for `length` positions with pseudo-random content (as a prompt of that length would)
  * without running a prefill; for decode-rate benchmarks at a given context length. */
 int32_t tllm_session_fake_context(tllm_session_t s, int32_t length, uint32_t seed, tllm_stream_t stream);
@@ -181,6 +194,13 @@ int32_t tllm_session_set_sampling(tllm_session_t s, const tllm_sampling_config_t
 int32_t tllm_sample_tokens(const float* logits, int32_t nparts, int32_t rows, int32_t vocab_part, int32_t vocab,
     const tllm_sampling_config_t* cfg, int32_t end_id, const int32_t* history, int32_t history_stride, const int32_t* input_lengths,
     int32_t max_input_len, const int32_t* g, int32_t* out_ids, float* u_out, tllm_stream_t stream);
+/* Kernel-level entry (parity tests): per-row log-probability of a target id, log-sum-exp and arg-max through the launchers
+ * tllm_session_score uses (rule and special values: TokenLogprobParams in csrc/kernels/kernels.h - target outside [0, vocab):
+ * log_prob 0; target logit -inf: log_prob -inf; NaN / +inf logits: undefined; the logits are not written).
+ * logits DEVICE f32 [nparts, rows, vocab_part] (id = part * vocab_part + i; ids >= vocab are padding); targets DEVICE int32 [rows];
+ * partials DEVICE f32 [nparts, rows, 8] scratch (left readable); log_probs DEVICE f32 [rows]; lse (f32) and top1_ids (int32) DEVICE [rows] or NULL. */
+int32_t tllm_token_logprobs(const float* logits, int32_t nparts, int32_t rows, int32_t vocab_part, int32_t vocab,
+    const int32_t* targets, float* partials, float* log_probs, float* lse, int32_t* top1_ids, tllm_stream_t stream);
 
 /* Parity-test tap (sessions created with debug_taps=1 only): the input of layer `layer`'s O-projection GEMM as the last
  * generation step computed it - the attention context after the split-KV merge, [B, H/tp * Dh] fp16, or int8 when the

@@ -472,6 +472,36 @@ int launch_sampling_step(const SamplingParams& p, hipStream_t stream);
 // true when the configuration is the plain arg-max the greedy step computes (top_k == 1, no penalty, min_length <= 1)
 bool sampling_is_greedy(const SamplingParams& p);
 
+// Per-token log-probabilities from fp32 logits rows without the rows leaving the device (kernels/token_logprob.hip; the
+// numpy float64 restatement is tensorrt_llm/runtime/scoring_ref.py).  Row r with target t = targets[r], over the ids v < vocab:
+//   lse = log sum_v exp(x[v]),  log_prob = x[t] - lse,  top1 = arg-max_v x[v] (ties -> lowest id, as launch_argmax).
+// The vocabulary may come in parts (tensor-parallel shards): the partial launch leaves one record of 8 words per (part, row),
+//   m = max of the part's valid ids (-inf if it has none),  s = sum exp(x - m) in fp32 (0 if m = -inf),
+//   xt = x[t] if t lies in the part else -inf,  top_val, top_id (global id; INT_MAX if the part has no valid id),  3 words of 0,
+// and the merge launch folds a row's records in part order: M = max m_p, S = sum s_p exp(m_p - M), lse = M + log S.  With one
+// part the merge is the identity on (m, s, xt, top).  Columns whose global id is >= vocab are padding and are never read.
+// Special values:
+//   * t outside [0, vocab) (-1 marks "no target"): log_prob = 0, nothing is read for it;
+//   * x[t] = -inf: log_prob = -inf; this includes the row of only -inf, whose lse is -inf and whose top1 is 0;
+//   * NaN or +inf among the valid ids: undefined.
+// The logits are never written.  Any ld and any 4-byte row alignment is served.  For a given launch geometry the result is
+// bit-reproducible: no atomics, a fixed reduction order.
+struct TokenLogprobParams
+{
+    const float* logits = nullptr; // part q (of this launch), row r, column i: logits[q * part_stride + r * ld + i]
+    int64_t part_stride = 0, ld = 0; // elements
+    int32_t rows = 0;
+    int32_t nparts = 1;     // parts in this launch
+    int32_t first_part = 0; // column i of launch part q has the global id (first_part + q) * vocab_part + i
+    int32_t vocab_part = 0, vocab = 0;
+    const int32_t* targets = nullptr; // int32 [rows]
+    float* partials = nullptr;        // f32 [nparts, rows, 8]
+};
+int launch_token_logprob_partial(const TokenLogprobParams& p, hipStream_t stream);
+// partials f32 [nparts, rows, 8] -> log_probs f32 [rows]; lse f32 [rows] and top1_ids int32 [rows] optional
+int launch_token_logprob_merge(const float* partials, int32_t nparts, int32_t rows, int32_t vocab, const int32_t* targets,
+    float* log_probs, float* lse, int32_t* top1_ids, hipStream_t stream);
+
 // teacher forcing for parity tests: overwrite the sampler's last choice (output slot seq_len[b], step input id, next input row)
 int launch_force_token(const int32_t* ids_dev, int32_t* cur_ids, int32_t* out_ids, int32_t out_stride, const int32_t* seq_len,
     const void* emb, void* x, int32_t batch, int32_t hidden, int32_t vocab, hipStream_t stream);

@@ -279,4 +279,29 @@ int32_t tllm_sample_tokens(const float* logits, int32_t nparts, int32_t rows, in
     return launch_sampling_step(sp, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
+int32_t tllm_token_logprobs(const float* logits, int32_t nparts, int32_t rows, int32_t vocab_part, int32_t vocab,
+    const int32_t* targets, float* partials, float* log_probs, float* lse, int32_t* top1_ids, tllm_stream_t stream)
+{
+    if (!logits || !targets || !partials || !log_probs || nparts < 1 || rows < 1 || vocab_part < 1 || vocab < 1
+        || (int64_t) nparts * vocab_part < vocab)
+    {
+        set_error("tllm_token_logprobs: bad arguments (the parts must cover the vocabulary)");
+        return 1;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    TokenLogprobParams p;
+    p.logits = logits;
+    p.part_stride = (int64_t) rows * vocab_part;
+    p.ld = vocab_part;
+    p.rows = rows;
+    p.nparts = nparts;
+    p.vocab_part = vocab_part;
+    p.vocab = vocab;
+    p.targets = targets;
+    p.partials = partials;
+    if (launch_token_logprob_partial(p, st))
+        return 1;
+    return launch_token_logprob_merge(partials, nparts, rows, vocab, targets, log_probs, lse, top1_ids, st) ? 1 : 0;
+}
+
 } // extern "C"

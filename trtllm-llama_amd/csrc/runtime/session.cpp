@@ -104,6 +104,37 @@ int32_t tllm_session_context(tllm_session_t s, const int32_t* input_ids, const i
     return 0;
 }
 
+int32_t tllm_session_score(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths, float* log_probs,
+    int32_t* top1_ids, tllm_stream_t stream)
+{
+    if (!s || !s->B)
+    {
+        set_error("tllm_session_score: call tllm_session_setup first");
+        return 1;
+    }
+    if (s->beam > 1)
+    {
+        set_error("tllm_session_score: beam_width 1 only (set up with beam_width %d)", s->beam);
+        return 1;
+    }
+    if (!input_ids || !input_lengths || !log_probs)
+    {
+        set_error("tllm_session_score: null argument");
+        return 1;
+    }
+    hipStream_t st = s->pick(stream);
+    // exactly tllm_session_context's launches, with the scoring between the head and the sampler (which leaves the next step's
+    // input row in x): the scoring writes buffers of its own and tmp, which every later launch fills before it reads it
+    RUN(upload_prompt(s, input_ids, input_lengths, st));
+    RUN(s->run_context(st));
+    RUN(s->score_enqueue(input_ids, input_lengths, st));
+    RUN(s->run_sampler(0, st));
+    HIP_OK(hipStreamSynchronize(st));
+    RUN(s->check_comm());
+    s->score_collect(log_probs, top1_ids);
+    return 0;
+}
+
 int32_t tllm_session_step(tllm_session_t s, int32_t n_steps, int32_t use_graph, tllm_stream_t stream)
 {
     if (!s || !s->B)

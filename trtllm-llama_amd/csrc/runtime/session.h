@@ -212,6 +212,25 @@ struct tllm_session
     int end_id = -1;
     bool sampling_on = false;       // tllm_session_set_sampling: run_sampler launches kernels/sampling.hip with `sampling`
     tllm::kernels::SamplingParams sampling; // configuration fields only; pointers and shapes are filled per launch
+    // tllm_session_score (session_context.cpp): session key score_chunk_rows = rows of fp32 logits per head GEMM (0: as many as fit
+    // 64 MiB).  The buffers below exist from the first score call on and go with the others in free_runtime
+    int score_chunk_cfg = 0;
+    struct ScoreBuffers
+    {
+        int chunk = 0;               // rows of `logits`
+        int max_rows = 0;            // Bc * (max_in - 1): rows that can have a next token
+        void* hidden = nullptr;      // fp16 [max_rows, D]: the gathered final hidden rows (ln_f leaves its result in tmp)
+        float* logits = nullptr;     // f32 [chunk, Vr]
+        int32_t* src_rows = nullptr; // [max_rows] row of x
+        int32_t* targets = nullptr;  // [max_rows] the next token's id
+        float* rec_local = nullptr;  // [max_rows, 8] this rank's records
+        float* rec_all = nullptr;    // [tp, max_rows, 8] (tensor parallel: the all-gather's result)
+        float* log_probs = nullptr;  // [max_rows]
+        int32_t* top1 = nullptr;     // [max_rows]
+    } score;
+    std::vector<int32_t> score_pos;  // host: output slot b * max_in + t + 1 of every scored row of the current call
+    std::vector<float> score_lp_host;
+    std::vector<int32_t> score_top_host;
     hipGraphExec_t graph = nullptr;
     hipStream_t graph_stream = nullptr;
     uint64_t graph_comm_gen = 0;   // comm::p2p::generation() the step graph was captured under
@@ -279,6 +298,10 @@ struct tllm_session
     int context_gate_up(const Layer& L, int M, const void* a_in, const void** p_in, hipStream_t st);
     int context_proj_residual(const Linear& L, int M, const void* in, bool fuse_res, hipStream_t st);
     int run_context(hipStream_t st);
+    // score: enqueue ln_f -> lm_head in row chunks -> partial records (-> all-gather) -> merge on the rows of x that have a next
+    // token (between run_context and the sampler, which reuses x); collect: after the stream is synchronised, scatter to the host
+    int score_enqueue(const int32_t* input_ids, const int32_t* input_lengths, hipStream_t st);
+    void score_collect(float* log_probs, int32_t* top1_ids);
 
     // ---- session_decode.cpp
     template <typename F>

@@ -5,6 +5,7 @@
 // SmoothQuant block template: SURVEY Appendix A.4 (the reference's SmoothQuant-LLaMA never ran; designed by analogy to
 // PY/quantization/layer.py:385-439,596-852).
 #include "session.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -235,4 +236,129 @@ int tllm_session::run_context(hipStream_t st)
         RUN(launch_gather_last_token(last_hidden, x, last_tok, Bc, S, D, st));
     RUN(run_head(last_hidden, Bc, st));
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------ scoring
+// The log-probability of every prompt token that has a predecessor.  Row (b, t) of x, t < len_b - 1, is the final hidden state
+// after ids[b][0..t]; it predicts ids[b][t + 1].  Only those rows go through the head: gathered -> ln_f (fp16 in tmp, the kernel
+// itself: context_norm would quantise in a SmoothQuant session) -> lm_head as a prefill GEMM with fp32 output, one chunk of rows
+// at a time -> kernels/token_logprob.hip on the chunk.  The [rows, Vr] logits exist one chunk at a time and stay on the device.
+int tllm_session::score_enqueue(const int32_t* input_ids, const int32_t* input_lengths, hipStream_t st)
+{
+    const int S = max_in, D = hidden;
+    std::vector<int32_t> src, tgt;
+    score_pos.clear();
+    int packed_base = 0;
+    for (int b = 0; b < Bc; ++b)
+    {
+        const int len = input_lengths[b]; // upload_prompt has checked the range
+        const int base = packed ? packed_base : b * S;
+        for (int t = 0; t + 1 < len; ++t)
+        {
+            src.push_back(base + t);
+            tgt.push_back(input_ids[(size_t) b * S + t + 1]);
+            score_pos.push_back(b * S + t + 1);
+        }
+        packed_base += len;
+    }
+    const int R = (int) src.size();
+    score_lp_host.assign(R, 0.f);
+    score_top_host.assign(R, -1);
+    if (R == 0)
+        return 0;
+    const bool gather = (tp > 1 || force_comm) && !no_comm;
+    if (!score.logits)
+    {
+        ScoreBuffers sb;
+        sb.max_rows = Bc * (S - 1);
+        int chunk = score_chunk_cfg > 0 ? score_chunk_cfg : std::max(32, (int) (((size_t) 64 << 20) / ((size_t) Vr * 4) / 32 * 32));
+        sb.chunk = std::min(chunk, sb.max_rows);
+        RUN(dalloc(&sb.hidden, (size_t) sb.max_rows * D * 2));
+        RUN(dalloc(&sb.logits, (size_t) sb.chunk * Vr * 4));
+        RUN(dalloc(&sb.src_rows, (size_t) sb.max_rows * 4));
+        RUN(dalloc(&sb.targets, (size_t) sb.max_rows * 4));
+        RUN(dalloc(&sb.rec_local, (size_t) sb.max_rows * 8 * 4));
+        if (gather)
+            RUN(dalloc(&sb.rec_all, (size_t) tp * sb.max_rows * 8 * 4));
+        RUN(dalloc(&sb.log_probs, (size_t) sb.max_rows * 4));
+        RUN(dalloc(&sb.top1, (size_t) sb.max_rows * 4));
+        score = sb;
+    }
+    HIP_OK(hipMemcpyAsync(score.src_rows, src.data(), (size_t) R * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(score.targets, tgt.data(), (size_t) R * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st)); // src / tgt go out of scope
+    RUN(launch_gather_rows(score.hidden, x, score.src_rows, R, D, st));
+    RmsnormParams r;
+    r.M = R;
+    r.N = D;
+    r.x = score.hidden;
+    r.gamma = lnf;
+    r.eps = eps;
+    r.y = tmp; // [Bc * S, D] fp16, free between the last layer and the next call
+    RUN(launch_rmsnorm(r, st));
+    for (int r0 = 0; r0 < R; r0 += score.chunk)
+    {
+        const int rows = std::min(score.chunk, R - r0);
+        GemmParams g;
+        g.wtype = head.wtype;
+        g.out_dtype = DT_FLOAT;
+        g.M = rows;
+        g.N = head.N;
+        g.K = head.K;
+        g.a = static_cast<const char*>(tmp) + (size_t) r0 * D * 2;
+        g.lda = D;
+        g.w = head.w;
+        g.ldw = head.ldw;
+        g.scale_col = head.scale_col;
+        g.per_channel = head.per_channel;
+        g.c = score.logits;
+        g.ldc = Vr;
+        if (launch_gemm(g, st))
+            return 1;
+        TokenLogprobParams p;
+        p.logits = score.logits;
+        p.ld = Vr;
+        p.rows = rows;
+        p.first_part = rank; // this rank's vocabulary shard: ids [rank * Vr, min(vocab, (rank + 1) * Vr))
+        p.vocab_part = Vr;
+        p.vocab = vocab;
+        p.targets = score.targets + r0;
+        p.partials = score.rec_local + (size_t) r0 * 8;
+        if (launch_token_logprob_partial(p, st))
+            return 1;
+    }
+    const float* rec = score.rec_local;
+    if (gather)
+    {
+        // 32 bytes per row and rank instead of the rank's logits: the choice of transport is run_head's
+        const int64_t bytes = (int64_t) R * 8 * 4;
+        if (comm::p2p::usable(tp, bytes))
+        {
+            if (comm::p2p::all_gather(score.rec_local, score.rec_all, bytes, st))
+                return 1;
+        }
+        else if (comm::all_gather(group, score.rec_local, score.rec_all, (int64_t) R * 8, TLLM_FLOAT, st))
+            return 1;
+        rec = score.rec_all;
+    }
+    // (no_comm: a timing-only session merges its own shard alone)
+    if (launch_token_logprob_merge(rec, gather ? tp : 1, R, vocab, score.targets, score.log_probs, nullptr, score.top1, st))
+        return 1;
+    HIP_OK(hipMemcpyAsync(score_lp_host.data(), score.log_probs, (size_t) R * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(score_top_host.data(), score.top1, (size_t) R * 4, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+void tllm_session::score_collect(float* log_probs, int32_t* top1_ids)
+{
+    const size_t n = (size_t) Bc * max_in;
+    std::fill(log_probs, log_probs + n, 0.f);
+    if (top1_ids)
+        std::fill(top1_ids, top1_ids + n, -1);
+    for (size_t k = 0; k < score_pos.size(); ++k)
+    {
+        log_probs[score_pos[k]] = score_lp_host[k];
+        if (top1_ids)
+            top1_ids[score_pos[k]] = score_top_host[k];
+    }
 }

@@ -22,6 +22,7 @@ void tllm_session::free_runtime()
     for (auto p : allocs)
         (void) hipFree(p);
     allocs.clear();
+    score = ScoreBuffers();
 }
 
 // ------------------------------------------------------------------------------------------ buffers

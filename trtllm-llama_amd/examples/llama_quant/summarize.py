@@ -212,6 +212,27 @@ def main(args):
         prompts = [rng.integers(3, vocab, int(l)).astype(np.int32) for l in lens]
         references = [None] * n
 
+    def nll_tensorrt_llm(batch):
+        """(sum of -log p(token | tokens before it) over the batch's prompts, tokens scored): one prefill, GenerationSession.score"""
+        lens = np.array([len(p) for p in batch], np.int32)
+        max_len = int(lens.max())
+        ids = np.full((len(batch), max_len), pad_id, np.int32)
+        for i, p in enumerate(batch):
+            ids[i, :len(p)] = p
+        decoder.setup(len(batch), max_len, output_len)
+        lp = np.asarray(decoder.score(ids, lens)['log_probs'], np.float64)
+        return -float(lp.sum()), int((lens - 1).sum())
+
+    @torch.no_grad()
+    def nll_hf(batch):
+        total, n = 0.0, 0
+        for p in batch:
+            ids = torch.from_numpy(p.astype(np.int64))[None].to(model.device)
+            lsm = torch.log_softmax(model(ids).logits[0, :-1].double(), dim=-1)
+            total -= float(lsm.gather(1, ids[0, 1:, None]).sum())
+            n += len(p) - 1
+        return total, n
+
     def summarize_tensorrt_llm(batch):
         lens = np.array([len(p) for p in batch], np.int32)
         max_len = int(lens.max())
@@ -245,10 +266,17 @@ def main(args):
 
     metric_trt, metric_hf, metric_vs_hf = Rouge(), Rouge(), Rouge()
     match, total = 0, 0
+    nll = {'tensorrt_llm': [0.0, 0], 'hf': [0.0, 0]}  # --eval_ppl: sum of negative log-likelihoods, tokens scored
     for it in range(0, len(prompts), args.batch_size):
         batch = prompts[it:it + args.batch_size]
         refs = references[it:it + args.batch_size]
         s_trt = s_hf = None
+        if args.eval_ppl:
+            for side, on, fn in (('tensorrt_llm', test_trt_llm, nll_tensorrt_llm), ('hf', test_hf and model is not None, nll_hf)):
+                if on:
+                    a, n = fn(batch)
+                    nll[side][0] += a
+                    nll[side][1] += n
         if test_trt_llm:
             profiler.start('tensorrt_llm')
             s_trt = summarize_tensorrt_llm(batch)
@@ -312,6 +340,17 @@ def main(args):
             if args.per_sample:
                 result['per_sample_rougeL'] = dict(tensorrt_llm=a.tolist(), hf=b.tolist())
             logger.info(f'  rougeL delta 95 % interval (paired bootstrap over {len(d)} prompts): {result["rougeL_delta_ci95"]}')
+        if args.eval_ppl:
+            # perplexity of the evaluation prompts under each side that ran: exp(mean negative log-likelihood per token)
+            for side, (a, n) in nll.items():
+                if n:
+                    result[f'{side}_perplexity'] = float(np.exp(a / n))
+                    logger.info(f'  {side} perplexity of the prompts ({n} tokens) : {result[f"{side}_perplexity"]:.4f}')
+            if nll['tensorrt_llm'][1] and nll['hf'][1]:
+                result['mean_nll_delta'] = nll['tensorrt_llm'][0] / nll['tensorrt_llm'][1] - nll['hf'][0] / nll['hf'][1]
+                logger.info(f'  mean NLL per token, engine - HF : {result["mean_nll_delta"]:.5f}')
+            elif test_hf and model is None:
+                logger.warning('--eval_ppl: HF ran from --hf_tokens_npy, so there are no HF logits to score the prompts with')
         if args.output_json:  # before the checks: a run that fails them still leaves its numbers
             with open(args.output_json, 'w') as f:
                 json.dump(result, f, indent=1)
@@ -364,6 +403,10 @@ def parse_arguments(argv=None):
     parser.add_argument('--max_input_tokens', type=int, default=923)
     parser.add_argument('--stop_at_eos', action='store_true')
     parser.add_argument('--output_json', type=str, default=None)
+    parser.add_argument('--eval_ppl', action='store_true',
+                        help='also report the perplexity of the evaluation prompts under each enabled side (engine: one scoring '
+                             'prefill per batch; HF: from its own logits) and the difference of the mean negative log-likelihood '
+                             'per token: tensorrt_llm_perplexity, hf_perplexity, mean_nll_delta in --output_json')
     return parser.parse_args(argv)
 
 

@@ -118,6 +118,42 @@ class GenerationSession(object):
         return out
 
     @staticmethod
+    def _check_score_args(ids, lens, batch_size: int, max_input_length: int, beam_width: int = 1):
+        """What score() refuses before anything reaches the device."""
+        if beam_width != 1:
+            raise ValueError(f'score() needs beam_width 1 (the session is set up with {beam_width})')
+        if ids.ndim != 2 or ids.shape != (batch_size, max_input_length):
+            raise ValueError(f'input_ids {ids.shape}: call setup() with matching sizes first '
+                             f'(batch {batch_size}, max_input_length {max_input_length})')
+        if lens.shape != (batch_size, ):
+            raise ValueError(f'input_lengths {lens.shape}: one length per sequence ({batch_size})')
+        if not (np.issubdtype(ids.dtype, np.integer) and np.issubdtype(lens.dtype, np.integer)):
+            raise TypeError('input_ids and input_lengths must be integers')
+        if lens.size and (lens.min() < 1 or lens.max() > max_input_length):
+            raise ValueError(f'input_lengths must lie in [1, {max_input_length}]')
+
+    def score(self, input_ids, input_lengths):
+        """Teacher-forced scoring of the prompts in one prefill (tllm_session_score).  input_ids int32 [batch, max_input_length]
+        and input_lengths [batch] as decode() takes them (torch tensor or ndarray).  Returns a dict:
+          log_probs  f32 [batch, max_input_length]: log p(ids[b][t] | ids[b][:t]) for 1 <= t < len_b, 0 elsewhere;
+          top1_ids   int32, same shape: the arg-max of that distribution, -1 where log_probs is 0 by definition;
+          perplexity f32 [batch]: exp(-sum_t log_probs[b][t] / (len_b - 1)); nan for a sequence of one token.
+        torch tensors on the input's device when input_ids is a torch tensor.  The session is left as the prompt pass of
+        decode() leaves it."""
+        from .scoring_ref import perplexity
+        is_torch = hasattr(input_ids, 'cpu')
+        ids = input_ids.cpu().numpy() if is_torch else np.asarray(input_ids)
+        lens = input_lengths.cpu().numpy() if hasattr(input_lengths, 'cpu') else np.asarray(input_lengths)
+        self._check_score_args(ids, lens, self.batch_size, self.max_input_length, getattr(self, 'beam_width', 1))
+        lp, top = self.runtime.score(ids.astype(np.int32), lens.astype(np.int32))
+        ppl = np.array([perplexity(lp[b], lens[b:b + 1]) for b in range(len(lens))], np.float32)
+        out = dict(log_probs=lp, top1_ids=top, perplexity=ppl)
+        if is_torch:
+            import torch
+            out = {k: torch.from_numpy(v).to(input_ids.device) for k, v in out.items()}
+        return out
+
+    @staticmethod
     def _native_sampling(scfg: SamplingConfig) -> dict:
         return dict(top_k=scfg.top_k, top_p=scfg.top_p, temperature=scfg.temperature,
                     repetition_penalty=scfg.repetition_penalty, presence_penalty=scfg.presence_penalty,

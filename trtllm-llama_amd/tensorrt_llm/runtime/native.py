@@ -85,6 +85,11 @@ def _lib():
                                        c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
                                        c.c_void_p, c.c_void_p]
     lib.tllm_sample_tokens.restype = c.c_int32
+    lib.tllm_session_score.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.tllm_session_score.restype = c.c_int32
+    lib.tllm_token_logprobs.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p,
+                                        c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.tllm_token_logprobs.restype = c.c_int32
     _bound = True
     return lib
 
@@ -127,6 +132,27 @@ def sample_tokens(logits, g, out_ids, *, vocab=None, end_id=-1, history=None, in
     _check(_lib().tllm_sample_tokens(logits.data_ptr(), nparts, rows, vpart, vocab or nparts * vpart, ctypes.byref(cfg), end_id,
                                      ptr(history), stride, ptr(input_lengths), max_input_len, g.data_ptr(), out_ids.data_ptr(),
                                      ptr(u_out), stream), 'sample_tokens')
+
+
+def token_logprobs(logits, targets, *, vocab=None, partials=None, stream: int = 0):
+    """tllm_token_logprobs on torch cuda tensors: logits f32 [rows, vocab] or [nparts, rows, vocab_part] (then `vocab` = the real
+    vocabulary size), targets int32 [rows] (-1 = no target) -> (log_probs f32 [rows], lse f32 [rows], top1_ids int32 [rows]).
+    partials: optional f32 [nparts, rows, 8] that receives the per-part records.  Asynchronous on `stream`."""
+    import torch
+    if logits.dim() == 2:
+        logits = logits.unsqueeze(0)
+    nparts, rows, vpart = logits.shape
+    assert logits.is_cuda and logits.is_contiguous() and logits.dtype == torch.float32
+    assert targets.is_cuda and targets.is_contiguous() and targets.dtype == torch.int32 and targets.numel() == rows
+    if partials is None:
+        partials = torch.empty((nparts, rows, 8), dtype=torch.float32, device=logits.device)
+    assert partials.is_cuda and partials.is_contiguous() and partials.dtype == torch.float32 and partials.numel() == nparts * rows * 8
+    lp = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    top = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    _check(_lib().tllm_token_logprobs(logits.data_ptr(), nparts, rows, vpart, vocab or nparts * vpart, targets.data_ptr(),
+                                      partials.data_ptr(), lp.data_ptr(), lse.data_ptr(), top.data_ptr(), stream), 'token_logprobs')
+    return lp, lse, top
 
 
 def _check(rc: int, what: str):
@@ -188,6 +214,7 @@ class NativeSession:
         _check(_lib().tllm_session_set_sampling(self._h, ctypes.byref(cfg)), 'set_sampling')
 
     sample_tokens = staticmethod(sample_tokens)
+    token_logprobs = staticmethod(token_logprobs)
 
     @staticmethod
     def _i32(a) -> np.ndarray:
@@ -197,6 +224,17 @@ class NativeSession:
         ids, lens = self._i32(input_ids), self._i32(input_lengths)
         assert ids.shape == (self.batch, self.max_in) and lens.shape == (self.batch, )
         _check(_lib().tllm_session_context(self._h, ids.ctypes.data, lens.ctypes.data, stream), 'context')
+
+    def score(self, input_ids, input_lengths, stream: int = 0):
+        """context() + the log-probability of every prompt token given the tokens before it (tllm_session_score):
+        (log_probs f32 [batch, max_in], top1_ids int32 [batch, max_in]); 0 / -1 at t = 0 and behind a sequence's end.  The session
+        is left as context() leaves it.  beam_width 1 only."""
+        ids, lens = self._i32(input_ids), self._i32(input_lengths)
+        assert ids.shape == (self.batch, self.max_in) and lens.shape == (self.batch, )
+        lp = np.empty((self.batch, self.max_in), np.float32)
+        top = np.empty((self.batch, self.max_in), np.int32)
+        _check(_lib().tllm_session_score(self._h, ids.ctypes.data, lens.ctypes.data, lp.ctypes.data, top.ctypes.data, stream), 'score')
+        return lp, top
 
     def step(self, n_steps: int = 1, use_graph: bool = False, stream: int = 0):
         _check(_lib().tllm_session_step(self._h, n_steps, 1 if use_graph else 0, stream), 'step')
