@@ -151,6 +151,10 @@ void* tllm_session_mlp_timeline_ptr(tllm_session_t s);
 int32_t tllm_session_get_step_state(tllm_session_t s, int32_t* sequence_length, int32_t* next_position, int32_t* masked_tokens,
     int32_t* input_lengths, tllm_stream_t stream);
 
+/* The device word the sampler advances once per generation step (the tags of the in-launch hand-offs derive from it): zero after
+ * tllm_session_setup's allocation, + 1 per step whichever sampler runs it.  For tests. */
+int32_t tllm_session_get_step_epoch(tllm_session_t s, uint32_t* epoch, tllm_stream_t stream);
+
 /* Teacher forcing for parity tests (greedy sessions): replace the token the last context / generation step chose by ids[b]
  * (host, [B]) - in the output buffer, as the next step's input id and as its input embedding row - so that two
  * implementations can be compared step by step on the SAME prefix (the reference's tests feed HF's tokens the same way,

@@ -63,22 +63,26 @@ __global__ __launch_bounds__(1024) void argmax_kernel(int32_t* out_ids, const fl
     }
 }
 
-__global__ __launch_bounds__(1024) void greedy_step_kernel(const GreedyParams p)
+// Entry contract (gemv_impl.h): what the logits loads are built from leads the parameter list and is preloaded into SGPRs; the
+// struct trails it for the bookkeeping and is first read behind the first logits requests.  launch_greedy_step fills both from
+// the one GreedyParams.
+__global__ __launch_bounds__(1024) void greedy_step_kernel(const float* const hot_logits, const int hot_batch, const int hot_vocab_part,
+    const int hot_nparts, const int hot_vocab, const GreedyParams p)
 {
     __shared__ float sv[16];
     __shared__ int si[16];
     const int b = blockIdx.x;
     float best = -INFINITY;
     int bi = 0x7fffffff;
-    for (int part = 0; part < p.nparts; ++part)
+    for (int part = 0; part < hot_nparts; ++part)
     {
-        const float* l = p.logits + ((int64_t) part * p.batch + b) * p.vocab_part;
-        const int base_id = part * p.vocab_part;
-        if ((p.vocab_part & 3) == 0 && (reinterpret_cast<uintptr_t>(l) & 15) == 0)
+        const float* l = hot_logits + ((int64_t) part * hot_batch + b) * hot_vocab_part;
+        const int base_id = part * hot_vocab_part;
+        if ((hot_vocab_part & 3) == 0 && (reinterpret_cast<uintptr_t>(l) & 15) == 0)
         {
             // 16-byte loads, all of a thread's requests in flight before the compares (latency-bound otherwise)
             constexpr int UNR = 8;
-            const int nvec = p.vocab_part >> 2;
+            const int nvec = hot_vocab_part >> 2;
             for (int v0 = threadIdx.x; v0 < nvec; v0 += blockDim.x * UNR)
             {
                 float4 vals[UNR];
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const GreedyParams p)
                     for (int e = 0; e < 4; ++e)
                     {
                         const int id = id0 + e;
-                        if (id < p.vocab && (f[e] > best || (f[e] == best && id < bi)))
+                        if (id < hot_vocab && (f[e] > best || (f[e] == best && id < bi)))
                         {
                             best = f[e];
                             bi = id;
@@ -108,10 +112,10 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const GreedyParams p)
             }
             continue;
         }
-        for (int i = threadIdx.x; i < p.vocab_part; i += blockDim.x)
+        for (int i = threadIdx.x; i < hot_vocab_part; i += blockDim.x)
         {
             const int id = base_id + i;
-            if (id >= p.vocab)
+            if (id >= hot_vocab)
                 break;
             const float v = l[i];
             if (v > best || (v == best && id < bi))
@@ -184,7 +188,7 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const GreedyParams p)
     {
         __syncthreads();
         const int id = si[0];
-        const bool ok = id >= 0 && id < p.vocab;
+        const bool ok = id >= 0 && id < hot_vocab;
         const uint16_t* src = reinterpret_cast<const uint16_t*>(p.emb_table) + (int64_t) (ok ? id : 0) * p.hidden;
         uint16_t* dst = reinterpret_cast<uint16_t*>(p.x_out) + (int64_t) b * p.hidden;
         for (int k = threadIdx.x * 8; k < p.hidden; k += blockDim.x * 8) // hidden % 8 == 0 (checked by the launcher)
@@ -366,7 +370,7 @@ int launch_greedy_step(const GreedyParams& p, hipStream_t stream)
         set_error("greedy step: fused embedding gather needs x_out and hidden %% 8 == 0 (got %d)", p.hidden);
         return -1;
     }
-    hipLaunchKernelGGL(greedy_step_kernel, dim3(p.batch), dim3(1024), 0, stream, p);
+    hipLaunchKernelGGL(greedy_step_kernel, dim3(p.batch), dim3(1024), 0, stream, p.logits, p.batch, p.vocab_part, p.nparts, p.vocab, p);
     return check_launch("greedy_step");
 }
 

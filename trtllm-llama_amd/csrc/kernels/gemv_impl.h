@@ -142,8 +142,16 @@ __device__ __forceinline__ int dot_sq(const uint4& w, const uint4& x, int acc)
 // registers (sum of squares -> ONE barrier -> normalise / quantise) -> LDS -> ONE barrier -> dots -> DPP reduction ->
 // epilogue.  Further tiles are double-buffered, with the next group's epilogue operands requested ahead of the next
 // tile so that waiting for them never drains the weight stream.
+//
+// Entry contract: the values the t = 0 requests are built from - the pointers, the row stride and the extents - lead the parameter
+// list as plain scalars, so that the kernarg preload puts them into SGPRs before the first instruction and the x / gamma / weight
+// loads go out without a scalar round trip to the kernarg segment.  The struct trails them for everything else (its copies of the
+// leading values are not read here); it is first touched behind the first weight tile's requests.  launch_inst fills both from
+// the one GemvArgs.
 template <int WT, int PK, int EK, int MB, int kNXV, int UU = tllm::kernels::gemv_detail::U>
-__global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
+__global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, const void* const hot_x, const void* const hot_gamma,
+    const void* const hot_w_up, const int64_t hot_ldw, const int hot_N, const int hot_K, const int hot_Kp, const int hot_ngroups,
+    const GemvArgs a)
 {
     // chunks per tile: 4, or 2 for rows of at most 2 KiB (int4 K = 4096): a 4-chunk tile would be half neutral elements -
     // half the load slots, LDS reads and dequantisation arithmetic wasted
@@ -157,7 +165,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const GemvParams& p = a.p;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int K = p.K, Kp = a.Kp;
+    const int K = hot_K, Kp = hot_Kp;
     float* red = reinterpret_cast<float*>(smem);
     char* xs = smem + kRedBytes; // [MB][Kp] halfs, or [MB][Kp] s8 for SQ
     constexpr int XES = SQ ? 1 : 2;
@@ -165,8 +173,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     const bool q_static = SQ && (p.pro == PRO_RMSNORM_QSTATIC || p.pro == PRO_QSTATIC);
 
     // ------------------------------------------------------------------ weight-tile helpers
-    const char* wbase = reinterpret_cast<const char*>(p.w);
-    const char* wup = p.w_up ? reinterpret_cast<const char*>(p.w_up) : wbase + (int64_t) p.N * p.ldw;
+    const char* wbase = reinterpret_cast<const char*>(hot_w);
+    const char* wup = hot_w_up ? reinterpret_cast<const char*>(hot_w_up) : wbase + (int64_t) hot_N * hot_ldw;
     const int lane_kbyte = lane * 16;
     // the last 16 bytes of the ROW, not of its stride: what lies between the two is the caller's (fp16 NaN bits there times a
     // zeroed activation would still be NaN)
@@ -174,9 +182,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     auto rows_of_group = [&](int g, const char* (&rowptr)[R]) {
         if constexpr (SWIGLU)
         {
-            const int o = g < p.N ? g : p.N - 1; // one output per group: gate row o, up row o
-            rowptr[0] = wbase + (int64_t) o * p.ldw;
-            rowptr[1] = wup + (int64_t) o * p.ldw;
+            const int o = g < hot_N ? g : hot_N - 1; // one output per group: gate row o, up row o
+            rowptr[0] = wbase + (int64_t) o * hot_ldw;
+            rowptr[1] = wup + (int64_t) o * hot_ldw;
         }
         else
         {
@@ -184,7 +192,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
             for (int r = 0; r < R; ++r)
             {
                 const int row = g * R + r;
-                rowptr[r] = wbase + (int64_t) (row < p.N ? row : p.N - 1) * p.ldw;
+                rowptr[r] = wbase + (int64_t) (row < hot_N ? row : hot_N - 1) * hot_ldw;
             }
         }
     };
@@ -208,7 +216,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     auto load_x_row = [&](int m) {
         if constexpr (X_HALF)
         {
-            const uint16_t* xg = reinterpret_cast<const uint16_t*>(p.x) + (int64_t) m * p.ldx;
+            const uint16_t* xg = reinterpret_cast<const uint16_t*>(hot_x) + (int64_t) m * p.ldx;
 #pragma unroll
             for (int j = 0; j < kNXV; ++j)
             {
@@ -222,7 +230,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
         else
         {
             // raw s8 activations: 16 values per vector
-            const int8_t* xg = reinterpret_cast<const int8_t*>(p.x) + (int64_t) m * p.ldx;
+            const int8_t* xg = reinterpret_cast<const int8_t*>(hot_x) + (int64_t) m * p.ldx;
 #pragma unroll
             for (int j = 0; j < kNXV; ++j)
             {
@@ -244,7 +252,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     load_x_row(0);
     if constexpr (PK == PK_NORM)
     {
-        const uint16_t* gam = reinterpret_cast<const uint16_t*>(p.gamma);
+        const uint16_t* gam = reinterpret_cast<const uint16_t*>(hot_gamma);
 #pragma unroll
         for (int j = 0; j < kNXV; ++j)
         {
@@ -256,12 +264,15 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     const int gstride = gridDim.x * 4;
     const char* rowptr[R];
     uint4 wv[U][R], wv2[U][R];
-    rows_of_group(g0 < a.ngroups ? g0 : 0, rowptr);
+    rows_of_group(g0 < hot_ngroups ? g0 : 0, rowptr);
     load_tile(rowptr, 0, wv);
+    // everything above is built from preloaded SGPRs and ids; the first read of the struct (a scalar load and its wait) stays
+    // behind these requests
+    __builtin_amdgcn_sched_barrier(0);
     // the tile stream of this wave: (group, chunk) of the next tile to request.  (Requesting the second ring buffer here too,
     // before the prologue, was measured: slower on every shape - QKV 10.3 -> 11.2 us, gate|up 16.5 -> 18.0 us.)
     const int tiles_per_group = (a.nchunks + U - 1) / U;
-    const int ngroups_mine = g0 < a.ngroups ? (a.ngroups - g0 + gstride - 1) / gstride : 0;
+    const int ngroups_mine = g0 < hot_ngroups ? (hot_ngroups - g0 + gstride - 1) / gstride : 0;
     const int ntiles = ngroups_mine * tiles_per_group;
     int t_issue = 1, gi_i = 0, ci_i = 1; // tile 0 is in flight in `wv`
     if (ci_i == tiles_per_group)
@@ -297,13 +308,13 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
     auto load_ops = [&](int g) {
         EpiOps e = {1.f, 1.f, 0, 0, 0};
         int n = g * NOUTS + (my_o < NOUTS ? my_o : 0);
-        n = n < p.N ? n : p.N - 1; // clamped: inactive lanes load a valid element and ignore it
+        n = n < hot_N ? n : hot_N - 1; // clamped: inactive lanes load a valid element and ignore it
         if constexpr (WT == W_INT8_WOQ || WT == W_INT4_WOQ)
         {
             const uint16_t* sc = reinterpret_cast<const uint16_t*>(p.scale_col);
             e.h0 = sc[n];
             if constexpr (SWIGLU)
-                e.h1 = p.scale_col_up ? reinterpret_cast<const uint16_t*>(p.scale_col_up)[n] : sc[p.N + n];
+                e.h1 = p.scale_col_up ? reinterpret_cast<const uint16_t*>(p.scale_col_up)[n] : sc[hot_N + n];
         }
         else if constexpr (SQ)
         {
@@ -312,7 +323,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
             if constexpr (SWIGLU)
             {
                 const float* su = reinterpret_cast<const float*>(p.scale_col_up);
-                e.s1 = su ? su[p.per_channel ? n : 0] : sc[p.per_channel ? p.N + n : 0];
+                e.s1 = su ? su[p.per_channel ? n : 0] : sc[p.per_channel ? hot_N + n : 0];
             }
         }
         if constexpr (!SWIGLU)
@@ -324,7 +335,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
         }
         return e;
     };
-    EpiOps ops_cur = load_ops(g0 < a.ngroups ? g0 : 0);
+    EpiOps ops_cur = load_ops(g0 < hot_ngroups ? g0 : 0);
     float static_row_scale = 1.f, static_row_scale_up = 1.f, epi_q = 1.f, pro_q = 1.f;
     if constexpr (SQ)
     {
@@ -522,12 +533,12 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a)
         const bool last = ci_p == tiles_per_group - 1;
         const int g = g0 + gi_p * gstride;
         const int n = g * NOUTS + (my_o < NOUTS ? my_o : 0);
-        const bool fin = last && my_active && n < p.N;
+        const bool fin = last && my_active && n < hot_N;
         const int64_t oidx = (int64_t) my_m * p.ldy + n;
         // (1) the next group's epilogue operands
         EpiOps ops_nxt = ops_cur;
         if (last)
-            ops_nxt = load_ops(g + gstride < a.ngroups ? g + gstride : g);
+            ops_nxt = load_ops(g + gstride < hot_ngroups ? g + gstride : g);
         // (2) the next tile, into the other ring buffer
         issue_next(nxt);
         // (3) dot products of the current tile
@@ -694,7 +705,9 @@ int launch_inst(const GemvArgs& a, hipStream_t stream)
         const int groups_per_wave = (a.ngroups + waves - 1) / waves;
         blocks = (a.ngroups + 4 * groups_per_wave - 1) / (4 * groups_per_wave);
     }
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), smem, stream, a);
+    // the leading (preloaded) parameters are the struct's own fields: one source for every pointer and extent
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), smem, stream, a.p.w, a.p.x, a.p.gamma, a.p.w_up, a.p.ldw, a.p.N, a.p.K, a.Kp,
+        a.ngroups, a);
     return launch_util::check_launch("gemv");
 }
 

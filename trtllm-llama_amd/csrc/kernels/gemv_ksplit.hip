@@ -35,8 +35,11 @@ struct KSplit
     static constexpr int NCMAX = WT == W_FP16 ? 6 : (WT == W_INT4_WOQ ? 2 : 3); // chunks per wave: 24 / 16 weight vectors per lane
 };
 
+// Entry contract (gemv_impl.h): what the t = 0 requests are built from leads the parameter list and is preloaded into SGPRs; the
+// struct trails it for the epilogue and is first read behind the weight requests.  launch_nc fills both from the one GemvArgs.
 template <int WT, int NC>
-__global__ __launch_bounds__(256) void gemv_ksplit_kernel(const GemvParams p, int nchunks)
+__global__ __launch_bounds__(256) void gemv_ksplit_kernel(const void* const hot_w, const void* const hot_x, const int64_t hot_ldw,
+    const int hot_N, const int hot_K, const int nchunks, const GemvParams p)
 {
     using T = KSplit<WT>;
     constexpr int VEC = T::VEC, XV = T::XV, RW = T::RW;
@@ -45,8 +48,8 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const GemvParams p, in
     __shared__ acc_t part[4][RW];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int row0 = blockIdx.x * RW;
-    const char* wbase = reinterpret_cast<const char*>(p.w);
-    const char* xg = reinterpret_cast<const char*>(p.x);
+    const char* wbase = reinterpret_cast<const char*>(hot_w);
+    const char* xg = reinterpret_cast<const char*>(hot_x);
     constexpr int XES = SQ ? 1 : 2; // bytes per activation
     // ---- t = 0: everything this workgroup will ever read
     uint4 w[NC][RW], xv[NC][XV];
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const GemvParams p, in
     {
         const int c = wid + 4 * i;
         const int k = (c * 64 + lane) * VEC;   // first element of this lane's weight vector
-        const bool ok = c < nchunks && k < p.K; // K is a multiple of VEC
+        const bool ok = c < nchunks && k < hot_K; // K is a multiple of VEC
         const int kc = ok ? k : 0;
 #pragma unroll
         for (int v = 0; v < XV; ++v)
@@ -69,15 +72,16 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const GemvParams p, in
 #pragma unroll
         for (int r = 0; r < RW; ++r)
         {
-            const int row = row0 + r < p.N ? row0 + r : p.N - 1;
-            w[i][r] = ld_nt16(wbase + (int64_t) row * p.ldw + woff);
+            const int row = row0 + r < hot_N ? row0 + r : hot_N - 1;
+            w[i][r] = ld_nt16(wbase + (int64_t) row * hot_ldw + woff);
         }
     }
+    __builtin_amdgcn_sched_barrier(0); // the struct's first read (a scalar load and its wait) stays behind the requests above
     // epilogue operands of row (tid % RW): every thread loads them (no lane-dependent branch around a load - that would make
     // the compiler fence it), threads 0 .. RW - 1 use them
     float s0 = 1.f, srow = 1.f;
     uint16_t s0_bits = 0, res_bits = 0; // fp16 operands stay raw until the epilogue (a conversion next to the load = a wait)
-    const int n = row0 + (tid % RW) < p.N ? row0 + (tid % RW) : p.N - 1;
+    const int n = row0 + (tid % RW) < hot_N ? row0 + (tid % RW) : hot_N - 1;
     if constexpr (SQ)
     {
         s0 = reinterpret_cast<const float*>(p.scale_col)[p.per_channel ? n : 0];
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(256) void gemv_ksplit_kernel(const GemvParams p, in
             part[wid][r] = a;
     }
     __syncthreads();
-    if (tid < RW && row0 + tid < p.N)
+    if (tid < RW && row0 + tid < hot_N)
     {
         const acc_t tot = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
         if constexpr (!SQ && WT != W_FP16)
@@ -140,7 +144,8 @@ void launch_nc(const GemvArgs& a, int per_wave, hipStream_t stream)
         if (per_wave < NC)
             return launch_nc<WT, NC - 1>(a, per_wave, stream);
     constexpr int RW = KSplit<WT>::RW;
-    hipLaunchKernelGGL((gemv_ksplit_kernel<WT, NC>), dim3((a.p.N + RW - 1) / RW), dim3(256), 0, stream, a.p, a.nchunks);
+    hipLaunchKernelGGL((gemv_ksplit_kernel<WT, NC>), dim3((a.p.N + RW - 1) / RW), dim3(256), 0, stream, a.p.w, a.p.x, a.p.ldw, a.p.N,
+        a.p.K, a.nchunks, a.p);
 }
 
 template <int WT>

@@ -182,8 +182,13 @@ __device__ __forceinline__ float groups_max(float v)
 // pair (two 1 KiB chunks), the half-raw splices of gemv_impl.h's W_INT4_WOQ path (two running sums per row, 72 * sum(x_b) off once per
 // row): bit-identical projection.  Two-stage form.
 constexpr int WK_SQ = 0, WK_WOQ8 = 1, WK_FP16 = 2, WK_WOQ4 = 3;
+//
+// Entry contract (gemv_impl.h): what the t = 0 requests are built from - x, gamma, the weight rows and their stride, the head count -
+// and the two device words the entry reads first lead the parameter list and are preloaded into SGPRs; the struct trails them for
+// everything else (its copies of the leading values are not read here).  launch_qkv_attn_fused fills both from the one struct.
 template <int NIT, bool INT8KV, int WK = WK_SQ>
-__global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnParams p)
+__global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const hot_x, const void* const hot_gamma, const void* const hot_w,
+    const int64_t hot_ldw, const int hot_num_heads, const uint32_t* const hot_epoch, uint32_t* const hot_error, const FusedQkvAttnParams p)
 {
     constexpr bool WOQ = WK == WK_WOQ8, F16W = WK == WK_FP16, WOQ4 = WK == WK_WOQ4;
     constexpr bool HALFX = WK != WK_SQ; // the projection's operand row stays fp16 (no quantiser)
@@ -211,51 +216,67 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
     float* misc = hpart + kMembers * (kDH + 8);                            // [0] score of the current token, [1] give-up flag
     uint32_t* qflag = reinterpret_cast<uint32_t*>(misc + 2);               // set by wave 0 once q' is in `rot`
 
-    const int H = p.num_heads;
+    const int H = hot_num_heads;
     const int h = blockIdx.x % H, mem = blockIdx.x / H;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid) >> 6; // scalar: the role branches below are s_cbranch, not exec masks
     const int K = p.K;
-    const uint32_t ep = p.epoch[0];
+    // ------------------------------------------------------------------ t = 0: x, gamma and the q rows
+    // Nothing in front of these requests waits for memory: every address below is built from preloaded SGPRs and ids.
+    // (a) x: vectors t and t + 256 of the 256-thread prologue this one restates (threads >= 256 repeat the first half's work so
+    //     that no load sits behind a branch); gamma for the vector this thread normalises
+    const int t2 = tid & 255;
+    const uint16_t* xg = reinterpret_cast<const uint16_t*>(hot_x);
+    const uint4 xa = *reinterpret_cast<const uint4*>(xg + t2 * 8);
+    const uint4 xb = *reinterpret_cast<const uint4*>(xg + (t2 + 256) * 8);
+    const uint4 gv = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(hot_gamma) + tid * 8);
+    int wrow[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        wrow[i] = (i * H + h) * kDH + mem * 16 + 2 * wid;
+    __builtin_amdgcn_sched_barrier(0); // issue order = consumption order (hipcc sank the gamma load below the weight loads)
+    // (b) the wave's q rows: rows 2 wid, 2 wid + 1 of the member's 16.  The k rows follow behind the prologue, the v rows into
+    //     the q rows' registers behind their dots: two 8 KB tiles per wave = 128 KB per CU in flight.  NOT the whole stream at
+    //     t = 0 (r05 first form, 230 KB per CU): a CU drains its load queue in order at ~25 GB/s, and what has to pass through it
+    //     later - the instruction fetch of the code below, x itself - waited: the prologue finished 6.6 us after the launch
+    //     instead of 3.4 (tools/fused_timeline.py).
+    const char* wbase = reinterpret_cast<const char*>(hot_w);
+    uint4 wa[kKChunks][2], wb[kKChunks][2];
+    // tile t of the wave's stream: matrix t / KH (q, k, v), chunks [4 (t % KH), + 4) of its two rows
+    auto load_tile = [&](int t, uint4 (&wt)[kKChunks][2]) {
+#pragma unroll
+        for (int u = 0; u < KCT; ++u)
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                wt[u][r] = ld_nt16(wbase + (int64_t) (wrow[t / KH] + r) * hot_ldw + ((t % KH) * kKChunks + u) * 1024 + lane * 16);
+    };
+    load_tile(0, wa);
+    __builtin_amdgcn_sched_barrier(0);
+    // ------------------------------------------------------------------ the device words and launch constants, behind the requests
+    // The scalar path's round trips - the struct's kernarg dwords, then the words its pointers lead to - run while x and the q rows
+    // are in flight: under the stream, not in front of it.  Not one batch: only the epoch's and the error word's pointers are
+    // preloaded, the sequence length and the scales need the struct first, and hipcc sinks each load into the branch that consumes
+    // it (the error word is waited for alone, for the early exit).  All of it stays in front of the kernel's first store (behind one
+    // hipcc no longer uses the scalar path for them) and nothing here consumes a VECTOR load: the counter is in order, a wait for
+    // one would be a wait for the q rows.
+    const uint32_t ep = hot_epoch[0];
+    const uint32_t err = hot_error[0];
+    const int tl = p.sequence_length[0]; // slots in use; the current token goes to slot tl
+    // a bounded wait of an EARLIER launch expired: the session has not looked yet (it reads the word at its next synchronisation),
+    // everything behind that launch is invalid anyway - do not spin again, layer after layer, step after step.  No store, no
+    // atomic and no poll has happened yet; the loads in flight are dropped with the wave
+    if (err != 0u) // uniform (scalar load)
+        return;
     // step tags live in the lower 31 bits (never 0: the exchange buffer starts zeroed), host tags carry the top bit: the two
     // numberings cannot meet, and a wrap of the 32-bit product after ~2^32 / (layers + 1) steps lands on a valid tag again
     const uint32_t ep_tag = (ep * p.tag_mul + p.tag_add) & 0x7fffffffu;
     const uint32_t tag = p.tag_host ? (p.tag_host | 0x80000000u) : (ep_tag ? ep_tag : 0x7fffffffu);
-    // a bounded wait of an EARLIER launch expired: the session has not looked yet (it reads the word at its next synchronisation),
-    // everything behind that launch is invalid anyway - do not spin again, layer after layer, step after step
-    if (p.error[0] != 0u) // uniform (scalar load)
-        return;
-    const int tl = p.sequence_length[0]; // slots in use; the current token goes to slot tl
     const int Smax = p.max_seq_len;
     const bool q_dyn = p.act_quant_scale == nullptr;
     gu64* gx = (gu64*) p.xchg + (size_t) h * kHeadGranules;
     gu64* gp = gx + 3 * 64;
     gu64* gc = (gu64*) p.xchg + (size_t) H * kHeadGranules; // [H][kCtxGranules]: the context rows (O-projection stage)
-    // O-projection stage: members 1 .. 7 of every head are the row workers - worker j takes rows [j n / W, (j + 1) n / W) of the dense
-    // projection, wave `wid` rows r0 + wid, + 8, + 16.  Their per-channel scales and residual elements are launch constants too
-    extern __shared__ __attribute__((aligned(16))) char wo_lds[]; // [rows of this worker][K bytes], filled by LDS-DMA
-    const bool o_stage = p.o_w != nullptr; // uniform
-    const int o_workers = (kMembers - 1) * H;
-    const int o_j = (mem - 1) * H + h;
-    const int o_r0 = o_stage && mem ? (int) ((int64_t) o_j * p.o_n / o_workers) : 0;
-    const int o_r1 = o_stage && mem ? (int) ((int64_t) (o_j + 1) * p.o_n / o_workers) : 0;
-    float o_cs[3], o_res[3];
-    float o_rs = 1.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-    {
-        const int row = o_r0 + wid + 8 * i;
-        const bool on = row < o_r1; // wave-uniform
-        if constexpr (WOQX)
-            o_cs[i] = on ? h2f(reinterpret_cast<const uint16_t*>(p.o_scale_col)[row]) : 0.f;
-        else
-            o_cs[i] = on ? reinterpret_cast<const float*>(p.o_scale_col)[p.o_per_channel ? row : 0] : 0.f;
-        o_res[i] = on ? h2f(reinterpret_cast<const uint16_t*>(p.x)[row]) : 0.f;
-    }
-    if (o_stage && WK == WK_SQ)
-        o_rs = p.o_scale_row[0];
-    // launch constants, requested before anything else (and before the kernel's first store: behind one hipcc no longer uses the
-    // scalar path for them, and as vector loads behind the q rows they held the prologue until the q rows had arrived)
+    // launch constants (still in front of the first store, see above)
     float pro_q = 1.f, deq = 1.f;
     if (!q_dyn) // uniform
     {
@@ -268,22 +289,11 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
         s_oq = p.kv_scale_orig_quant[0];
         s_qo = p.kv_scale_quant_orig[0];
     }
-
-    // ------------------------------------------------------------------ t = 0: x, gamma, the scales and the q rows
-    // (a) x: vectors t and t + 256 of the 256-thread prologue this one restates (threads >= 256 repeat the first half's work so
-    //     that no load sits behind a branch); gamma for the vector this thread normalises
-    const int t2 = tid & 255;
-    const uint16_t* xg = reinterpret_cast<const uint16_t*>(p.x);
-    const uint4 xa = *reinterpret_cast<const uint4*>(xg + t2 * 8);
-    const uint4 xb = *reinterpret_cast<const uint4*>(xg + (t2 + 256) * 8);
-    const uint4 gv = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(p.gamma) + tid * 8);
     // the per-channel scales of the wave's 6 rows (wave-uniform addresses: scalar loads)
-    int wrow[3];
     float cscale[3][2];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
     {
-        wrow[i] = (i * H + h) * kDH + mem * 16 + 2 * wid;
 #pragma unroll
         for (int r = 0; r < 2; ++r)
         {
@@ -296,23 +306,34 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
         }
     }
     const float4 cs = reinterpret_cast<const float4*>(p.rope_row)[lane & 31]; // RoPE coefficients of elements 2 l', 2 l' + 1
-    __builtin_amdgcn_sched_barrier(0); // issue order = consumption order (hipcc sank the gamma load below the weight loads)
-    // (b) the wave's q rows: rows 2 wid, 2 wid + 1 of the member's 16.  The k rows follow behind the prologue, the v rows into
-    //     the q rows' registers behind their dots: two 8 KB tiles per wave = 128 KB per CU in flight.  NOT the whole stream at
-    //     t = 0 (r05 first form, 230 KB per CU): a CU drains its load queue in order at ~25 GB/s, and what has to pass through it
-    //     later - the instruction fetch of the code below, x itself - waited: the prologue finished 6.6 us after the launch
-    //     instead of 3.4 (tools/fused_timeline.py).
-    const char* wbase = reinterpret_cast<const char*>(p.w);
-    uint4 wa[kKChunks][2], wb[kKChunks][2];
-    // tile t of the wave's stream: matrix t / KH (q, k, v), chunks [4 (t % KH), + 4) of its two rows
-    auto load_tile = [&](int t, uint4 (&wt)[kKChunks][2]) {
+    // O-projection stage: members 1 .. 7 of every head are the row workers - worker j takes rows [j n / W, (j + 1) n / W) of the dense
+    // projection, wave `wid` rows r0 + wid, + 8, + 16.  Their per-channel scales and residual elements are launch constants too
+    extern __shared__ __attribute__((aligned(16))) char wo_lds[]; // [rows of this worker][K bytes], filled by LDS-DMA
+    const bool o_stage = p.o_w != nullptr; // uniform
+    const int o_workers = (kMembers - 1) * H;
+    const int o_j = (mem - 1) * H + h;
+    const int o_r0 = o_stage && mem ? (int) ((int64_t) o_j * p.o_n / o_workers) : 0;
+    const int o_r1 = o_stage && mem ? (int) ((int64_t) (o_j + 1) * p.o_n / o_workers) : 0;
+    // the residual elements (and the weight-only scales) are 16-bit: vector loads.  Unconditional, from a clamped row, and kept as
+    // raw bits until the O-projection's epilogue - a conversion here would wait for them behind the q rows
+    float o_cs[3];
+    uint16_t o_res_bits[3], o_cs_bits[3];
+    float o_rs = 1.f;
 #pragma unroll
-        for (int u = 0; u < KCT; ++u)
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-                wt[u][r] = ld_nt16(wbase + (int64_t) (wrow[t / KH] + r) * p.ldw + ((t % KH) * kKChunks + u) * 1024 + lane * 16);
-    };
-    load_tile(0, wa);
+    for (int i = 0; i < 3; ++i)
+    {
+        const int row = o_r0 + wid + 8 * i;
+        const bool on = row < o_r1; // wave-uniform
+        o_cs[i] = 0.f;
+        o_cs_bits[i] = 0;
+        if constexpr (WOQX)
+            o_cs_bits[i] = reinterpret_cast<const uint16_t*>(on ? p.o_scale_col : hot_x)[on ? row : 0];
+        else
+            o_cs[i] = on ? reinterpret_cast<const float*>(p.o_scale_col)[p.o_per_channel ? row : 0] : 0.f;
+        o_res_bits[i] = reinterpret_cast<const uint16_t*>(hot_x)[on ? row : 0];
+    }
+    if (o_stage && WK == WK_SQ)
+        o_rs = p.o_scale_row[0];
     __builtin_amdgcn_sched_barrier(0);
     TLLM_STAMP(0);
 
@@ -358,8 +379,8 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
             // the splice bias 1152 * sum of the normalised row (int4: 72 * the sum over the halves that face the 1024 + 16 n splices) (fp16 values, fp32 sums) in the unfused prologue's order: thread
             // t < 256 of that kernel owns vectors t and t + 256 - both are in this thread's registers (t2 = tid & 255), so waves
             // 0 - 3 restate its sums and waves 4 - 7 repeat them
-            const uint4 ga = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(p.gamma) + t2 * 8);
-            const uint4 gb = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(p.gamma) + (t2 + 256) * 8);
+            const uint4 ga = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(hot_gamma) + t2 * 8);
+            const uint4 gb = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(hot_gamma) + (t2 + 256) * 8);
             const uint32_t xv[2][4] = {{xa.x, xa.y, xa.z, xa.w}, {xb.x, xb.y, xb.z, xb.w}};
             const uint32_t gg[2][4] = {{ga.x, ga.y, ga.z, ga.w}, {gb.x, gb.y, gb.z, gb.w}};
             float sa = 0.f, sb = 0.f;
@@ -762,7 +783,7 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
     if (misc[1] != 0.f) // uniform
     {
         if (tid == 0)
-            atomicOr(p.error, 1u);
+            atomicOr(hot_error, 1u);
         return;
     }
     // O-projection stage, row workers: waves 3 - 7 (no part in the publication below) request the worker's rows of the dense
@@ -846,7 +867,7 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
         if (misc[1] != 0.f) // uniform
         {
             if (tid == 0)
-                atomicOr(p.error, 4u);
+                atomicOr(hot_error, 4u);
             return;
         }
         float obias = 0.f;
@@ -938,8 +959,9 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
             const int i = lane;
             const int row = o_r0 + wid + 8 * i;
             const float a = (float) (i == 0 ? acc[0] : (i == 1 ? acc[1] : acc[2])) - obias;
-            const float cs_i = i == 0 ? o_cs[0] : (i == 1 ? o_cs[1] : o_cs[2]);
-            const float rs_i = i == 0 ? o_res[0] : (i == 1 ? o_res[1] : o_res[2]);
+            const float cs_i = WOQX ? h2f(i == 0 ? o_cs_bits[0] : (i == 1 ? o_cs_bits[1] : o_cs_bits[2]))
+                                    : (i == 0 ? o_cs[0] : (i == 1 ? o_cs[1] : o_cs[2]));
+            const float rs_i = h2f(i == 0 ? o_res_bits[0] : (i == 1 ? o_res_bits[1] : o_res_bits[2]));
             if (row < o_r1)
                 reinterpret_cast<uint16_t*>(p.x_out)[row] = f2h(h2f(f2h(a * (cs_i * o_rs))) + rs_i);
         }
@@ -1012,7 +1034,7 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const FusedQkvAttnP
     if (misc[1] != 0.f)
     {
         if (tid == 0)
-            atomicOr(p.error, 2u);
+            atomicOr(hot_error, 2u);
         return;
     }
     const bool has_new = tl < Smax;
@@ -1230,7 +1252,8 @@ int launch_qkv_attn_fused(const FusedQkvAttnParams& p, hipStream_t stream)
     const void* kfn = fused_kernel(pick_nit(p.max_seq_len, p.int8_kv != 0), p.int8_kv != 0, wk);
     const dim3 grid(p.num_heads * kMembers), block(64 * kWavesF);
     FusedQkvAttnParams q = p;
-    void* args[] = {&q};
+    // the leading (preloaded) parameters are the struct's own fields: one source for every pointer
+    void* args[] = {&q.x, &q.gamma, &q.w, &q.ldw, &q.num_heads, &q.epoch, &q.error, &q};
     const hipError_t e = hipLaunchKernel(kfn, grid, block, args, fused_dyn_lds(o_stage), stream);
     if (e != hipSuccess)
     {

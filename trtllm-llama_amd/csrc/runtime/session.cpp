@@ -456,6 +456,19 @@ int32_t tllm_session_get_step_state(tllm_session_t s, int32_t* sequence_length, 
     return 0;
 }
 
+int32_t tllm_session_get_step_epoch(tllm_session_t s, uint32_t* epoch, tllm_stream_t stream)
+{
+    if (!s || !s->B || !epoch)
+    {
+        set_error("tllm_session_get_step_epoch: bad arguments / setup not called");
+        return 1;
+    }
+    hipStream_t st = s->pick(stream);
+    HIP_OK(hipMemcpyAsync(epoch, s->step_epoch, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
 int32_t tllm_session_force_tokens(tllm_session_t s, const int32_t* ids, tllm_stream_t stream)
 {
     if (!s || !s->B || !ids)

@@ -60,6 +60,8 @@ def _lib():
     lib.tllm_session_kv_cache_ptr.restype = c.c_void_p
     lib.tllm_session_get_step_state.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.tllm_session_get_step_state.restype = c.c_int32
+    lib.tllm_session_get_step_epoch.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.tllm_session_get_step_epoch.restype = c.c_int32
     lib.tllm_session_get_tap.argtypes = [c.c_void_p, c.c_int32, c.c_void_p, c.c_size_t, c.c_void_p]
     lib.tllm_session_get_tap.restype = c.c_int32
     lib.tllm_session_get_tap_ex.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_void_p, c.c_size_t, c.c_void_p]
@@ -322,6 +324,12 @@ class NativeSession:
                                                   d['masked_tokens'].ctypes.data, d['input_lengths'].ctypes.data, stream),
                'get_step_state')
         return d
+
+    def step_epoch(self, stream: int = 0) -> int:
+        """the device word the sampler advances once per generation step"""
+        v = ctypes.c_uint32()
+        _check(_lib().tllm_session_get_step_epoch(self._h, ctypes.byref(v), stream), 'get_step_epoch')
+        return int(v.value)
 
     def force_tokens(self, ids, stream: int = 0):
         """teacher forcing: overwrite the token the last step chose (parity tests compare on identical prefixes)"""
