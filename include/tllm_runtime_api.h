@@ -27,7 +27,9 @@ typedef struct tllm_session* tllm_session_t;
 /* Create a session from a configuration text.  Recognised keys (defaults in parentheses):
  *   num_layers, num_heads, hidden_size, inter_size, vocab_size, max_position_embeddings (2048),
  *   rms_norm_eps (1e-6), tp_size (1), tp_rank (0), quant_mode (0: QuantMode bits,
- *   T/tensorrt_llm/quantization/mode.py:6-21), weight_only_precision (int8|int4),
+ *   T/tensorrt_llm/quantization/mode.py:6-21; bit 32 = int8 KV cache, bit 64 = fp8 (OCP E4M3) KV cache: one-byte cache
+ *   elements and the two attention.kv_*_scale tensors per layer either way, the two bits are exclusive and an fp8 session runs
+ *   the separate-launch generation step), weight_only_precision (int8|int4),
  *   use_gpt_attention_plugin/use_gemm_plugin (informational), neox_rotary_style (1),
  *   force_comm (0; tests: issue the tensor-parallel collectives on a 1-rank communicator as well),
  *   remove_input_padding (0; 1: the context phase runs on the packed real tokens only),

@@ -131,7 +131,7 @@ __device__ __forceinline__ uint4 rope_kv_finish(const ContextAttnParams& p, int 
     }
     if (s < p.max_seq_len)
     {
-        const int esz = p.int8_kv ? 1 : 2;
+        const int esz = (p.int8_kv || p.fp8_kv) ? 1 : 2;
         char* kc = reinterpret_cast<char*>(p.kv_cache)
             + (((int64_t) (b * p.cache_seq_stride * 2 + 0) * H + h) * p.max_seq_len + s) * DH * esz + li * 8 * esz;
         char* vc = reinterpret_cast<char*>(p.kv_cache)
@@ -156,6 +156,12 @@ __device__ __forceinline__ uint4 rope_kv_finish(const ContextAttnParams& p, int 
             const float sc = p.kv_scale_orig_quant[0];
             *reinterpret_cast<uint2*>(kc) = quant8(k4, sc);
             *reinterpret_cast<uint2*>(vc) = quant8(v4, sc);
+        }
+        else if (p.fp8_kv)
+        {
+            const float sc = p.kv_scale_orig_quant[0];
+            *reinterpret_cast<uint2*>(kc) = quant8_fp8(k4, sc);
+            *reinterpret_cast<uint2*>(vc) = quant8_fp8(v4, sc);
         }
         else
         {
@@ -771,6 +777,12 @@ int launch_context_attention(const ContextAttnParams& p, hipStream_t stream)
     if (p.int8_kv && !p.kv_scale_orig_quant)
     {
         set_error("context attention: int8 KV cache needs kv_scale_orig_quant");
+        return -1;
+    }
+    if (p.fp8_kv && (p.int8_kv || !p.kv_scale_orig_quant))
+    {
+        set_error(p.int8_kv ? "context attention: int8_kv and fp8_kv are exclusive"
+                            : "context attention: fp8 KV cache needs kv_scale_orig_quant");
         return -1;
     }
     if (p.block_pointers)

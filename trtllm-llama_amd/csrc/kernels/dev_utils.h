@@ -142,6 +142,42 @@ __device__ __forceinline__ uint2 quant8(const uint4& v, float s)
     return make_uint2(o[0], o[1]);
 }
 
+// 8 fp16 -> 8 OCP E4M3 (e4m3fn) bytes of the KV cache: rne(clamp(float(x16) * s, -448, +448)).  The product is rounded once to
+// fp32 (the empty asm keeps the backend from contracting it into anything else); the clamp is plain float code in front of the
+// conversion, so the result does not depend on the instruction's overflow mode and the NaN codes 0x7f / 0xff are never written
+// (NaN input is undefined by contract).  v_cvt_pk_fp8_f32 rounds to nearest even, into the subnormals too (2^-9 is the
+// smallest, 2^-10 ties to 0), and keeps the sign of zero.
+__device__ __forceinline__ uint2 quant8_fp8(const uint4& v, float s)
+{
+    float f[8];
+    h8_to_f(v, f);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+    {
+        float x = f[j] * s;
+        asm("" : "+v"(x));
+        f[j] = __builtin_fminf(__builtin_fmaxf(x, -448.f), 448.f);
+    }
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    return make_uint2((uint32_t) lo, (uint32_t) hi);
+}
+
+// 8 cached E4M3 bytes -> 8 fp16, exactly (every E4M3 value is an fp16 value; the scale operand 1.0 multiplies by 2^0):
+// v_cvt_scalef32_pk_f16_fp8, one instruction per two elements
+__device__ __forceinline__ uint4 dequant8_fp8(const uint2& q)
+{
+    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+    const h2v a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int) q.x, 1.0f, false);
+    const h2v b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int) q.x, 1.0f, true);
+    const h2v c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int) q.y, 1.0f, false);
+    const h2v d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int) q.y, 1.0f, true);
+    return make_uint4(h2_as_u32(a), h2_as_u32(b), h2_as_u32(c), h2_as_u32(d));
+}
+
 // LDS image [row][BKB bytes], BKB = 128 or 64: byte offset of 16-byte piece c16 of tile row `row`, XOR-swizzled so that the 16
 // lanes of a ds_read_b128 phase (16 consecutive rows, same k-piece) hit 16 different 16-byte bank groups
 template <int BKB>

@@ -21,7 +21,8 @@ enum DType : int32_t
     DT_FLOAT = 0,
     DT_HALF = 1,
     DT_INT8 = 2,
-    DT_INT32 = 3
+    DT_INT32 = 3,
+    DT_FP8 = 6 // OCP E4M3 bytes (KV cache only; the value of TLLM_FP8)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -127,7 +128,7 @@ int launch_gather_last_token(void* out, const void* hidden, const int32_t* last_
 
 // ---------------------------------------------------------------------------------------------
 // Decode attention (A2/A3): masked multi-head attention for one new token per sequence, with RoPE,
-// KV-cache write (fp16 or int8) and split-KV across workgroups.
+// KV-cache write (fp16, int8 or fp8 E4M3) and split-KV across workgroups.
 // ---------------------------------------------------------------------------------------------
 struct MmhaParams
 {
@@ -135,10 +136,11 @@ struct MmhaParams
     int32_t rotary_dim = 0, neox = 1;
     float inv_sqrt_dh = 1.f;
     int32_t int8_kv = 0;
+    int32_t fp8_kv = 0;        // OCP E4M3 cache (one byte per element, the two scales of int8_kv); exclusive with int8_kv
     int32_t max_seq_len = 0;   // cache capacity Smax
     int32_t max_input_len = 0; // padded prompt length (RoPE position = timestep - (max_input_len - input_len[b]))
     const void* qkv = nullptr; // fp16 [B, 3*H*Dh] (q | k | v)
-    void* kv_cache = nullptr;  // [B, 2, H, Smax, Dh] fp16 or s8
+    void* kv_cache = nullptr;  // [B, 2, H, Smax, Dh] fp16, s8 or e4m3
     const int32_t* sequence_length = nullptr; // [B] device: tlength (slots already used)
     const int32_t* input_lengths = nullptr;   // [B] device
     const int32_t* masked_tokens = nullptr;   // [B, Smax] device or null
@@ -292,6 +294,7 @@ struct ContextAttnParams
     int32_t rotary_dim = 0, neox = 1;
     float inv_sqrt_dh = 1.f;
     int32_t int8_kv = 0, max_seq_len = 0;
+    int32_t fp8_kv = 0; // OCP E4M3 cache (kv_scale_orig_quant as for int8_kv); exclusive with int8_kv
     void* qkv = nullptr;      // fp16 [B, S, 3*H*Dh]; q,k rewritten in place with RoPE applied (reference :1401-1403)
     void* kv_cache = nullptr; // [B, 2, H, Smax, Dh]
     const int32_t* input_lengths = nullptr; // [B]

@@ -10,7 +10,8 @@
 // around any load (out-of-range rows load a clamped address and are dropped by a select: a lane-dependent `if`
 // makes hipcc fence every load with s_waitcnt vmcnt(0) + exec masking); scores with v_dot2_f32_f16 + a DPP sum
 // inside the lane group; the int8 cache is widened with a byte splice to exact integers and the scale is folded
-// into the dot product; an independent softmax partial {max, sum, out[Dh]} per lane group (no cross-group
+// into the dot product; the fp8 (OCP E4M3) cache is decoded to exact fp16 by v_cvt_scalef32_pk_f16_fp8 and takes the fp16 dot
+// products, its scale applied once to the score and once to the P.V sum; an independent softmax partial {max, sum, out[Dh]} per lane group (no cross-group
 // shuffles), merged per workgroup through LDS and published per split as (m, l) + un-normalised fp32 o.
 // The splits of a (batch, head) are merged INSIDE this launch by the last split of the head to arrive (step 6: write-through
 // partials, one ticket per workgroup, agent-scope loads; MmhaParams::tail_tickets) - plugin and session alike - which leaves the
@@ -23,7 +24,8 @@
 // prepared for this step (GreedyParams::rope_row_out), so nothing chases length -> position -> table.
 //
 // Numerics follow SURVEY Appendix A.1: RoPE in fp32 -> fp16; int8 cache store = sat(rni(float(k16) * s)),
-// load = fp16(float(q8) * s^-1); q.k products fp32-accumulated, * inv_sqrt_dh in fp32; masked positions are
+// load = fp16(float(q8) * s^-1); fp8 cache store = e4m3fn_rne(clamp(float(k16) * s, +-448)), load = the exact value * s^-1;
+// q.k products fp32-accumulated, * inv_sqrt_dh in fp32; masked positions are
 // dropped (weight 0, excluded from the max); probabilities rounded to fp16 before P.V; fp32 accumulation;
 // normaliser (sum + 1e-6); one final rounding to fp16.  The split only reorders fp32 additions and rounds the
 // un-normalised probability instead of the normalised one.
@@ -77,6 +79,14 @@ __device__ __forceinline__ uint4 dequant8(const uint2& q, float s)
 //   CACHE_BEAM    the same buffer, rows of the sibling hypothesis cache_indirection names
 //   CACHE_PAGED   block table [B, 2, max_blocks] of pointers to [H, tokens_per_block, DH] blocks (K/kvCacheUtils.h:34-112),
 //                 through the cache indirection too when beam_width > 1
+// KV: the cache element - fp16, int8 (8-byte rows) or fp8 E4M3 (8-byte rows)
+enum
+{
+    KV_F16 = 0,
+    KV_I8 = 1,
+    KV_F8 = 2
+};
+
 enum
 {
     CACHE_LINEAR = 0,
@@ -84,7 +94,7 @@ enum
     CACHE_PAGED = 2
 };
 
-template <int DH, int NIT, bool INT8KV, int CACHE>
+template <int DH, int NIT, int KV, int CACHE>
 __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, float2* ws_ml, float* ws_o, int nsplit_max)
 {
     using G = MmhaGeom<DH, NIT>;
@@ -96,7 +106,8 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     const int H = p.num_heads, Smax = p.max_seq_len;
     const int t0 = c * G::TCHUNK;
 
-    constexpr int ESZ = INT8KV ? 1 : 2;
+    constexpr bool INT8KV = KV == KV_I8, FP8KV = KV == KV_F8;
+    constexpr int ESZ = KV == KV_F16 ? 2 : 1;
     char* kbase = reinterpret_cast<char*>(p.kv_cache) + ((int64_t) (b * 2 + 0) * H + h) * Smax * DH * ESZ;
     char* vbase = reinterpret_cast<char*>(p.kv_cache) + ((int64_t) (b * 2 + 1) * H + h) * Smax * DH * ESZ;
 
@@ -158,7 +169,7 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
             kp = kblk[i] + off;
             vp = vblk[i] + off;
         }
-        if constexpr (INT8KV)
+        if constexpr (INT8KV || FP8KV)
         {
             const uint2 k8 = *reinterpret_cast<const uint2*>(kp);
             const uint2 v8 = *reinterpret_cast<const uint2*>(vp);
@@ -267,7 +278,7 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     const uint4 k_new = f_to_h8(kf);
 
     float s_oq = 1.f, s_qo = 1.f;
-    if constexpr (INT8KV)
+    if constexpr (INT8KV || FP8KV)
     {
         s_oq = p.kv_scale_orig_quant[0];
         s_qo = p.kv_scale_quant_orig[0];
@@ -298,6 +309,11 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
                 *reinterpret_cast<uint2*>(kw) = quant8(k_new, s_oq);
                 *reinterpret_cast<uint2*>(vw) = quant8(v_new, s_oq);
             }
+            else if constexpr (FP8KV)
+            {
+                *reinterpret_cast<uint2*>(kw) = quant8_fp8(k_new, s_oq);
+                *reinterpret_cast<uint2*>(vw) = quant8_fp8(v_new, s_oq);
+            }
             else
             {
                 *reinterpret_cast<uint4*>(kw) = k_new;
@@ -311,13 +327,15 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     // and the dequantisation scale is applied once to the dot product / to the P.V sum instead of to every element
     // (the reference rounds every dequantised element to fp16 first, ...Utils.h:2358-2365 - this is the same value
     // without that rounding; well inside the 2e-3 tolerance of the reference's own plugin test).
+    // fp8 cache: the bytes decode to fp16 exactly (every E4M3 value is an fp16 value), the fp16 dot products run on them as they
+    // are, and the scale is applied once in the same two places.
     float dnew = 0.f;
     dnew = dot2(q16.x, k_new.x, dnew);
     dnew = dot2(q16.y, k_new.y, dnew);
     dnew = dot2(q16.z, k_new.z, dnew);
     dnew = dot2(q16.w, k_new.w, dnew);
     dnew = group_sum<LPR>(dnew) * p.inv_sqrt_dh;
-    const float kscale = INT8KV ? s_qo * p.inv_sqrt_dh : p.inv_sqrt_dh;
+    const float kscale = (INT8KV || FP8KV) ? s_qo * p.inv_sqrt_dh : p.inv_sqrt_dh;
     float s[NIT];
     float m_g = -INFINITY;
 #pragma unroll
@@ -334,6 +352,14 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
             d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, ka, 0x04030402u)) - bias, u32_as_h2(q16.y), d, false);
             d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, kb, 0x04010400u)) - bias, u32_as_h2(q16.z), d, false);
             d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, kb, 0x04030402u)) - bias, u32_as_h2(q16.w), d, false);
+        }
+        else if constexpr (FP8KV)
+        {
+            const uint4 k16 = dequant8_fp8(make_uint2(kreg[i].x, kreg[i].y));
+            d = dot2(q16.x, k16.x, d);
+            d = dot2(q16.y, k16.y, d);
+            d = dot2(q16.z, k16.z, d);
+            d = dot2(q16.w, k16.w, d);
         }
         else
         {
@@ -378,7 +404,10 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
         else
         {
             float vf[8];
-            h8_to_f(vreg[i], vf);
+            if constexpr (FP8KV)
+                h8_to_f(dequant8_fp8(make_uint2(vreg[i].x, vreg[i].y)), vf);
+            else
+                h8_to_f(vreg[i], vf);
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 o[j] = fmaf(p16, vf[j], o[j]);
@@ -392,6 +421,8 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
         {
             if constexpr (INT8KV)
                 o[j] = s_qo * (o[j] - 128.f * l16); // sum p (u - 128) = sum p u - 128 sum p
+            if constexpr (FP8KV)
+                o[j] = s_qo * o[j];
             o[j] = fmaf(p_new, vf[j], o[j]);
         }
     }
@@ -581,25 +612,34 @@ int launch_nit(const MmhaParams& p, hipStream_t stream)
     dim3 grid(ns, p.num_heads, p.batch);
     const bool beam = p.beam_width > 1 && p.cache_indirection;
     const int mode = p.block_pointers ? CACHE_PAGED : (beam ? CACHE_BEAM : CACHE_LINEAR);
-#define TLLM_MMHA_LAUNCH(I8, MODE)                                                                                     \
-    hipLaunchKernelGGL((mmha_partial_kernel<DH, NIT, I8, MODE>), grid, dim3(256), 0, stream, p, ws_ml, ws_o, ns)
+#define TLLM_MMHA_LAUNCH(ELEM, MODE)                                                                                   \
+    hipLaunchKernelGGL((mmha_partial_kernel<DH, NIT, ELEM, MODE>), grid, dim3(256), 0, stream, p, ws_ml, ws_o, ns)
     if (p.int8_kv)
     {
         if (mode == CACHE_PAGED)
-            TLLM_MMHA_LAUNCH(true, CACHE_PAGED);
+            TLLM_MMHA_LAUNCH(KV_I8, CACHE_PAGED);
         else if (mode == CACHE_BEAM)
-            TLLM_MMHA_LAUNCH(true, CACHE_BEAM);
+            TLLM_MMHA_LAUNCH(KV_I8, CACHE_BEAM);
         else
-            TLLM_MMHA_LAUNCH(true, CACHE_LINEAR);
+            TLLM_MMHA_LAUNCH(KV_I8, CACHE_LINEAR);
+    }
+    else if (p.fp8_kv)
+    {
+        if (mode == CACHE_PAGED)
+            TLLM_MMHA_LAUNCH(KV_F8, CACHE_PAGED);
+        else if (mode == CACHE_BEAM)
+            TLLM_MMHA_LAUNCH(KV_F8, CACHE_BEAM);
+        else
+            TLLM_MMHA_LAUNCH(KV_F8, CACHE_LINEAR);
     }
     else
     {
         if (mode == CACHE_PAGED)
-            TLLM_MMHA_LAUNCH(false, CACHE_PAGED);
+            TLLM_MMHA_LAUNCH(KV_F16, CACHE_PAGED);
         else if (mode == CACHE_BEAM)
-            TLLM_MMHA_LAUNCH(false, CACHE_BEAM);
+            TLLM_MMHA_LAUNCH(KV_F16, CACHE_BEAM);
         else
-            TLLM_MMHA_LAUNCH(false, CACHE_LINEAR);
+            TLLM_MMHA_LAUNCH(KV_F16, CACHE_LINEAR);
     }
 #undef TLLM_MMHA_LAUNCH
     if (!p.tail_tickets)
@@ -695,6 +735,16 @@ int launch_mmha(const MmhaParams& p, hipStream_t stream)
     if (p.int8_kv && (!p.kv_scale_orig_quant || !p.kv_scale_quant_orig))
     {
         set_error("mmha: int8 KV cache needs both scales");
+        return -1;
+    }
+    if (p.fp8_kv && p.int8_kv)
+    {
+        set_error("mmha: int8_kv and fp8_kv are exclusive");
+        return -1;
+    }
+    if (p.fp8_kv && (!p.kv_scale_orig_quant || !p.kv_scale_quant_orig))
+    {
+        set_error("mmha: fp8 KV cache needs both scales");
         return -1;
     }
     if (p.timestep_host >= p.max_seq_len)

@@ -475,6 +475,8 @@ __global__ __launch_bounds__(256) void fill_random_kernel(void* dst, int dtype, 
             reinterpret_cast<uint16_t*>(dst)[i] = f2h(((float) (r >> 8) * (1.f / 8388608.f) - 1.f) * scale);
         else if (dtype == DT_INT8)
             reinterpret_cast<int8_t*>(dst)[i] = (int8_t) ((int) (r % 255u) - 127);
+        else if (dtype == DT_FP8) // finite E4M3 codes only, |x| < 2 (exponent field <= 7): never the NaN codes 0x7f / 0xff
+            reinterpret_cast<uint8_t*>(dst)[i] = (uint8_t) ((r & 0x80u) | ((r >> 8) & 0x3fu));
         else
             reinterpret_cast<float*>(dst)[i] = ((float) (r >> 8) * (1.f / 8388608.f) - 1.f) * scale;
     }

@@ -136,8 +136,9 @@ public:
         // reserved plugin features, rejected with a clear error until built
         if (c.multi_query_mode)
             throw std::runtime_error("GPTAttention: multi_query_mode not built (LLaMA-7B is MHA)");
-        if (c.fp8_kv_cache)
-            throw std::runtime_error("GPTAttention: fp8_kv_cache not built");
+        // the reference lets int8 win when both are set (gptAttentionCommon.cpp:137); here a cache has one element type
+        if (c.fp8_kv_cache && c.int8_kv_cache)
+            throw std::runtime_error("GPTAttention: int8_kv_cache and fp8_kv_cache are exclusive");
         if (c.in_flight_batching)
             throw std::runtime_error("GPTAttention: in_flight_batching not built");
         if (!c.unidirectional)
@@ -177,13 +178,13 @@ public:
         const Desc& d = io[pos];
         if (!linear_fmt(d))
             return false;
-        const int nin_expected = 8 + (c.int8_kv_cache ? 2 : 0) + (c.paged_kv_cache ? 1 : 0);
+        const int nin_expected = 8 + (quant_kv() ? 2 : 0) + (c.paged_kv_cache ? 1 : 0);
         if (nin != nin_expected)
             return false;
         if (pos == 0 || pos == nin)
             return d.type == c.type_id;
         if (pos == 1 || pos == nin + 1)
-            return d.type == (c.int8_kv_cache ? TLLM_INT8 : c.type_id);
+            return d.type == (c.int8_kv_cache ? TLLM_INT8 : (c.fp8_kv_cache ? TLLM_FP8 : c.type_id));
         if (pos >= 2 && pos <= 7)
             return d.type == TLLM_INT32;
         if (c.paged_kv_cache && pos == block_pointers_idx())
@@ -191,7 +192,8 @@ public:
         return d.type == TLLM_FLOAT; // kv scales
     }
 
-    int block_pointers_idx() const { return c.int8_kv_cache ? 10 : 8; } // gptAttentionPlugin.h:156-159
+    bool quant_kv() const { return c.int8_kv_cache || c.fp8_kv_cache; } // one-byte cache elements + the two scale inputs
+    int block_pointers_idx() const { return quant_kv() ? 10 : 8; } // gptAttentionPlugin.h:156-159
 
     size_t workspaceSize(const Desc* in, int nin, const Desc* out, int nout) const override
     {
@@ -208,7 +210,7 @@ public:
     int enqueue(const Desc* inDesc, const Desc* outDesc, const void* const* in, void* const* out, void* ws,
         hipStream_t stream) override
     {
-        const int nin_expected = 8 + (c.int8_kv_cache ? 2 : 0);
+        const int nin_expected = 8 + (quant_kv() ? 2 : 0);
         (void) nin_expected;
         const bool packed = c.remove_input_padding != 0; // tokens of all sequences back to back (gptAttentionPlugin.cpp:344-356)
         const int B = packed ? inDesc[5].dims.d[0] : inDesc[0].dims.d[0];
@@ -291,6 +293,7 @@ public:
             p.neox = c.neox_rotary_style;
             p.inv_sqrt_dh = inv_sqrt_dh;
             p.int8_kv = c.int8_kv_cache;
+            p.fp8_kv = c.fp8_kv_cache;
             p.max_seq_len = Smax;
             p.qkv = const_cast<void*>(in[0]);
             p.kv_cache = out[1];
@@ -305,7 +308,7 @@ public:
                 p.cache_seq_stride = rows == B ? 1 : beam_width;
             }
             p.input_lengths = static_cast<const int32_t*>(in[5]);
-            p.kv_scale_orig_quant = c.int8_kv_cache ? static_cast<const float*>(in[8]) : nullptr;
+            p.kv_scale_orig_quant = quant_kv() ? static_cast<const float*>(in[8]) : nullptr;
             p.rope_table = table;
             p.rope_table_len = table_len;
             p.out = out[0];
@@ -325,6 +328,7 @@ public:
         p.neox = c.neox_rotary_style;
         p.inv_sqrt_dh = inv_sqrt_dh;
         p.int8_kv = c.int8_kv_cache;
+        p.fp8_kv = c.fp8_kv_cache;
         p.max_seq_len = Smax;
         p.max_input_len = max_input_len;
         p.qkv = in[0];
@@ -349,7 +353,7 @@ public:
             p.tokens_per_block = tokens_per_block;
             p.max_blocks_per_seq = max_blocks;
         }
-        if (c.int8_kv_cache)
+        if (quant_kv())
         {
             p.kv_scale_orig_quant = static_cast<const float*>(in[8]);
             p.kv_scale_quant_orig = static_cast<const float*>(in[9]);

@@ -439,7 +439,7 @@ int verify_network(const std::string& network_json, const ScheduleDesc& d, std::
         const int qkv = linear(p + "attention.qkv", 0, h16, hq, hs, "");
         std::vector<int> ain = {qkv, in("past_key_value_" + std::to_string(i)), in("sequence_length"), in("past_key_value_length"),
             in("masked_tokens"), in("input_lengths"), in("max_input_length"), in("cache_indirection")};
-        if (d.int8_kv)
+        if (d.int8_kv || d.fp8_kv)
         {
             ain.push_back(P(p + "attention.kv_orig_quant_scale"));
             ain.push_back(P(p + "attention.kv_quant_orig_scale"));
@@ -449,7 +449,7 @@ int verify_network(const std::string& network_json, const ScheduleDesc& d, std::
         const Fields af = {{"num_heads", {(double) d.heads_per_rank}}, {"head_size", {(double) d.head_size}}, {"unidirectional", {1}},
             {"q_scaling", {1}}, {"rotary_embedding_dim", {(double) d.head_size}}, {"neox_rotary_style", {d.neox ? 1.0 : 0.0}},
             {"context_fmha_type", {0}}, {"multi_block_mode", {0}}, {"multi_query_mode", {0}},
-            {"int8_kv_cache", {d.int8_kv ? 1.0 : 0.0}}, {"fp8_kv_cache", {0}}, {"remove_input_padding", {d.packed ? 1.0 : 0.0}},
+            {"int8_kv_cache", {d.int8_kv ? 1.0 : 0.0}}, {"fp8_kv_cache", {d.fp8_kv ? 1.0 : 0.0}}, {"remove_input_padding", {d.packed ? 1.0 : 0.0}},
             {"mask_type", {1}}, {"paged_kv_cache", {d.paged ? 1.0 : 0.0}}, {"type_id", {HALF}}, {"in_flight_batching", {0}}};
         const int ctx = E.plugin("GPTAttention", ain, af, 2);
         present[i] = g.apply("plugin:GPTAttention", ain, fields_text(af), 1);

@@ -192,7 +192,7 @@ int32_t tllm_session_fake_context(tllm_session_t s, int32_t length, uint32_t see
     // a padded prompt of `length` real tokens: slots [length, max_in) are masked
     RUN(upload_prompt(s, ids.data(), lens.data(), st));
     for (int i = 0; i < s->num_layers; ++i)
-        RUN(launch_fill_random(s->layers[i].kv, s->int8_kv ? DT_INT8 : DT_HALF, s->kv_elems, seed + 7919u * i, 1.0f, st));
+        RUN(launch_fill_random(s->layers[i].kv, s->fp8_kv ? DT_FP8 : (s->int8_kv ? DT_INT8 : DT_HALF), s->kv_elems, seed + 7919u * i, 1.0f, st));
     RUN(s->run_sampler(0, st)); // prepares the RoPE row of the first generation step (the ids are overwritten next)
     RUN(launch_fill_i32(s->cur_ids, 3, B, st));
     RUN(launch_embedding(s->x, s->cur_ids, s->emb, B, s->hidden, s->vocab, st)); // what the sampler would have left in x
@@ -553,7 +553,7 @@ int64_t tllm_session_step_bytes(tllm_session_t s, int32_t context_len)
         return b;
     };
     int64_t bytes = lin(s->head);
-    const int64_t kv_row = (int64_t) 2 * s->Hr * s->Dh * (s->int8_kv ? 1 : 2);
+    const int64_t kv_row = (int64_t) 2 * s->Hr * s->Dh * (int64_t) s->kv_esz();
     for (auto& L : s->layers)
         bytes += lin(L.qkv) + lin(L.dense) + lin(L.fc) + lin(L.gate) + lin(L.proj) + kv_row * s->B * (context_len + 1);
     return bytes;

@@ -28,7 +28,8 @@ enum QuantBits
     QM_ACTIVATIONS = 4,
     QM_PER_CHANNEL = 8,
     QM_PER_TOKEN = 16,
-    QM_INT8_KV = 32
+    QM_INT8_KV = 32,
+    QM_FP8_KV = 64
 };
 
 struct TensorRec
@@ -116,6 +117,8 @@ struct tllm_session
     // derived
     int Hr = 0, Dh = 0, Dr = 0, Ir = 0, Vr = 0;
     bool sq = false, woq = false, int8_kv = false, per_token = false, per_channel = false;
+    bool fp8_kv = false; // OCP E4M3 cache (quant_mode bit 64): one-byte elements and the two scales of int8_kv, never both
+    size_t kv_esz() const { return (int8_kv || fp8_kv) ? 1 : 2; }
     int wtype = tllm::kernels::W_FP16; // of every layer's five projections (lm_head stays fp16)
 
     std::map<std::string, TensorRec> tensors;

@@ -109,6 +109,7 @@ int tllm_session::context_attention(const Layer& L, bool q_in_attn, hipStream_t 
     c.neox = neox;
     c.inv_sqrt_dh = 1.f / sqrtf((float) Dh);
     c.int8_kv = int8_kv;
+    c.fp8_kv = fp8_kv;
     c.max_seq_len = Smax;
     c.qkv = qkv;
     c.kv_cache = L.kv;

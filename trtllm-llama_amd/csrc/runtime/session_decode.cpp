@@ -387,6 +387,7 @@ int tllm_session::stage_attention(const DecodeStep& ds, int li)
     m.neox = neox;
     m.inv_sqrt_dh = 1.f / sqrtf((float) Dh);
     m.int8_kv = int8_kv;
+    m.fp8_kv = fp8_kv;
     m.max_seq_len = Smax;
     m.max_input_len = max_in;
     m.qkv = qkv;

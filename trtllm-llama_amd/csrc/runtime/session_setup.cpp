@@ -30,7 +30,7 @@ int tllm_session::alloc_buffers()
 {
     const int S = max_in, D = hidden;
     const size_t M = std::max((size_t) Bc * S, (size_t) B); // prompt rows; the generation phase needs B
-    const size_t kv_esz = int8_kv ? 1 : 2;
+    const size_t kv_esz = this->kv_esz();
     size_t kv_bytes = (size_t) B * 2 * Hr * Smax * Dh * kv_esz;
     const int T = tokens_per_block;
     max_blocks = paged_kv ? (Smax + T - 1) / T : 0;
@@ -181,6 +181,10 @@ int tllm_session::decide_decode_form()
     // (resolve_linear), so that type is the kind of all layers.
     const bool fp16_w = wtype == W_FP16, woq4 = wtype == W_INT4_WOQ;
     const int wkind = wtype == W_INT8_SQ ? 0 : (wtype == W_INT8_WOQ ? 1 : (fp16_w ? 2 : 3)); // qkv_attn_fused_serves' weight_kind
+    // an fp8 cache runs the separate launches (QKV GEMV, attention with its in-launch merge, O GEMV): the one-launch form has no
+    // E4M3 instance yet
+    if (fp8_kv)
+        return 0;
     const int kv8 = int8_kv ? 1 : 0;
     if (fuse_qkv_cfg == 0 || !attn_tail || B != 1 || beam != 1 || paged_kv || tp != 1 || !neox
         || !qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0))

@@ -207,6 +207,12 @@ tllm_session_t tllm_session_create(const char* config_text)
     s->sq = (qm & QM_ACTIVATIONS) && (qm & QM_INT8_WEIGHTS);
     s->woq = !s->sq && (qm & (QM_INT8_WEIGHTS | QM_INT4_WEIGHTS));
     s->int8_kv = qm & QM_INT8_KV;
+    s->fp8_kv = qm & QM_FP8_KV;
+    if (s->int8_kv && s->fp8_kv)
+    {
+        set_error("tllm_session_create: quant_mode %d sets both INT8_KV_CACHE (32) and FP8_KV_CACHE (64); a cache has one element type", qm);
+        return nullptr;
+    }
     s->per_token = qm & QM_PER_TOKEN;
     s->per_channel = qm & QM_PER_CHANNEL;
     if (s->woq)
@@ -284,7 +290,7 @@ int32_t tllm_session_finalize(tllm_session_t s)
             RUN(s->scalar_f32(p + "attention.quantization_scaling_factor", &L.attn_qscale));
             RUN(s->scalar_f32(p + "mlp.quantization_scaling_factor", &L.mlp_qscale));
         }
-        if (s->int8_kv)
+        if (s->int8_kv || s->fp8_kv)
         {
             RUN(s->scalar_f32(p + "attention.kv_orig_quant_scale", &L.kv_oq));
             RUN(s->scalar_f32(p + "attention.kv_quant_orig_scale", &L.kv_qo));
@@ -383,6 +389,7 @@ int verify_engine_network(tllm_session_t s, const std::vector<EngineEntry>& ents
     d.woq = s->woq;
     d.int4 = s->wtype == W_INT4_WOQ;
     d.int8_kv = s->int8_kv;
+    d.fp8_kv = s->fp8_kv;
     d.paged = s->paged_kv;
     d.packed = s->packed;
     d.neox = s->neox != 0;

@@ -71,6 +71,9 @@ def parse_arguments(args=None):
     p.add_argument('--per_channel', default=False, action='store_true')
     p.add_argument('--per_token', default=False, action='store_true')
     p.add_argument('--int8_kv_cache', default=False, action='store_true')
+    p.add_argument('--fp8_kv_cache', default=False, action='store_true',
+                   help='OCP E4M3 KV cache: the bytes of the int8 cache without a calibration run (scale 1.0 unless the '
+                        'model directory holds a calibrated one)')
     p.add_argument('--random_seed', type=int, default=None)
     p.add_argument('--paged_kv_cache', action='store_true', default=False)
     args = p.parse_args(args)
@@ -95,8 +98,12 @@ def parse_arguments(args=None):
         args.quant_mode = QuantMode.use_weight_only(args.weight_only_precision == 'int4')
     else:
         args.quant_mode = QuantMode(0)
+    if args.int8_kv_cache and args.fp8_kv_cache:
+        p.error('--int8_kv_cache and --fp8_kv_cache are exclusive: a cache has one element type')
     if args.int8_kv_cache:
         args.quant_mode = args.quant_mode.set_int8_kv_cache()
+    if args.fp8_kv_cache:
+        args.quant_mode = args.quant_mode.set_fp8_kv_cache()
     return args
 
 

@@ -24,9 +24,10 @@ def _f32(x, dev):
 
 @torch.no_grad()
 def engine_tensors(sd, num_layers, mode='fp16', act_range=None, alpha=0.5, per_channel=True, per_token=False,
-                   int8_kv=False, num_heads=None, threads=16, alpha_down=None):
+                   int8_kv=False, num_heads=None, threads=16, alpha_down=None, fp8_kv=False):
     """sd: HF-named state dict (torch tensors, one device).  mode: 'fp16' | 'woq8' | 'woq4' | 'sq'.
-    `act_range` (capture_activation_range of the UN-smoothed model) is needed for 'sq' and for int8_kv; with 'sq' the
+    `act_range` (capture_activation_range of the UN-smoothed model) is needed for 'sq' and for int8_kv (fp8_kv takes the
+    calibrated scale when there is one, else 1.0); with 'sq' the
     state dict is smoothed on a float32 copy first.  Returns {engine tensor name: torch tensor}."""
     dev = sd['model.embed_tokens.weight'].device
     out = {'vocab_embedding.weight': sd['model.embed_tokens.weight'].half().contiguous(),
@@ -37,6 +38,7 @@ def engine_tensors(sd, num_layers, mode='fp16', act_range=None, alpha=0.5, per_c
         act_range = {k: {kk: vv.clone() for kk, vv in v.items()} for k, v in act_range.items()}
         sd = {k: (v.detach().float().clone() if '.layers.' in k else v) for k, v in sd.items()}
         smooth_llama_model(sd, act_range, alpha, num_layers, num_heads, num_heads, alpha_down=alpha_down)
+    assert not (int8_kv and fp8_kv), 'int8_kv and fp8_kv are exclusive'
     woq_jobs = []
     for i in range(num_layers):
         hp, p = f'model.layers.{i}.', f'layers.{i}.'
@@ -94,6 +96,12 @@ def engine_tensors(sd, num_layers, mode='fp16', act_range=None, alpha=0.5, per_c
             if mode != 'sq':
                 assert qkv_range is not None, 'int8 KV cache needs calibrated activation ranges'
                 kv_scale = np.array([float(qkv_range['y'].max()) / 127.0], np.float32)
+            out[p + 'attention.kv_quant_orig_scale'] = _f32(kv_scale, dev)
+            out[p + 'attention.kv_orig_quant_scale'] = _f32(1.0 / kv_scale, dev)
+        if fp8_kv:
+            # E4M3 covers +-448: the calibrated scale of the QKV output when there is one, else 1.0
+            if mode != 'sq':
+                kv_scale = np.array([float(qkv_range['y'].max()) / 127.0 if qkv_range is not None else 1.0], np.float32)
             out[p + 'attention.kv_quant_orig_scale'] = _f32(kv_scale, dev)
             out[p + 'attention.kv_orig_quant_scale'] = _f32(1.0 / kv_scale, dev)
     if woq_jobs:

@@ -89,6 +89,13 @@ def load_from_hf_llama(tensorrt_llm_llama, hf_llama, rank=0, tensor_parallel=1, 
             s = np.float32(kv_scales[i])
             layer.attention.kv_orig_quant_scale.value = np.array([1.0 / s], np.float32)
             layer.attention.kv_quant_orig_scale.value = np.array([s], np.float32)
+        elif quant_mode.has_fp8_kv_cache():
+            # E4M3 covers +-448: usable without calibration (scale 1.0); a calibrated kv_scales[layer] is taken when given
+            s = np.float32(kv_scales[i]) if kv_scales is not None else np.float32(1.0)
+            layer.attention.kv_orig_quant_scale.value = np.array([1.0 / s], np.float32)
+            layer.attention.kv_quant_orig_scale.value = np.array([s], np.float32)
+    if quant_mode.has_fp8_kv_cache():
+        print('fp8 KV cache: ' + ('calibrated kv_scales' if kv_scales is not None else 'kv_orig_quant = kv_quant_orig = 1.0'))
     tensorrt_llm.logger.info(f'Weights loaded. Total time: {time.time() - tik:.1f} s')
 
 
@@ -180,6 +187,7 @@ def load_from_ft_llama(tensorrt_llm_llama, dir_path, rank=0, tensor_parallel=1, 
         if not per_tok:
             module.act_scale.value = need(f'{base}.scale_y_quant_orig.bin', None, np.float32).reshape(-1)[:1].reshape(1, 1)
 
+    fp8_kv_calibrated = 0
     for i, layer in enumerate(m.layers):
         p = f'model.model.layers.{i}.'
         layer.input_layernorm.weight.value = need(p + 'input_layernorm.weight.bin')
@@ -213,4 +221,14 @@ def load_from_ft_llama(tensorrt_llm_llama, dir_path, rank=0, tensor_parallel=1, 
             t = need(p + 'attention.query_key_value.scale_y_quant_orig.bin', None, np.float32).reshape(-1)[:1]
             layer.attention.kv_orig_quant_scale.value = (1.0 / t).astype(np.float32)
             layer.attention.kv_quant_orig_scale.value = t.astype(np.float32)
+        elif quant_mode.has_fp8_kv_cache():
+            # the directory's calibrated scale when it is there, else 1.0: E4M3 covers +-448 and needs no calibration run
+            t = fromfile(p + 'attention.query_key_value.scale_y_quant_orig.bin', None, np.float32)
+            fp8_kv_calibrated += t is not None
+            t = np.ones(1, np.float32) if t is None else t.reshape(-1)[:1]
+            layer.attention.kv_orig_quant_scale.value = (1.0 / t).astype(np.float32)
+            layer.attention.kv_quant_orig_scale.value = t.astype(np.float32)
+    if quant_mode.has_fp8_kv_cache():
+        print(f'fp8 KV cache: calibrated scale from {d} for {fp8_kv_calibrated} of {len(m.layers)} layers, '
+              f'kv_orig_quant = kv_quant_orig = 1.0 for the rest')
     tensorrt_llm.logger.info(f'Weights loaded. Total time: {time.time() - tik:.1f} s')

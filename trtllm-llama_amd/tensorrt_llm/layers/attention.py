@@ -16,7 +16,7 @@ class Attention(Module):
                  apply_query_key_layer_scaling=False, attention_mask_type=AttentionMaskType.padding, bias=True,
                  dtype=None, position_embedding_type=PositionEmbeddingType.learned_absolute, neox_rotary_style=False,
                  use_int8_kv_cache=False, rotary_embedding_percentage=1.0, tp_group=None, tp_size=1,
-                 multi_block_mode=False, multi_query_mode=False):
+                 multi_block_mode=False, multi_query_mode=False, use_fp8_kv_cache=False):
         super().__init__()
         self.attention_mask_type = attention_mask_type
         self.attention_head_size = hidden_size // num_attention_heads
@@ -40,7 +40,10 @@ class Attention(Module):
             self.rotary_embedding_dim = int(self.attention_head_size * rotary_embedding_percentage)  # :88-92
         self.dtype = dtype
         self.use_int8_kv_cache = use_int8_kv_cache
-        if use_int8_kv_cache:  # :98-104
+        self.use_fp8_kv_cache = use_fp8_kv_cache
+        if use_int8_kv_cache and use_fp8_kv_cache:
+            raise ValueError('use_int8_kv_cache and use_fp8_kv_cache are exclusive: a cache has one element type')
+        if use_int8_kv_cache or use_fp8_kv_cache:  # :98-104 (the fp8 cache takes the same two scales)
             self.kv_orig_quant_scale = Parameter(shape=(1, ), dtype='float32')
             self.kv_quant_orig_scale = Parameter(shape=(1, ), dtype='float32')
         else:
@@ -66,13 +69,14 @@ class Attention(Module):
         assert hidden_states.row_lengths is not None
         if self.position_embedding_type == PositionEmbeddingType.alibi:
             raise ValueError('ALiBi is only supported without GPTAttention plugin')
-        kv_oq = self.kv_orig_quant_scale.value if self.use_int8_kv_cache else None
-        kv_qo = self.kv_quant_orig_scale.value if self.use_int8_kv_cache else None
+        quant_kv = self.use_int8_kv_cache or self.use_fp8_kv_cache
+        kv_oq = self.kv_orig_quant_scale.value if quant_kv else None
+        kv_qo = self.kv_quant_orig_scale.value if quant_kv else None
         return gpt_attention(qkv, past_key_value, sequence_length, past_key_value_length, masked_tokens,
                              hidden_states.row_lengths, hidden_states.max_row_length, cache_indirection,
                              self.num_attention_heads, self.attention_head_size, self.q_scaling,
                              self.rotary_embedding_dim, self.neox_rotary_style, self.multi_block_mode,
-                             self.multi_query_mode, kv_oq, kv_qo, self.use_int8_kv_cache,
+                             self.multi_query_mode, kv_oq, kv_qo, self.use_int8_kv_cache, self.use_fp8_kv_cache,
                              kv_cache_block_pointers=kv_cache_block_pointers)
 
     def forward(self, hidden_states: RaggedTensor, attention_mask=None, past_key_value=None, sequence_length=None,

@@ -42,7 +42,8 @@ class LLaMADecoderLayer(Module):
                                    position_embedding_type=PositionEmbeddingType.rope,
                                    neox_rotary_style=neox_rotary_style, multi_query_mode=multi_query_mode,
                                    tp_group=tp_group, tp_size=tp_size,
-                                   use_int8_kv_cache=quant_mode.has_int8_kv_cache())
+                                   use_int8_kv_cache=quant_mode.has_int8_kv_cache(),
+                                   use_fp8_kv_cache=quant_mode.has_fp8_kv_cache())
         self.mlp = GatedMLP(hidden_size=hidden_size, ffn_hidden_size=self.mlp_hidden_size, hidden_act=hidden_act,
                             dtype=dtype, bias=False, tp_group=tp_group, tp_size=tp_size)
         self.post_layernorm = RmsNorm(normalized_shape=hidden_size, dtype=dtype)
@@ -114,6 +115,8 @@ class LLaMAForCausalLM(LLaMAModel):
         self.kv_dtype = str_dtype_to_trt(dtype) if isinstance(dtype, str) else DataType(dtype)
         if quant_mode.has_int8_kv_cache():
             self.kv_dtype = str_dtype_to_trt('int8')
+        elif quant_mode.has_fp8_kv_cache():
+            self.kv_dtype = DataType.FP8
         self.quant_mode = quant_mode
         self.num_layers = num_layers
         self.num_heads = num_heads

@@ -208,17 +208,17 @@ class SmoothQuantGatedMLP(Module):
 
 
 class SmoothQuantAttention(Attention):
-    """int8 QKV GEMM -> fp16 -> GPTAttention plugin (RoPE, fp16|int8 KV) -> quantise context -> int8 dense GEMM."""
+    """int8 QKV GEMM -> fp16 -> GPTAttention plugin (RoPE, fp16|int8|fp8 KV) -> quantise context -> int8 dense GEMM."""
 
     def __init__(self, hidden_size, num_attention_heads, max_position_embeddings, num_layers=1,
                  apply_query_key_layer_scaling=False, attention_mask_type=AttentionMaskType.causal, bias=False,
                  dtype=None, position_embedding_type=PositionEmbeddingType.rope, neox_rotary_style=True,
                  use_int8_kv_cache=False, tp_group=None, tp_size=1, multi_block_mode=False, multi_query_mode=False,
-                 quant_mode=QuantMode(0)):
+                 quant_mode=QuantMode(0), use_fp8_kv_cache=False):
         super().__init__(hidden_size, num_attention_heads, max_position_embeddings, num_layers,
                          apply_query_key_layer_scaling, attention_mask_type, False, dtype, position_embedding_type,
                          neox_rotary_style, use_int8_kv_cache, 1.0, tp_group, tp_size, multi_block_mode,
-                         multi_query_mode)
+                         multi_query_mode, use_fp8_kv_cache)
         self.quant_mode = quant_mode
         self.qkv = SmoothQuantLinear(hidden_size, hidden_size * 3, bias=bias, dtype=dtype, tp_group=tp_group,
                                      tp_size=tp_size, gather_output=False, quant_mode=quant_mode)
