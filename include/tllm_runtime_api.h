@@ -26,6 +26,10 @@ typedef struct tllm_session* tllm_session_t;
 
 /* Create a session from a configuration text.  Recognised keys (defaults in parentheses):
  *   num_layers, num_heads, hidden_size, inter_size, vocab_size, max_position_embeddings (2048),
+ *   num_kv_heads (num_heads; grouped-query attention: Hkv K/V heads, query head h reads K/V head h / (num_heads / Hkv); the
+ *   attention.qkv weight is [(H + 2 Hkv) Dh / tp, hidden] in the block order q | k | v, the cache [B, 2, Hkv / tp, Smax, Dh]; refused
+ *   with an error naming the key when it does not divide num_heads, when tp_size does not divide it, or with SmoothQuant
+ *   weights; a session with Hkv != num_heads runs the separate-launch generation step),
  *   rms_norm_eps (1e-6), tp_size (1), tp_rank (0), quant_mode (0: QuantMode bits,
  *   T/tensorrt_llm/quantization/mode.py:6-21; bit 32 = int8 KV cache, bit 64 = fp8 (OCP E4M3) KV cache: one-byte cache
  *   elements and the two attention.kv_*_scale tensors per layer either way, the two bits are exclusive and an fp8 session runs
@@ -369,6 +373,64 @@ int32_t tllm_gemm_tactic_lookup(int32_t wtype, int32_t M, int32_t N, int32_t K);
 /* Microbenchmark hook: while set (non-NULL), every workgroup of the phased SmoothQuant GEMM writes {shader cycles, ticks of
  * the constant 100 MHz counter} over its lifetime to device_buffer[2 * workgroup] (uint64) - the clock the chip held. */
 void tllm_gemm_set_clock_probe(void* device_buffer);
+
+/* Kernel-level entry for the two attention launchers (kernels/mmha_decode.hip, kernels/context_attn.hip) with grouped-query
+ * attention: num_kv_heads = Hkv K/V heads, 1 <= Hkv <= H, H % Hkv == 0, query head h reads K/V head h / (H / Hkv); 0 or H is
+ * multi-head attention, bit for bit what the GPTAttention plugin runs; Hkv = 1 is multi-query attention.  Layouts:
+ *   qkv     fp16, one row per token [ q: H*Dh | k: Hkv*Dh | v: Hkv*Dh ]; decode [B, row], context [B, S, row] or, packed
+ *           (cu_seqlens set), [sum(len), row]; the context launch rewrites q and k in place with RoPE applied;
+ *   cache   [B, 2, Hkv, Smax, Dh] fp16 / int8 / fp8 E4M3 (kv_cache_type TLLM_HALF / TLLM_INT8 / TLLM_FP8); paged (block_pointers
+ *           int64 [B, 2, max_blocks_per_seq] set): blocks [Hkv, tokens_per_block, Dh], kv_cache = the pool the blocks lie in (the
+ *           decode launch reads the rows of a block the table does not map yet - entry 0 - from there, and masks them);
+ *   out     fp16 [B, H*Dh] (decode), [B, S, H*Dh] or packed (context).
+ * Numerics are those documented at the head of the two kernel files, per query head on the K/V head it maps to; RoPE on the new
+ * k, the cache quantisation and the cache write happen once per K/V head.  The RoPE table is the process-wide one the plugin uses.
+ * Every field not needed is 0 / NULL (memset the struct). */
+typedef struct
+{
+    int32_t batch;         /* sequences (decode: batch x beam) */
+    int32_t seq;           /* context: the padded / longest prompt length; decode: ignored */
+    int32_t num_heads, num_kv_heads, head_size;
+    int32_t rotary_dim, neox;
+    float q_scaling;       /* scores * 1 / (sqrt(Dh) * q_scaling); 0 = 1 */
+    int32_t kv_cache_type; /* TLLM_HALF (or 0), TLLM_INT8, TLLM_FP8 */
+    int32_t max_seq_len;   /* cache capacity Smax */
+    int32_t max_input_len; /* decode: padded prompt length (RoPE position = timestep - (max_input_len - input_lengths[b])) */
+    int32_t timestep;      /* decode: past length from the host; -1 = sequence_length[b] */
+    void* qkv;
+    void* kv_cache;
+    const int32_t* sequence_length; /* decode: device int32 [B], slots in use; the new token goes to that slot */
+    const int32_t* input_lengths;   /* device int32 [B] */
+    const int32_t* masked_tokens;   /* decode: device int32 [B, Smax] or NULL */
+    const float* kv_scale_orig_quant; /* device f32 [1] (int8 / fp8 cache) */
+    const float* kv_scale_quant_orig; /* device f32 [1] (decode, int8 / fp8 cache) */
+    const int32_t* cache_indirection; /* decode, beam_width > 1: device int32 [B, Smax] */
+    int32_t beam_width;               /* 0 = 1 */
+    int32_t cache_seq_stride;         /* context: prompt b fills the cache rows of sequence b * cache_seq_stride; 0 = 1 */
+    const int64_t* block_pointers;
+    int32_t tokens_per_block, max_blocks_per_seq;
+    const int32_t* cu_seqlens; /* context, packed inputs: device int32 [B + 1] */
+    /* decode launch shape.  rows_per_group: cache rows per lane group and split (4, 12, 16); 0 = the plugin's rule.
+     * q_heads_per_workgroup: query heads of one K/V head served from one load of the cache rows (1, 2, 4, 8); 0 = the launcher's
+     * rule.  A forced value runs exactly that instance or the call returns non-zero with tllm_last_error() set and nothing
+     * launched - never a substitute.  combine_launch: 1 = merge the splits in a second launch even where the in-launch merge
+     * (at most 16 splits) would serve. */
+    int32_t rows_per_group, q_heads_per_workgroup, combine_launch;
+    const float* tail_quant_scale; /* decode, in-launch merge: static int8 image of the context row to tail_out_q8 */
+    void* tail_out_q8;
+    int8_t* out_q8; /* context: static int8 image instead of (MFMA kernel) or next to `out` */
+    const float* out_q_scale;
+    void* out;
+    void* workspace; /* tllm_attention_workspace_size() bytes; context: NULL runs the wave-per-query kernel */
+} tllm_attention_params_t;
+/* bytes of workspace for the decode (is_context 0: merge tickets + split partials) or the context launch (the V^T image) */
+size_t tllm_attention_workspace_size(const tllm_attention_params_t* p, int32_t is_context);
+int32_t tllm_attention_decode(const tllm_attention_params_t* p, tllm_stream_t stream);
+int32_t tllm_attention_context(const tllm_attention_params_t* p, tllm_stream_t stream);
+/* split geometry of the decode launch tllm_attention_decode would run for p: time steps per split, splits for max_seq_len, the
+ * query tile, and whether the splits are merged inside the launch (1) or by the combine launch (0).  Non-zero: p is refused. */
+int32_t tllm_attention_decode_layout(const tllm_attention_params_t* p, int32_t* tchunk, int32_t* nsplit, int32_t* q_tile,
+    int32_t* in_launch_merge);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,21 @@ using namespace dev;
 namespace
 {
 
+// grouped-query attention (ContextAttnParams::num_kv_heads): K/V heads, the halfs of a fused QKV row [q: H | k: Hkv | v: Hkv] and
+// the K/V head of query head h.  The launcher passes num_kv_heads resolved (never 0); with Hkv == H everything is as it was.
+__device__ __forceinline__ int kv_heads(const ContextAttnParams& p)
+{
+    return p.num_kv_heads;
+}
+__device__ __forceinline__ int64_t qkv_row_halfs(const ContextAttnParams& p, int DH)
+{
+    return (int64_t) (p.num_heads + 2 * p.num_kv_heads) * DH;
+}
+__device__ __forceinline__ int kv_head_of(const ContextAttnParams& p, int h)
+{
+    return p.num_kv_heads == p.num_heads ? h : h / (p.num_heads / p.num_kv_heads);
+}
+
 // first row of sequence b in the (padded or packed) token-major buffers
 __device__ __forceinline__ int64_t seq_row0(const ContextAttnParams& p, int b)
 {
@@ -36,11 +51,14 @@ __device__ __forceinline__ int64_t seq_row0(const ContextAttnParams& p, int b)
 // One (token s, head h) of sequence b, handled by a group of DH / 8 consecutive lanes (li = lane in the group): RoPE on q and k in
 // place, padding rows zeroed, k / v appended to the cache (rope_kv_load + rope_kv_finish).  rope_kv_finish returns this lane's 8 v
 // elements as attention will see them (zero for padding positions); every lane of the group must call it (shuffles inside the group).
+// Grouped-query attention: the row of query head h < Hkv also carries K/V head h (RoPE on k, quantisation and the cache write
+// happen once per K/V head); the rows of the heads h >= Hkv carry q alone (has_kv false: k / v are loaded from K/V head 0 to keep
+// the loads unconditional, and never stored).
 struct RopeRow
 {
     uint4 q4, k4, v4;
     uint16_t *qp, *kp, *vp;
-    bool valid, has_row;
+    bool valid, has_row, has_kv;
 };
 
 // the loads of one (token, head) - split from the rest so that a caller with several rows can have all of them in flight
@@ -48,13 +66,15 @@ template <int DH>
 __device__ __forceinline__ RopeRow rope_kv_load(const ContextAttnParams& p, int s, int h, int b, int li)
 {
     RopeRow r;
-    const int H = p.num_heads;
+    const int H = p.num_heads, Hkv = kv_heads(p);
     r.valid = s < p.input_lengths[b];
     r.has_row = r.valid || !p.cu_seqlens; // packed buffers hold no padding rows
-    uint16_t* row = reinterpret_cast<uint16_t*>(p.qkv) + (seq_row0(p, b) + (r.has_row ? s : 0)) * 3 * H * DH;
+    r.has_kv = h < Hkv;
+    const int kvh = r.has_kv ? h : 0;
+    uint16_t* row = reinterpret_cast<uint16_t*>(p.qkv) + (seq_row0(p, b) + (r.has_row ? s : 0)) * qkv_row_halfs(p, DH);
     r.qp = row + (int64_t) h * DH + li * 8;
-    r.kp = row + (int64_t) (H + h) * DH + li * 8;
-    r.vp = row + (int64_t) (2 * H + h) * DH + li * 8;
+    r.kp = row + (int64_t) (H + kvh) * DH + li * 8;
+    r.vp = row + (int64_t) (H + Hkv + kvh) * DH + li * 8;
     r.q4 = *reinterpret_cast<const uint4*>(r.qp);
     r.k4 = *reinterpret_cast<const uint4*>(r.kp);
     r.v4 = *reinterpret_cast<const uint4*>(r.vp);
@@ -65,7 +85,7 @@ template <int DH>
 __device__ __forceinline__ uint4 rope_kv_finish(const ContextAttnParams& p, int s, int h, int b, int li, const RopeRow& r)
 {
     constexpr int LPR = DH / 8;
-    const int H = p.num_heads;
+    const int Hkv = kv_heads(p); // the cache holds K/V heads; h < Hkv wherever has_kv
     const bool valid = r.valid, has_row = r.has_row;
     uint16_t *qp = r.qp, *kp = r.kp, *vp = r.vp;
     uint4 q4 = r.q4, k4 = r.k4, v4 = r.v4;
@@ -125,17 +145,20 @@ __device__ __forceinline__ uint4 rope_kv_finish(const ContextAttnParams& p, int 
     if (has_row)
     {
         *reinterpret_cast<uint4*>(qp) = q4;
-        *reinterpret_cast<uint4*>(kp) = k4;
-        if (!valid)
-            *reinterpret_cast<uint4*>(vp) = v4;
+        if (r.has_kv)
+        {
+            *reinterpret_cast<uint4*>(kp) = k4;
+            if (!valid)
+                *reinterpret_cast<uint4*>(vp) = v4;
+        }
     }
-    if (s < p.max_seq_len)
+    if (s < p.max_seq_len && r.has_kv)
     {
         const int esz = (p.int8_kv || p.fp8_kv) ? 1 : 2;
         char* kc = reinterpret_cast<char*>(p.kv_cache)
-            + (((int64_t) (b * p.cache_seq_stride * 2 + 0) * H + h) * p.max_seq_len + s) * DH * esz + li * 8 * esz;
+            + (((int64_t) (b * p.cache_seq_stride * 2 + 0) * Hkv + h) * p.max_seq_len + s) * DH * esz + li * 8 * esz;
         char* vc = reinterpret_cast<char*>(p.kv_cache)
-            + (((int64_t) (b * p.cache_seq_stride * 2 + 1) * H + h) * p.max_seq_len + s) * DH * esz + li * 8 * esz;
+            + (((int64_t) (b * p.cache_seq_stride * 2 + 1) * Hkv + h) * p.max_seq_len + s) * DH * esz + li * 8 * esz;
         bool mapped = true;
         if (p.block_pointers) // uniform: paged cache, block s / tokens_per_block of the sequence, row s % tokens_per_block
         {
@@ -187,7 +210,7 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const ContextAttnPar
 }
 
 // The same per-row work for a tile of 64 tokens of ONE head, plus the V^T image the MFMA kernel stages its PV operand from
-// ([B, H, DH, spad] fp16, keys contiguous; keys beyond the sequence are zero): the v values pass through an LDS tile and leave
+// ([B, Hkv, DH, spad] fp16, keys contiguous; keys beyond the sequence are zero): the v values pass through an LDS tile and leave
 // transposed, so V is read once instead of by a transpose launch of its own (14.1 + 6.7 us per layer at S = 1024 before).
 // grid (spad / 64, H, B), 256 threads.
 template <int DH>
@@ -219,8 +242,10 @@ __global__ __launch_bounds__(256) void rope_kv_vt_kernel(const ContextAttnParams
         d[2] = v.z;
         d[3] = v.w;
     }
+    if (h >= kv_heads(p)) // block-uniform: a query head beyond the K/V heads has no V^T image
+        return;
     __syncthreads();
-    uint16_t* vt = reinterpret_cast<uint16_t*>(p.workspace) + ((int64_t) (b * p.num_heads + h) * DH) * spad + kv0;
+    uint16_t* vt = reinterpret_cast<uint16_t*>(p.workspace) + ((int64_t) (b * kv_heads(p) + h) * DH) * spad + kv0;
     for (int i = threadIdx.x; i < DH * 8; i += 256)
     {
         const int g = i % 8, d = i / 8; // 8 keys g * 8 .. + 8 of column d: eight consecutive lanes fill one 128-byte line of V^T
@@ -251,11 +276,12 @@ __global__ __launch_bounds__(256) void context_attn_kernel(const ContextAttnPara
             *reinterpret_cast<uint4*>(outp) = make_uint4(0, 0, 0, 0);
         return;
     }
-    const uint16_t* base = reinterpret_cast<const uint16_t*>(p.qkv) + seq_row0(p, b) * 3 * H * DH;
-    const int64_t rs = (int64_t) 3 * H * DH; // row stride
+    const int64_t rs = qkv_row_halfs(p, DH); // row stride
+    const int kvh = kv_head_of(p, h);
+    const uint16_t* base = reinterpret_cast<const uint16_t*>(p.qkv) + seq_row0(p, b) * rs;
     const uint4 q16 = *reinterpret_cast<const uint4*>(base + (int64_t) qi * rs + (int64_t) h * DH + li * 8);
-    const uint16_t* kb = base + (int64_t) (H + h) * DH + li * 8;
-    const uint16_t* vb = base + (int64_t) (2 * H + h) * DH + li * 8;
+    const uint16_t* kb = base + (int64_t) (H + kvh) * DH + li * 8;
+    const uint16_t* vb = base + (int64_t) (H + kv_heads(p) + kvh) * DH + li * 8;
 
     float m = -INFINITY, l = 0.f;
     float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -410,10 +436,11 @@ __global__ __launch_bounds__(128 * NQ) void context_attn_mfma_ks_kernel(const Co
     const int ql = lane & 31, hf = lane >> 5;
     const int q = q0 + ql;
     const int len = p.input_lengths[b];
-    const int64_t rs = (int64_t) 3 * H * DH * 2; // bytes per token row of the fused QKV buffer
+    const int64_t rs = qkv_row_halfs(p, DH) * 2; // bytes per token row of the fused QKV buffer
+    const int kvh = kv_head_of(p, h);            // its K rows and its V^T image are those of K/V head h / (H / Hkv)
     const char* qkv = reinterpret_cast<const char*>(p.qkv) + seq_row0(p, b) * rs;
     const int nrows = p.cu_seqlens ? len : S; // token rows of this sequence that exist in the buffers
-    const char* vt = reinterpret_cast<const char*>(p.workspace) + ((int64_t) (b * H + h) * DH) * spad * 2;
+    const char* vt = reinterpret_cast<const char*>(p.workspace) + ((int64_t) (b * kv_heads(p) + kvh) * DH) * spad * 2;
 
     // Q fragments (B operand): lane (q, half) holds d = 16 s + 8 half .. + 8 for every k-step s
     uint4 qf[KST];
@@ -473,7 +500,7 @@ __global__ __launch_bounds__(128 * NQ) void context_attn_mfma_ks_kernel(const Co
                 const int sub = c / 8, row = (c % 8) * 8 + r8;
                 const int col = (lane & 7) ^ ((row >> 1) & 7);
                 const int key = kv0 + row < nrows ? kv0 + row : nrows - 1;
-                src = qkv + (int64_t) key * rs + (int64_t) (H + h) * DH * 2 + sub * 128 + col * 16;
+                src = qkv + (int64_t) key * rs + (int64_t) (H + kvh) * DH * 2 + sub * 128 + col * 16;
             }
             else
             {
@@ -763,12 +790,20 @@ int launch_dh(const ContextAttnParams& p, hipStream_t stream)
 
 size_t context_attention_workspace_size(int batch, int num_heads, int head_size, int seq)
 {
-    // V^T scratch of the MFMA path: [B, H, Dh, roundup(S, 64)] fp16
+    // V^T scratch of the MFMA path: [B, Hkv, Dh, roundup(S, 64)] fp16; sized for Hkv = H, which covers every Hkv <= H
     return (size_t) batch * num_heads * head_size * ((seq + 63) / 64 * 64) * 2;
 }
 
-int launch_context_attention(const ContextAttnParams& p, hipStream_t stream)
+int launch_context_attention(const ContextAttnParams& pin, hipStream_t stream)
 {
+    ContextAttnParams p = pin;
+    if (p.num_kv_heads == 0)
+        p.num_kv_heads = p.num_heads;
+    if (p.num_heads < 1 || p.num_kv_heads < 1 || p.num_kv_heads > p.num_heads || p.num_heads % p.num_kv_heads)
+    {
+        set_error("context attention: num_kv_heads %d must divide num_heads %d", p.num_kv_heads, p.num_heads);
+        return -1;
+    }
     if (p.rotary_dim > 0 && (!p.rope_table || (p.neox && p.rotary_dim != p.head_size)))
     {
         set_error("context attention: bad rotary configuration");

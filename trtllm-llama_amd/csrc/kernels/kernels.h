@@ -169,7 +169,18 @@ struct MmhaParams
     void* tail_out_q8 = nullptr;             // s8 [B, H*Dh]
     void* out = nullptr;       // fp16 [B, H*Dh]
     void* workspace = nullptr; // mmha_workspace_size bytes
+    // grouped-query attention: Hkv K/V heads, 1 <= Hkv <= H, H % Hkv == 0, query head h reads K/V head h / (H / Hkv); 0 = num_heads.
+    // With Hkv != H:  qkv is fp16 [B, (H + 2*Hkv)*Dh] (q: H*Dh | k: Hkv*Dh | v: Hkv*Dh), the cache [B, 2, Hkv, Smax, Dh], paged
+    // blocks [Hkv, tokens_per_block, Dh]; tickets, workspace and `out` stay per QUERY head.
+    int32_t num_kv_heads = 0;
+    // query heads of one K/V head that a workgroup serves from ONE load of its cache rows: 1, 2, 4 or 8 (must divide H / Hkv; a
+    // value the launcher cannot run is an error, never a substitute); 0 = the launcher's rule (mmha_default_q_tile)
+    int32_t q_heads_per_workgroup = 0;
 };
+// the launcher's rule for q_heads_per_workgroup = 0
+int mmha_default_q_tile(int32_t num_heads, int32_t num_kv_heads);
+// num_kv_heads / q_heads_per_workgroup of p resolved (0 -> num_heads / the default tile) and checked; non-zero: refused, error set
+int mmha_resolve_grouping(MmhaParams& p);
 // Split geometry for a given rows_per_group: timesteps per split, number of splits for max_seq_len, and the byte
 // offset of the partial outputs inside the workspace ({max,sum} float2 [B,H,ns] first, then out f32 [B,H,ns,Dh]).
 int mmha_split_layout(int32_t head_size, int32_t max_seq_len, int32_t rows_per_group, int32_t batch, int32_t num_heads,
@@ -234,12 +245,13 @@ struct FusedQkvAttnParams
     void* x_out = nullptr;                 // fp16 [o_n]: may be x itself (every workgroup has consumed x long before)
 };
 size_t qkv_attn_fused_xchg_bytes(int32_t num_heads);
-bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t weight_kind = 0);
+bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t weight_kind = 0,
+    int32_t num_kv_heads = 0);
 // (woq8 / o_stage decide the instance and its dynamic LDS: the residency check - occupancy query x CUs of the current device >= grid
 // - is made for exactly the launch that will run)
 // weight_kind: 0 SmoothQuant int8, 1 weight-only int8, 2 fp16, 3 weight-only int4
 bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int32_t max_seq_len, int32_t int8_kv, int32_t weight_kind = 0,
-    int32_t o_stage = 0);
+    int32_t o_stage = 0, int32_t num_kv_heads = 0); // num_kv_heads != num_heads (and != 0): not served
 int launch_qkv_attn_fused(const FusedQkvAttnParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
@@ -317,6 +329,9 @@ struct ContextAttnParams
     // paged KV cache: see MmhaParams (kv_cache unused when set)
     const int64_t* block_pointers = nullptr;
     int32_t tokens_per_block = 0, max_blocks_per_seq = 0;
+    // grouped-query attention, as MmhaParams::num_kv_heads (0 = num_heads): qkv rows are [q: H*Dh | k: Hkv*Dh | v: Hkv*Dh], RoPE
+    // on k, the cache quantisation and the cache write run once per K/V head; `out` stays [B, S, H*Dh]
+    int32_t num_kv_heads = 0;
 };
 size_t context_attention_workspace_size(int batch, int num_heads, int head_size, int seq);
 // cu[0] = 0, cu[b + 1] = cu[b] + lens[b]  (device, one tiny launch; packed-input bookkeeping)

@@ -94,29 +94,41 @@ enum
     CACHE_PAGED = 2
 };
 
-template <int DH, int NIT, int KV, int CACHE>
-__global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, float2* ws_ml, float* ws_o, int nsplit_max)
+// QT: the query tile (grouped-query attention, MmhaParams::q_heads_per_workgroup) - the workgroup (split, tile, batch) loads its K
+// and V rows ONCE, exactly as the one-head form does, and then runs steps 4 - 5 for the QT query heads h0 .. h0 + QT - 1 of the
+// same K/V head one after the other on those registers: QT independent softmax partials, the cache rows the launch requests
+// 1 / QT of the head-mapped form's.  The heads of a tile take turns on the same LDS; hipcc hoists parts of the later heads'
+// work, so registers grow with QT (Dh 128, fp16, 16 rows: 216 -> 254 -> 256 + 25 -> 256 + 99 parked in AGPRs), no instance
+// uses scratch (profiles/gqa_attention.txt).  QT = 1 with the head map h -> h / group serves every group size; with Hkv == H it
+// is the kernel as it was.  Measured, the heads in turn cost more than the rows saved below ~4000 tokens of context: the rows of a
+// group already come from L2 in the head-mapped form.
+//   kv_magic = ceil(2^24 / group): kvh = h0 * kv_magic >> 24 is h0 / group without a division in front of the first loads
+//   (exact while H * group < 2^24; the launcher checks).
+template <int DH, int NIT, int KV, int CACHE, int QT>
+__global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, float2* ws_ml, float* ws_o, int nsplit_max,
+    uint32_t kv_magic, int group)
 {
     using G = MmhaGeom<DH, NIT>;
     constexpr int LPR = G::LPR, RPW = G::RPW, NGRP = G::NGRP;
-    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int c = blockIdx.x, h0 = blockIdx.y * QT, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane % LPR, grp = lane / LPR;
     const int gid = wid * RPW + grp; // lane group inside the workgroup
-    const int H = p.num_heads, Smax = p.max_seq_len;
+    const int H = p.num_heads, Hkv = p.num_kv_heads, Smax = p.max_seq_len; // the launcher passes Hkv resolved (never 0)
+    const int kvh = (int) (((uint64_t) (uint32_t) h0 * kv_magic) >> 24);   // the K/V head of this tile
     const int t0 = c * G::TCHUNK;
 
     constexpr bool INT8KV = KV == KV_I8, FP8KV = KV == KV_F8;
     constexpr int ESZ = KV == KV_F16 ? 2 : 1;
-    char* kbase = reinterpret_cast<char*>(p.kv_cache) + ((int64_t) (b * 2 + 0) * H + h) * Smax * DH * ESZ;
-    char* vbase = reinterpret_cast<char*>(p.kv_cache) + ((int64_t) (b * 2 + 1) * H + h) * Smax * DH * ESZ;
+    char* kbase = reinterpret_cast<char*>(p.kv_cache) + ((int64_t) (b * 2 + 0) * Hkv + kvh) * Smax * DH * ESZ;
+    char* vbase = reinterpret_cast<char*>(p.kv_cache) + ((int64_t) (b * 2 + 1) * Hkv + kvh) * Smax * DH * ESZ;
 
     // ---- 1. request the cache rows: nothing below is needed to form their addresses (rows at or beyond the
     //         current length are loaded too - the buffer has Smax rows - and dropped by the validity mask)
     uint4 kreg[NIT], vreg[NIT];
     constexpr bool BEAM = CACHE == CACHE_BEAM, PAGED = CACHE == CACHE_PAGED;
     // beam search: timestep t of this hypothesis lives in the cache rows of a sibling (cache_indirection); the row
-    // strides between siblings are whole (batch, 2, H, Smax, DH) sequences
+    // strides between siblings are whole (batch, 2, Hkv, Smax, DH) sequences
     int64_t sib[NIT];
     // paged: the block holding time step t, from the sequence's (or the sibling's) row of the block table
     const char* kblk[NIT];
@@ -147,7 +159,7 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     if constexpr (BEAM)
     {
         const int32_t* ci = p.cache_indirection + (int64_t) b * Smax;
-        const int64_t seq_bytes = (int64_t) 2 * H * Smax * DH * ESZ;
+        const int64_t seq_bytes = (int64_t) 2 * Hkv * Smax * DH * ESZ;
         const int k_own = b % p.beam_width;
 #pragma unroll
         for (int i = 0; i < NIT; ++i)
@@ -165,7 +177,7 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
         const char *kp = kbase + off, *vp = vbase + off;
         if constexpr (PAGED)
         {
-            off = (((int64_t) h * p.tokens_per_block + (t & tpb_mask)) * DH + li * 8) * ESZ;
+            off = (((int64_t) kvh * p.tokens_per_block + (t & tpb_mask)) * DH + li * 8) * ESZ;
             kp = kblk[i] + off;
             vp = vblk[i] + off;
         }
@@ -184,10 +196,13 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     }
     // ---- 2. the new token's q, k, v, the step scalars, the padding-mask words and the RoPE row: all requested
     //         here, before anything is consumed (one memory round trip for the whole prologue)
-    const uint16_t* qkv = reinterpret_cast<const uint16_t*>(p.qkv) + (int64_t) b * 3 * H * DH;
-    const uint4 q_raw = *reinterpret_cast<const uint4*>(qkv + (int64_t) h * DH + li * 8);
-    const uint4 k_raw = *reinterpret_cast<const uint4*>(qkv + (int64_t) (H + h) * DH + li * 8);
-    const uint4 v_new = *reinterpret_cast<const uint4*>(qkv + (int64_t) (2 * H + h) * DH + li * 8);
+    const uint16_t* qkv = reinterpret_cast<const uint16_t*>(p.qkv) + (int64_t) b * (H + 2 * Hkv) * DH; // q: H | k: Hkv | v: Hkv
+    uint4 q_raw[QT];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt)
+        q_raw[qt] = *reinterpret_cast<const uint4*>(qkv + (int64_t) (h0 + qt) * DH + li * 8);
+    const uint4 k_raw = *reinterpret_cast<const uint4*>(qkv + (int64_t) (H + kvh) * DH + li * 8);
+    const uint4 v_new = *reinterpret_cast<const uint4*>(qkv + (int64_t) (H + Hkv + kvh) * DH + li * 8);
     const int tl = p.sequence_length[b]; // slots already used; the new token goes to slot tl
     int mk[NIT];
 #pragma unroll
@@ -235,47 +250,49 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     const int nact = min(tl / G::TCHUNK + 1, nsplit_max);
     if (c >= nact)
         return; // uniform: this split lies entirely beyond the sequence
-    float qf[8], kf[8];
-    h8_to_f(q_raw, qf);
-    h8_to_f(k_raw, kf);
-    if (p.rotary_dim > 0)
-    {
-        const float cs[16] = {c4[0].x, c4[0].y, c4[0].z, c4[0].w, c4[1].x, c4[1].y, c4[1].z, c4[1].w,
-            c4[2].x, c4[2].y, c4[2].z, c4[2].w, c4[3].x, c4[3].y, c4[3].z, c4[3].w};
-        if (p.neox)
+    // RoPE of one row (q of a head of the tile, or the new k - once per K/V head), fp32 -> fp16
+    const float cs[16] = {c4[0].x, c4[0].y, c4[0].z, c4[0].w, c4[1].x, c4[1].y, c4[1].z, c4[1].w,
+        c4[2].x, c4[2].y, c4[2].z, c4[2].w, c4[3].x, c4[3].y, c4[3].z, c4[3].w};
+    auto rope_row = [&](const uint4& raw) -> uint4 {
+        float xf[8];
+        h8_to_f(raw, xf);
+        if (p.rotary_dim > 0)
         {
-            // pair (j, j + rot/2); rot == DH: the partner sits in lane li ^ (LPR/2)
-            const bool second = li >= LPR / 2;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
+            if (p.neox)
             {
-                const float qp = __shfl_xor(qf[j], LPR / 2, 64);
-                const float kp = __shfl_xor(kf[j], LPR / 2, 64);
-                // first half:  x' = x cos - y sin ; second half: y' = y cos + x sin
-                // fp16 rounding of the rotated value (...Utils.h:1517-1531)
-                const float c = cs[2 * j], sn = second ? cs[2 * j + 1] : -cs[2 * j + 1];
-                qf[j] = h2f(f2h(c * qf[j] + sn * qp));
-                kf[j] = h2f(f2h(c * kf[j] + sn * kp));
+                // pair (j, j + rot/2); rot == DH: the partner sits in lane li ^ (LPR/2)
+                const bool second = li >= LPR / 2;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                {
+                    const float xp = __shfl_xor(xf[j], LPR / 2, 64);
+                    // first half:  x' = x cos - y sin ; second half: y' = y cos + x sin
+                    // fp16 rounding of the rotated value (...Utils.h:1517-1531)
+                    const float c = cs[2 * j], sn = second ? cs[2 * j + 1] : -cs[2 * j + 1];
+                    xf[j] = h2f(f2h(c * xf[j] + sn * xp));
+                }
+            }
+            else
+            {
+                // GPT-J style: pair (2i, 2i+1), both in this lane
+#pragma unroll
+                for (int j = 0; j < 8; j += 2)
+                {
+                    const float c = (li * 8 + j < p.rotary_dim) ? cs[j] : 1.f;
+                    const float sn = (li * 8 + j < p.rotary_dim) ? cs[j + 1] : 0.f;
+                    const float x0 = xf[j], x1 = xf[j + 1];
+                    xf[j] = h2f(f2h(c * x0 - sn * x1));
+                    xf[j + 1] = h2f(f2h(c * x1 + sn * x0));
+                }
             }
         }
-        else
-        {
-            // GPT-J style: pair (2i, 2i+1), both in this lane
+        return f_to_h8(xf);
+    };
+    uint4 q16s[QT];
 #pragma unroll
-            for (int j = 0; j < 8; j += 2)
-            {
-                const float c = (li * 8 + j < p.rotary_dim) ? cs[j] : 1.f;
-                const float sn = (li * 8 + j < p.rotary_dim) ? cs[j + 1] : 0.f;
-                const float q0 = qf[j], q1 = qf[j + 1], k0 = kf[j], k1 = kf[j + 1];
-                qf[j] = h2f(f2h(c * q0 - sn * q1));
-                qf[j + 1] = h2f(f2h(c * q1 + sn * q0));
-                kf[j] = h2f(f2h(c * k0 - sn * k1));
-                kf[j + 1] = h2f(f2h(c * k1 + sn * k0));
-            }
-        }
-    }
-    const uint4 q16 = f_to_h8(qf);
-    const uint4 k_new = f_to_h8(kf);
+    for (int qt = 0; qt < QT; ++qt)
+        q16s[qt] = rope_row(q_raw[qt]);
+    const uint4 k_new = rope_row(k_raw);
 
     float s_oq = 1.f, s_qo = 1.f;
     if constexpr (INT8KV || FP8KV)
@@ -284,8 +301,9 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
         s_qo = p.kv_scale_quant_orig[0];
     }
 
-    // ---- 3. the workgroup that owns slot tl appends the new token to the cache
-    if (tl / G::TCHUNK == c && gid == 0 && tl < Smax)
+    // ---- 3. the workgroup that owns slot tl appends the new token to the cache: exactly one per (K/V head, sequence) - of the
+    //         tiles that share the K/V head, the first
+    if (tl / G::TCHUNK == c && gid == 0 && tl < Smax && h0 == kvh * group)
     {
         int64_t off = ((int64_t) tl * DH + li * 8) * ESZ;
         char *kw = kbase + off, *vw = vbase + off;
@@ -295,7 +313,7 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
             // the sequence's OWN block (never a sibling's: a new token belongs to the hypothesis that consumed it)
             const int lg = 31 - __builtin_clz(p.tokens_per_block);
             const int64_t* row = p.block_pointers + (int64_t) b * 2 * p.max_blocks_per_seq + (tl >> lg);
-            off = (((int64_t) h * p.tokens_per_block + (tl & tpb_mask)) * DH + li * 8) * ESZ;
+            off = (((int64_t) kvh * p.tokens_per_block + (tl & tpb_mask)) * DH + li * 8) * ESZ;
             // the manager must have mapped the block of slot tl before this step (KVCacheManager.step); a missing block is
             // the caller's error and must not become a wild store
             mapped = row[0] != 0 && row[p.max_blocks_per_seq] != 0;
@@ -329,160 +347,171 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     // without that rounding; well inside the 2e-3 tolerance of the reference's own plugin test).
     // fp8 cache: the bytes decode to fp16 exactly (every E4M3 value is an fp16 value), the fp16 dot products run on them as they
     // are, and the scale is applied once in the same two places.
-    float dnew = 0.f;
-    dnew = dot2(q16.x, k_new.x, dnew);
-    dnew = dot2(q16.y, k_new.y, dnew);
-    dnew = dot2(q16.z, k_new.z, dnew);
-    dnew = dot2(q16.w, k_new.w, dnew);
-    dnew = group_sum<LPR>(dnew) * p.inv_sqrt_dh;
     const float kscale = (INT8KV || FP8KV) ? s_qo * p.inv_sqrt_dh : p.inv_sqrt_dh;
-    float s[NIT];
-    float m_g = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i)
-    {
-        const int t = t0 + i * NGRP + gid;
-        float d = 0.f;
-        if constexpr (INT8KV)
-        {
-            const uint32_t magic = 0x64646464u;
-            const h2_t bias = {(_Float16) 1152.f, (_Float16) 1152.f};
-            const uint32_t ka = kreg[i].x ^ 0x80808080u, kb = kreg[i].y ^ 0x80808080u;
-            d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, ka, 0x04010400u)) - bias, u32_as_h2(q16.x), d, false);
-            d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, ka, 0x04030402u)) - bias, u32_as_h2(q16.y), d, false);
-            d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, kb, 0x04010400u)) - bias, u32_as_h2(q16.z), d, false);
-            d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, kb, 0x04030402u)) - bias, u32_as_h2(q16.w), d, false);
-        }
-        else if constexpr (FP8KV)
-        {
-            const uint4 k16 = dequant8_fp8(make_uint2(kreg[i].x, kreg[i].y));
-            d = dot2(q16.x, k16.x, d);
-            d = dot2(q16.y, k16.y, d);
-            d = dot2(q16.z, k16.z, d);
-            d = dot2(q16.w, k16.w, d);
-        }
-        else
-        {
-            d = dot2(q16.x, kreg[i].x, d);
-            d = dot2(q16.y, kreg[i].y, d);
-            d = dot2(q16.z, kreg[i].z, d);
-            d = dot2(q16.w, kreg[i].w, d);
-        }
-        d = group_sum<LPR>(d) * kscale;
-        if (t == tl)
-            d = dnew; // the current token uses the un-quantised k (MM/...Template.h:1517-1549)
-        const bool valid = t <= tl && t < Smax && (t == tl || mk[i] == 0);
-        s[i] = valid ? d : -INFINITY;
-        m_g = fmaxf(m_g, s[i]);
-    }
-    float l_g = 0.f, l16 = 0.f;
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float p_new = 0.f;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i)
-    {
-        const int t = t0 + i * NGRP + gid;
-        const float pr = (s[i] == -INFINITY) ? 0.f : __expf(s[i] - m_g);
-        l_g += pr;
-        const float p16 = h2f(f2h(pr));
-        if (t == tl)
-        {
-            p_new = p16;
-            continue;
-        }
-        if constexpr (INT8KV)
-        {
-            const uint32_t va = vreg[i].x ^ 0x80808080u, vb = vreg[i].y ^ 0x80808080u;
-            l16 += p16;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-            {
-                o[j] = fmaf(p16, (float) ((va >> (8 * j)) & 0xffu), o[j]);
-                o[4 + j] = fmaf(p16, (float) ((vb >> (8 * j)) & 0xffu), o[4 + j]);
-            }
-        }
-        else
-        {
-            float vf[8];
-            if constexpr (FP8KV)
-                h8_to_f(dequant8_fp8(make_uint2(vreg[i].x, vreg[i].y)), vf);
-            else
-                h8_to_f(vreg[i], vf);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                o[j] = fmaf(p16, vf[j], o[j]);
-        }
-    }
-    {
-        float vf[8];
-        h8_to_f(v_new, vf);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-        {
-            if constexpr (INT8KV)
-                o[j] = s_qo * (o[j] - 128.f * l16); // sum p (u - 128) = sum p u - 128 sum p
-            if constexpr (FP8KV)
-                o[j] = s_qo * o[j];
-            o[j] = fmaf(p_new, vf[j], o[j]);
-        }
-    }
-
-    // ---- 5. merge the lane groups of the workgroup through LDS, publish the split partial
+    const bool tail = p.tail_tickets != nullptr; // uniform
     __shared__ float sm_m[NGRP], sm_l[NGRP], sm_w[NGRP];
     __shared__ __attribute__((aligned(16))) float sm_o[NGRP][DH];
-    *reinterpret_cast<float4*>(&sm_o[gid][li * 8]) = make_float4(o[0], o[1], o[2], o[3]);
-    *reinterpret_cast<float4*>(&sm_o[gid][li * 8 + 4]) = make_float4(o[4], o[5], o[6], o[7]);
-    if (li == 0)
-    {
-        sm_m[gid] = m_g;
-        sm_l[gid] = l_g;
-    }
-    __syncthreads();
-    float M = -INFINITY;
-    for (int g = 0; g < NGRP; ++g)
-        M = fmaxf(M, sm_m[g]);
-    if (tid < NGRP)
-        sm_w[tid] = (sm_m[tid] == -INFINITY) ? 0.f : __expf(sm_m[tid] - M);
-    __syncthreads();
-    const int64_t pi = ((int64_t) b * H + h) * nsplit_max + c;
-    const bool tail = p.tail_tickets != nullptr; // uniform
     __shared__ __attribute__((aligned(16))) float sm_out[DH];
-    for (int d = tid; d < DH; d += 256)
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) // the heads of the tile, one after the other, on the rows loaded in step 1
     {
-        float L = 0.f, O = 0.f;
-        for (int g = 0; g < NGRP; ++g)
+        const int h = h0 + qt;
+        const uint4 q16 = q16s[qt];
+        float dnew = 0.f;
+        dnew = dot2(q16.x, k_new.x, dnew);
+        dnew = dot2(q16.y, k_new.y, dnew);
+        dnew = dot2(q16.z, k_new.z, dnew);
+        dnew = dot2(q16.w, k_new.w, dnew);
+        dnew = group_sum<LPR>(dnew) * p.inv_sqrt_dh;
+        float s[NIT];
+        float m_g = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < NIT; ++i)
         {
-            L += sm_l[g] * sm_w[g];
-            O += sm_o[g][d] * sm_w[g];
+            const int t = t0 + i * NGRP + gid;
+            float d = 0.f;
+            if constexpr (INT8KV)
+            {
+                const uint32_t magic = 0x64646464u;
+                const h2_t bias = {(_Float16) 1152.f, (_Float16) 1152.f};
+                const uint32_t ka = kreg[i].x ^ 0x80808080u, kb = kreg[i].y ^ 0x80808080u;
+                d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, ka, 0x04010400u)) - bias, u32_as_h2(q16.x), d, false);
+                d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, ka, 0x04030402u)) - bias, u32_as_h2(q16.y), d, false);
+                d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, kb, 0x04010400u)) - bias, u32_as_h2(q16.z), d, false);
+                d = __builtin_amdgcn_fdot2(u32_as_h2(__builtin_amdgcn_perm(magic, kb, 0x04030402u)) - bias, u32_as_h2(q16.w), d, false);
+            }
+            else if constexpr (FP8KV)
+            {
+                const uint4 k16 = dequant8_fp8(make_uint2(kreg[i].x, kreg[i].y));
+                d = dot2(q16.x, k16.x, d);
+                d = dot2(q16.y, k16.y, d);
+                d = dot2(q16.z, k16.z, d);
+                d = dot2(q16.w, k16.w, d);
+            }
+            else
+            {
+                d = dot2(q16.x, kreg[i].x, d);
+                d = dot2(q16.y, kreg[i].y, d);
+                d = dot2(q16.z, kreg[i].z, d);
+                d = dot2(q16.w, kreg[i].w, d);
+            }
+            d = group_sum<LPR>(d) * kscale;
+            if (t == tl)
+                d = dnew; // the current token uses the un-quantised k (MM/...Template.h:1517-1549)
+            const bool valid = t <= tl && t < Smax && (t == tl || mk[i] == 0);
+            s[i] = valid ? d : -INFINITY;
+            m_g = fmaxf(m_g, s[i]);
         }
+        float l_g = 0.f, l16 = 0.f;
+        float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float p_new = 0.f;
+#pragma unroll
+        for (int i = 0; i < NIT; ++i)
+        {
+            const int t = t0 + i * NGRP + gid;
+            const float pr = (s[i] == -INFINITY) ? 0.f : __expf(s[i] - m_g);
+            l_g += pr;
+            const float p16 = h2f(f2h(pr));
+            if (t == tl)
+            {
+                p_new = p16;
+                continue;
+            }
+            if constexpr (INT8KV)
+            {
+                const uint32_t va = vreg[i].x ^ 0x80808080u, vb = vreg[i].y ^ 0x80808080u;
+                l16 += p16;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                {
+                    o[j] = fmaf(p16, (float) ((va >> (8 * j)) & 0xffu), o[j]);
+                    o[4 + j] = fmaf(p16, (float) ((vb >> (8 * j)) & 0xffu), o[4 + j]);
+                }
+            }
+            else
+            {
+                float vf[8];
+                if constexpr (FP8KV)
+                    h8_to_f(dequant8_fp8(make_uint2(vreg[i].x, vreg[i].y)), vf);
+                else
+                    h8_to_f(vreg[i], vf);
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    o[j] = fmaf(p16, vf[j], o[j]);
+            }
+        }
+        {
+            float vf[8];
+            h8_to_f(v_new, vf);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+            {
+                if constexpr (INT8KV)
+                    o[j] = s_qo * (o[j] - 128.f * l16); // sum p (u - 128) = sum p u - 128 sum p
+                if constexpr (FP8KV)
+                    o[j] = s_qo * o[j];
+                o[j] = fmaf(p_new, vf[j], o[j]);
+            }
+        }
+
+        // ---- 5. merge the lane groups of the workgroup through LDS, publish the split partial
+        *reinterpret_cast<float4*>(&sm_o[gid][li * 8]) = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4*>(&sm_o[gid][li * 8 + 4]) = make_float4(o[4], o[5], o[6], o[7]);
+        if (li == 0)
+        {
+            sm_m[gid] = m_g;
+            sm_l[gid] = l_g;
+        }
+        __syncthreads();
+        float M = -INFINITY;
+        for (int g = 0; g < NGRP; ++g)
+            M = fmaxf(M, sm_m[g]);
+        if (tid < NGRP)
+            sm_w[tid] = (sm_m[tid] == -INFINITY) ? 0.f : __expf(sm_m[tid] - M);
+        __syncthreads();
+        const int64_t pi = ((int64_t) b * H + h) * nsplit_max + c;
+        for (int d = tid; d < DH; d += 256)
+        {
+            float L = 0.f, O = 0.f;
+            for (int g = 0; g < NGRP; ++g)
+            {
+                L += sm_l[g] * sm_w[g];
+                O += sm_o[g][d] * sm_w[g];
+            }
+            if (tail)
+            {
+                sm_out[d] = O;
+                if (d == 0) // (m, l) as ONE 8-byte write-through store
+                    __hip_atomic_store(reinterpret_cast<uint64_t*>(ws_ml + pi),
+                        (uint64_t) __float_as_uint(M) | ((uint64_t) __float_as_uint(L) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            else
+            {
+                ws_o[pi * DH + d] = O;
+                if (d == 0)
+                    ws_ml[pi] = make_float2(M, L);
+            }
+        }
+        // write-through (sc1) 16-byte stores of the partial: the merging workgroup may sit on another XCD, whose L2 never sees this
+        // one's; scalar write-through stores are one fabric write each (guide: dword ~6 x the dwordx4 time per byte)
         if (tail)
         {
-            sm_out[d] = O;
-            if (d == 0) // (m, l) as ONE 8-byte write-through store
-                __hip_atomic_store(reinterpret_cast<uint64_t*>(ws_ml + pi),
-                    (uint64_t) __float_as_uint(M) | ((uint64_t) __float_as_uint(L) << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            if (tid < DH / 4)
+            {
+                typedef float f32x4_t __attribute__((ext_vector_type(4)));
+                const f32x4_t v = *reinterpret_cast<const f32x4_t*>(&sm_out[tid * 4]);
+                float* dst = ws_o + pi * DH + tid * 4;
+                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
+            }
         }
-        else
-        {
-            ws_o[pi * DH + d] = O;
-            if (d == 0)
-                ws_ml[pi] = make_float2(M, L);
-        }
-    }
+        if constexpr (QT > 1)
+            __syncthreads(); // the next head of the tile reuses sm_m / sm_l / sm_w / sm_o
+    } // qt
     if (!tail)
         return;
-    // write-through (sc1) 16-byte stores of the partial: the merging workgroup may sit on another XCD, whose L2 never sees this
-    // one's; scalar write-through stores are one fabric write each (guide: dword ~6 x the dwordx4 time per byte)
-    __syncthreads();
-    if (tid < DH / 4)
-    {
-        typedef float f32x4_t __attribute__((ext_vector_type(4)));
-        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(&sm_out[tid * 4]);
-        float* dst = ws_o + pi * DH + tid * 4;
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
-    }
-    // ---- 6. (tail merge) the partial is written through -> one ticket per workgroup -> the last arriver of the (sequence, head)
-    //         merges.  Protocol = the guide's R1 form (cdna_hip_programming.md G16: "sc1 payload -> asm vmcnt(0) -> relaxed agent flag;
+    // ---- 6. (tail merge) the partials are written through -> one ticket per workgroup -> the last arriver of the (sequence, tile)
+    //         merges the QT heads of the tile (the ticket word is that of the tile's first head).  Protocol = the guide's R1 form (cdna_hip_programming.md G16: "sc1 payload -> asm vmcnt(0) -> relaxed agent flag;
     //         sc1 loads may replace the acquire when the producer stored sc1"): write-through payload, drained by every storing wave
     //         (vmcnt(0) in asm: the compiler may drop its own wait), workgroup barrier, relaxed agent-scope ticket; the consumer reads
     //         the payload with agent-scope (L1-bypassing) loads behind the ticket it took.  The ticket word re-arms itself for the
@@ -491,15 +520,16 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     __syncthreads();
     __shared__ uint32_t sm_ticket;
     if (tid == 0)
-        sm_ticket = __hip_atomic_fetch_add(p.tail_tickets + b * H + h, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sm_ticket = __hip_atomic_fetch_add(p.tail_tickets + b * H + h0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if ((int) sm_ticket != nact - 1)
         return;
     if (tid == 0) // re-arm for the next launch (ordered by the kernel boundary)
-        __hip_atomic_store(p.tail_tickets + b * H + h, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int64_t base = ((int64_t) b * H + h) * nsplit_max;
-    for (int d = tid; d < DH; d += 256)
+        __hip_atomic_store(p.tail_tickets + b * H + h0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int e = tid; e < QT * DH; e += 256)
     {
+        const int h = h0 + e / DH, d = e % DH;
+        const int64_t base = ((int64_t) b * H + h) * nsplit_max;
         // the arithmetic of the O-projection's merge prologue (gemv_impl.h PK_ATTN), slot order, fp32: bit-identical results.
         // Up to kTailSlots partials (the prologue form stops at 8: there every slot costs each of ~500 workgroups a load)
         float ms[kTailSlots], ls[kTailSlots], os[kTailSlots];
@@ -590,8 +620,8 @@ __global__ __launch_bounds__(256) void mmha_combine_kernel(const MmhaParams p, c
     }
 }
 
-template <int DH, int NIT>
-int launch_nit(const MmhaParams& p, hipStream_t stream)
+template <int DH, int NIT, int QT>
+int launch_qt(const MmhaParams& p, hipStream_t stream)
 {
     using G = MmhaGeom<DH, NIT>;
     const int ns = (p.max_seq_len + G::TCHUNK - 1) / G::TCHUNK;
@@ -609,11 +639,13 @@ int launch_nit(const MmhaParams& p, hipStream_t stream)
     float2* ws_ml = reinterpret_cast<float2*>(ws);
     const size_t ml_bytes = ((size_t) p.batch * p.num_heads * ns * sizeof(float2) + 255) / 256 * 256;
     float* ws_o = reinterpret_cast<float*>(ws + ml_bytes);
-    dim3 grid(ns, p.num_heads, p.batch);
+    dim3 grid(ns, p.num_heads / QT, p.batch);
+    const int group = p.num_heads / p.num_kv_heads;
+    const uint32_t kv_magic = (uint32_t) (((1u << 24) + group - 1) / group);
     const bool beam = p.beam_width > 1 && p.cache_indirection;
     const int mode = p.block_pointers ? CACHE_PAGED : (beam ? CACHE_BEAM : CACHE_LINEAR);
 #define TLLM_MMHA_LAUNCH(ELEM, MODE)                                                                                   \
-    hipLaunchKernelGGL((mmha_partial_kernel<DH, NIT, ELEM, MODE>), grid, dim3(256), 0, stream, p, ws_ml, ws_o, ns)
+    hipLaunchKernelGGL((mmha_partial_kernel<DH, NIT, ELEM, MODE, QT>), grid, dim3(256), 0, stream, p, ws_ml, ws_o, ns, kv_magic, group)
     if (p.int8_kv)
     {
         if (mode == CACHE_PAGED)
@@ -645,6 +677,18 @@ int launch_nit(const MmhaParams& p, hipStream_t stream)
     if (!p.tail_tickets)
         hipLaunchKernelGGL((mmha_combine_kernel<DH, NIT>), dim3(p.num_heads, p.batch), dim3(256), 0, stream, p, ws_ml, ws_o, ns);
     return launch_util::check_launch("mmha");
+}
+
+template <int DH, int NIT>
+int launch_nit(const MmhaParams& p, hipStream_t stream)
+{
+    switch (p.q_heads_per_workgroup) // resolved and checked by launch_mmha
+    {
+    case 1: return launch_qt<DH, NIT, 1>(p, stream);
+    case 2: return launch_qt<DH, NIT, 2>(p, stream);
+    case 4: return launch_qt<DH, NIT, 4>(p, stream);
+    default: return launch_qt<DH, NIT, 8>(p, stream);
+    }
 }
 
 template <int DH>
@@ -717,8 +761,54 @@ void fill_rope_table_host(float* table, int32_t max_pos, int32_t rotary_dim)
         }
 }
 
-int launch_mmha(const MmhaParams& p, hipStream_t stream)
+// The default query tile.  profiles/gqa_attention.txt (MI355X, batch 1, G 4 / 8 / 32, contexts 128 / 1024 / 4000): tile 2 beats
+// tile 1 beyond the run-to-run spread only at context 4000 (x1.03 - x1.40) and loses at 128 and 1024 (x0.77 - x1.00); tiles 4 and
+// 8 lose nearly everywhere.  The context length is not known to the launcher, so tile 1 is the default for every G; every tile
+// stays reachable through MmhaParams::q_heads_per_workgroup.  A rule on max_seq_len (tile 2 for caches of 4096 slots and more,
+// x1.32 - x1.40 at G 8 and 4000 tokens) was considered and rejected: the capacity is not the length - a session sized for 4096
+// slots spends most of its steps at the short contexts where tile 2 loses up to 23 %.  The arguments stay for a rule per G once a
+// tile that scores its heads side by side is measured.
+int mmha_default_q_tile(int32_t num_heads, int32_t num_kv_heads)
 {
+    (void) num_heads;
+    (void) num_kv_heads;
+    return 1;
+}
+
+// The one place the grouping is resolved and checked (launch_mmha and the session-free entry points): num_kv_heads 0 -> num_heads,
+// q_heads_per_workgroup 0 -> the default tile.
+int mmha_resolve_grouping(MmhaParams& p)
+{
+    if (p.num_kv_heads == 0)
+        p.num_kv_heads = p.num_heads;
+    if (p.num_heads < 1 || p.num_kv_heads < 1 || p.num_kv_heads > p.num_heads || p.num_heads % p.num_kv_heads)
+    {
+        set_error("mmha: num_kv_heads %d must divide num_heads %d", p.num_kv_heads, p.num_heads);
+        return -1;
+    }
+    const int group = p.num_heads / p.num_kv_heads;
+    if ((int64_t) p.num_heads * group >= (1 << 24))
+    {
+        set_error("mmha: num_heads %d x %d query heads per K/V head is beyond the head map's range (2^24)", p.num_heads, group);
+        return -1;
+    }
+    int& qt = p.q_heads_per_workgroup;
+    if (qt == 0)
+        qt = mmha_default_q_tile(p.num_heads, p.num_kv_heads);
+    if ((qt != 1 && qt != 2 && qt != 4 && qt != 8) || group % qt)
+    {
+        set_error("mmha: q_heads_per_workgroup %d is not 1, 2, 4 or 8 or does not divide the %d query heads of a K/V head (num_heads %d, "
+                  "num_kv_heads %d)", qt, group, p.num_heads, p.num_kv_heads);
+        return -1;
+    }
+    return 0;
+}
+
+int launch_mmha(const MmhaParams& pin, hipStream_t stream)
+{
+    MmhaParams p = pin;
+    if (mmha_resolve_grouping(p))
+        return -1;
     if (p.rotary_dim > 0)
     {
         if (!p.rope_table || p.rope_table_len <= 0)

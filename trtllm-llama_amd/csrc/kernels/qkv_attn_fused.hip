@@ -1174,8 +1174,11 @@ size_t qkv_attn_fused_xchg_bytes(int32_t num_heads)
 
 // the O-projection stage: K = H * Dh = 4 KiB rows (the context row is swept by 512 threads x two granules), every row worker's
 // share of the rows fits its LDS area
-bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t weight_kind)
+bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t weight_kind,
+    int32_t num_kv_heads)
 {
+    if (num_kv_heads != 0 && num_kv_heads != num_heads)
+        return false; // grouped K/V heads: the front is built for one K/V head per query head
     const int workers = (kMembers - 1) * num_heads;
     const int64_t row_bytes = weight_kind == WK_WOQ4 ? o_k / 2 : o_k; // (int8 kinds; fp16 has no such stage)
     return head_size == kDH && o_k == num_heads * head_size && o_k == kKChunks * 1024 && num_heads * kCtxGranules == 1024
@@ -1183,8 +1186,10 @@ bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, 
 }
 
 bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int32_t max_seq_len, int32_t int8_kv, int32_t weight_kind,
-    int32_t o_stage)
+    int32_t o_stage, int32_t num_kv_heads)
 {
+    if (num_kv_heads != 0 && num_kv_heads != num_heads)
+        return false; // grouped K/V heads: the q | k | v row and the cache of the front are those of one K/V head per query head
     const int nit = pick_nit(max_seq_len, int8_kv != 0);
     // (K = 4096 elements: rows of 4 KiB int8 / 8 KiB fp16 = one / two tiles of 4 x 1 KiB chunks x 2 rows)
     if (K != kKChunks * 1024 || head_size != kDH || nit == 0 || weight_kind < WK_SQ || weight_kind > WK_WOQ4)

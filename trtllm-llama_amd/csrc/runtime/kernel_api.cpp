@@ -5,6 +5,7 @@
 #include "../plugins/plugin_base.h"
 #include "sampling_config.h"
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -50,7 +51,196 @@ static GemmParams gemm_params(const tllm_gemm_params_t* q)
     return g;
 }
 
+// tllm_attention_params_t -> the decode launcher's struct, with the launch shape the GPTAttention plugin picks where the caller
+// left it open (rows_per_group 16 / 12 and the in-launch merge while the cache fits 16 splits, else the finest split and the
+// combine launch).  in_launch: the splits are merged inside the launch (tickets at the head of the workspace).
+static int attention_decode_params(const tllm_attention_params_t* q, MmhaParams& p, bool& in_launch)
+{
+    if (!q || q->batch < 1 || q->num_heads < 1 || q->head_size < 1 || q->max_seq_len < 1)
+    {
+        set_error("tllm_attention_decode: bad arguments (batch, num_heads, head_size, max_seq_len)");
+        return 1;
+    }
+    p.num_heads = q->num_heads;
+    p.num_kv_heads = q->num_kv_heads;
+    p.q_heads_per_workgroup = q->q_heads_per_workgroup;
+    if (mmha_resolve_grouping(p)) // the launcher's own check: one statement of the rule
+        return 1;
+    if (q->rows_per_group != 0 && q->rows_per_group != 4 && q->rows_per_group != 12 && q->rows_per_group != 16)
+    {
+        set_error("tllm_attention_decode: rows_per_group %d is not 4, 12 or 16", q->rows_per_group);
+        return 1;
+    }
+    if (q->kv_cache_type != 0 && q->kv_cache_type != TLLM_HALF && q->kv_cache_type != TLLM_INT8 && q->kv_cache_type != TLLM_FP8)
+    {
+        set_error("tllm_attention_decode: kv_cache_type %d is not TLLM_HALF, TLLM_INT8 or TLLM_FP8", q->kv_cache_type);
+        return 1;
+    }
+    p.batch = q->batch;
+    p.head_size = q->head_size;
+    p.rotary_dim = q->rotary_dim;
+    p.neox = q->neox;
+    p.inv_sqrt_dh = 1.f / (sqrtf((float) q->head_size) * (q->q_scaling != 0.f ? q->q_scaling : 1.f));
+    p.int8_kv = q->kv_cache_type == TLLM_INT8;
+    p.fp8_kv = q->kv_cache_type == TLLM_FP8;
+    p.max_seq_len = q->max_seq_len;
+    p.max_input_len = q->max_input_len;
+    p.qkv = q->qkv;
+    p.kv_cache = q->kv_cache;
+    p.sequence_length = q->sequence_length;
+    p.input_lengths = q->input_lengths;
+    p.masked_tokens = q->masked_tokens;
+    p.timestep_host = q->timestep;
+    p.kv_scale_orig_quant = q->kv_scale_orig_quant;
+    p.kv_scale_quant_orig = q->kv_scale_quant_orig;
+    if (q->beam_width > 1)
+    {
+        p.cache_indirection = q->cache_indirection;
+        p.beam_width = q->beam_width;
+    }
+    p.block_pointers = q->block_pointers;
+    p.tokens_per_block = q->tokens_per_block;
+    p.max_blocks_per_seq = q->max_blocks_per_seq;
+    p.tail_quant_scale = q->tail_quant_scale;
+    p.tail_out_q8 = q->tail_out_q8;
+    p.out = q->out;
+    // the plugin's rule (plugins.cpp, GPTAttention enqueue)
+    int tc = 0, ns = 0;
+    in_launch = false;
+    p.rows_per_group = q->rows_per_group;
+    if (q->rows_per_group == 0)
+    {
+        if (mmha_split_layout(q->head_size, q->max_seq_len, 16, q->batch, q->num_heads, &tc, &ns, nullptr) == 0 && ns <= 16)
+        {
+            p.rows_per_group = 16;
+            if (mmha_split_layout(q->head_size, q->max_seq_len, 12, q->batch, q->num_heads, &tc, &ns, nullptr) == 0 && ns <= 8)
+                p.rows_per_group = 12;
+            in_launch = true;
+        }
+    }
+    else if (mmha_split_layout(q->head_size, q->max_seq_len, q->rows_per_group, q->batch, q->num_heads, &tc, &ns, nullptr) == 0)
+        in_launch = ns <= 16;
+    if (q->combine_launch)
+        in_launch = false;
+    return 0;
+}
+
 extern "C" {
+
+size_t tllm_attention_workspace_size(const tllm_attention_params_t* q, int32_t is_context)
+{
+    if (!q)
+        return 0;
+    if (is_context)
+        return context_attention_workspace_size(q->batch, q->num_heads, q->head_size, q->seq) + 256;
+    return mmha_workspace_size(q->batch, q->num_heads, q->head_size, q->max_seq_len) + 256;
+}
+
+int32_t tllm_attention_decode_layout(const tllm_attention_params_t* q, int32_t* tchunk, int32_t* nsplit, int32_t* q_tile,
+    int32_t* in_launch_merge)
+{
+    MmhaParams p;
+    bool in_launch = false;
+    if (attention_decode_params(q, p, in_launch))
+        return 1;
+    int tc = 0, ns = 0;
+    if (mmha_split_layout(p.head_size, p.max_seq_len, p.rows_per_group, p.batch, p.num_heads, &tc, &ns, nullptr))
+    {
+        set_error("tllm_attention_decode: head_size %d not supported", p.head_size);
+        return 1;
+    }
+    if (tchunk)
+        *tchunk = tc;
+    if (nsplit)
+        *nsplit = ns;
+    if (q_tile)
+        *q_tile = p.q_heads_per_workgroup;
+    if (in_launch_merge)
+        *in_launch_merge = in_launch ? 1 : 0;
+    return 0;
+}
+
+int32_t tllm_attention_decode(const tllm_attention_params_t* q, tllm_stream_t stream)
+{
+    MmhaParams p;
+    bool in_launch = false;
+    if (attention_decode_params(q, p, in_launch))
+        return 1;
+    // paged: kv_cache is the pool itself - the rows of a block the table does not map yet are still loaded (and masked), from there
+    if (!q->qkv || !q->out || !q->workspace || !q->sequence_length || !q->input_lengths || !q->kv_cache)
+    {
+        set_error("tllm_attention_decode: qkv, out, workspace, sequence_length, input_lengths and kv_cache (paged: the pool) must be set");
+        return 1;
+    }
+    if (q->beam_width > 1 && !q->cache_indirection)
+    {
+        set_error("tllm_attention_decode: beam width %d without a cache indirection", q->beam_width);
+        return 1;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (p.rotary_dim > 0)
+    {
+        p.rope_table = tllm::plugins::rope_table(p.rotary_dim, p.max_seq_len, &p.rope_table_len);
+        if (!p.rope_table)
+            return 1;
+    }
+    // workspace: the merge tickets (zeroed per call, as the plugin does), then the partials
+    if (in_launch)
+    {
+        if (mmha_reset_workspace(q->workspace, p.batch, p.num_heads, st))
+            return 1;
+        p.tail_tickets = static_cast<uint32_t*>(q->workspace);
+    }
+    p.workspace = static_cast<char*>(q->workspace) + mmha_ticket_bytes(p.batch, p.num_heads);
+    return launch_mmha(p, st) ? 1 : 0;
+}
+
+int32_t tllm_attention_context(const tllm_attention_params_t* q, tllm_stream_t stream)
+{
+    if (!q || q->batch < 1 || q->seq < 1 || q->num_heads < 1 || !q->qkv || !q->out || !q->input_lengths
+        || (!q->kv_cache && !q->block_pointers))
+    {
+        set_error("tllm_attention_context: bad arguments (batch, seq, num_heads, qkv, out, input_lengths and the cache must be set)");
+        return 1;
+    }
+    if (q->kv_cache_type != 0 && q->kv_cache_type != TLLM_HALF && q->kv_cache_type != TLLM_INT8 && q->kv_cache_type != TLLM_FP8)
+    {
+        set_error("tllm_attention_context: kv_cache_type %d is not TLLM_HALF, TLLM_INT8 or TLLM_FP8", q->kv_cache_type);
+        return 1;
+    }
+    ContextAttnParams p;
+    p.batch = q->batch;
+    p.seq = q->seq;
+    p.num_heads = q->num_heads;
+    p.num_kv_heads = q->num_kv_heads;
+    p.head_size = q->head_size;
+    p.rotary_dim = q->rotary_dim;
+    p.neox = q->neox;
+    p.inv_sqrt_dh = 1.f / (sqrtf((float) q->head_size) * (q->q_scaling != 0.f ? q->q_scaling : 1.f));
+    p.int8_kv = q->kv_cache_type == TLLM_INT8;
+    p.fp8_kv = q->kv_cache_type == TLLM_FP8;
+    p.max_seq_len = q->max_seq_len;
+    p.qkv = q->qkv;
+    p.kv_cache = q->kv_cache;
+    p.input_lengths = q->input_lengths;
+    p.kv_scale_orig_quant = q->kv_scale_orig_quant;
+    if (p.rotary_dim > 0)
+    {
+        p.rope_table = tllm::plugins::rope_table(p.rotary_dim, p.max_seq_len, &p.rope_table_len);
+        if (!p.rope_table)
+            return 1;
+    }
+    p.out = q->out;
+    p.out_q8 = q->out_q8;
+    p.out_q_scale = q->out_q_scale;
+    p.workspace = q->workspace;
+    p.cu_seqlens = q->cu_seqlens;
+    p.cache_seq_stride = q->cache_seq_stride > 0 ? q->cache_seq_stride : 1;
+    p.block_pointers = q->block_pointers;
+    p.tokens_per_block = q->tokens_per_block;
+    p.max_blocks_per_seq = q->max_blocks_per_seq;
+    return launch_context_attention(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
 
 int32_t tllm_gemv(const tllm_gemv_params_t* q, tllm_stream_t stream)
 {

@@ -553,7 +553,7 @@ int64_t tllm_session_step_bytes(tllm_session_t s, int32_t context_len)
         return b;
     };
     int64_t bytes = lin(s->head);
-    const int64_t kv_row = (int64_t) 2 * s->Hr * s->Dh * (int64_t) s->kv_esz();
+    const int64_t kv_row = (int64_t) 2 * s->Hkvr * s->Dh * (int64_t) s->kv_esz();
     for (auto& L : s->layers)
         bytes += lin(L.qkv) + lin(L.dense) + lin(L.fc) + lin(L.gate) + lin(L.proj) + kv_row * s->B * (context_len + 1);
     return bytes;

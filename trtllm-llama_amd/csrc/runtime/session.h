@@ -116,6 +116,9 @@ struct tllm_session
     std::string network_json; // the traced network an engine file carries (Builder.build_engine), verified by load_engine
     // derived
     int Hr = 0, Dh = 0, Dr = 0, Ir = 0, Vr = 0;
+    // grouped-query attention (config key num_kv_heads, default num_heads): K/V heads of the model and of this rank (Hkv / tp), and
+    // the extent of a fused QKV row of this rank, (Hr + 2 * Hkvr) * Dh
+    int num_kv_heads = 0, Hkvr = 0, QKVr = 0;
     bool sq = false, woq = false, int8_kv = false, per_token = false, per_channel = false;
     bool fp8_kv = false; // OCP E4M3 cache (quant_mode bit 64): one-byte elements and the two scales of int8_kv, never both
     size_t kv_esz() const { return (int8_kv || fp8_kv) ? 1 : 2; }

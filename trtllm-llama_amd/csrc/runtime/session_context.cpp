@@ -104,6 +104,7 @@ int tllm_session::context_attention(const Layer& L, bool q_in_attn, hipStream_t 
     c.batch = Bc;
     c.seq = max_in;
     c.num_heads = Hr;
+    c.num_kv_heads = Hkvr;
     c.head_size = Dh;
     c.rotary_dim = Dh;
     c.neox = neox;

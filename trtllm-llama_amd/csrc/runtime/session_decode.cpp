@@ -367,10 +367,10 @@ int tllm_session::stage_qkv(const DecodeStep& ds, int li)
         // the previous layer's seam left input_layernorm's output (quantised for SmoothQuant) in ar_norm
         if (ds.taps)
             RUN(tap_copy(ds, 0, li, ar_norm, sq ? 1 : 2));
-        return gemv(L.qkv, B, PRO_NONE, EPI_NONE, ar_norm, hidden, nullptr, nullptr, nullptr, nullptr, qkv, 3 * Dr, DT_HALF, nullptr,
+        return gemv(L.qkv, B, PRO_NONE, EPI_NONE, ar_norm, hidden, nullptr, nullptr, nullptr, nullptr, qkv, QKVr, DT_HALF, nullptr,
             ds.st, ds.ar_rows);
     }
-    return gemv(L.qkv, B, ds.pro_norm, EPI_NONE, x, hidden, L.ln1, L.ln1_scale, nullptr, nullptr, qkv, 3 * Dr, DT_HALF, nullptr,
+    return gemv(L.qkv, B, ds.pro_norm, EPI_NONE, x, hidden, L.ln1, L.ln1_scale, nullptr, nullptr, qkv, QKVr, DT_HALF, nullptr,
         ds.st, nullptr, ds.taps ? tap_ptr(0, li) : nullptr);
 }
 
@@ -382,6 +382,7 @@ int tllm_session::stage_attention(const DecodeStep& ds, int li)
     MmhaParams m;
     m.batch = B;
     m.num_heads = Hr;
+    m.num_kv_heads = Hkvr;
     m.head_size = Dh;
     m.rotary_dim = Dh;
     m.neox = neox;

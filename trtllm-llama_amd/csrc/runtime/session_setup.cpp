@@ -31,10 +31,10 @@ int tllm_session::alloc_buffers()
     const int S = max_in, D = hidden;
     const size_t M = std::max((size_t) Bc * S, (size_t) B); // prompt rows; the generation phase needs B
     const size_t kv_esz = this->kv_esz();
-    size_t kv_bytes = (size_t) B * 2 * Hr * Smax * Dh * kv_esz;
+    size_t kv_bytes = (size_t) B * 2 * Hkvr * Smax * Dh * kv_esz;
     const int T = tokens_per_block;
     max_blocks = paged_kv ? (Smax + T - 1) / T : 0;
-    const size_t nblocks = (size_t) B * max_blocks, blk_bytes = (size_t) Hr * T * Dh * kv_esz;
+    const size_t nblocks = (size_t) B * max_blocks, blk_bytes = (size_t) Hkvr * T * Dh * kv_esz;
     if (paged_kv)
         kv_bytes = 2 * nblocks * blk_bytes;
     kv_elems = kv_bytes / kv_esz;
@@ -65,7 +65,7 @@ int tllm_session::alloc_buffers()
     }
     RUN(dalloc(&x, M * D * 2));
     RUN(dalloc(&tmp, M * D * 2));
-    RUN(dalloc(&qkv, M * 3 * Dr * 2));
+    RUN(dalloc(&qkv, M * QKVr * 2));
     RUN(dalloc(&ctx, M * Dr * 2));
     RUN(dalloc(&g, M * Ir * 2));
     RUN(dalloc(&u, M * Ir * 2));
@@ -186,8 +186,9 @@ int tllm_session::decide_decode_form()
     if (fp8_kv)
         return 0;
     const int kv8 = int8_kv ? 1 : 0;
-    if (fuse_qkv_cfg == 0 || !attn_tail || B != 1 || beam != 1 || paged_kv || tp != 1 || !neox
-        || !qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0))
+    // grouped K/V heads (Hkvr != Hr) run the separate-launch step: the one-launch front is built for one K/V head per query head
+    if (fuse_qkv_cfg == 0 || Hkvr != Hr || !attn_tail || B != 1 || beam != 1 || paged_kv || tp != 1 || !neox
+        || !qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0, Hkvr))
         return 0;
     for (auto& L : layers)
         if (!(L.qkv.wtype == wtype && L.qkv.K == D && L.qkv.ldw == (fp16_w ? 2 * D : (woq4 ? D / 2 : D)) && L.qkv.N == 3 * Dr
@@ -201,12 +202,12 @@ int tllm_session::decide_decode_form()
     for (auto& L : layers)
         o_fused = o_fused && L.dense.N == D && L.dense.scale_col && L.dense.wtype == wtype
             && (sq ? (L.dense.act_scale && L.attn_qscale) : true)
-            && qkv_attn_fused_serves_o(Hr, Dh, L.dense.N, L.dense.K, L.dense.ldw, wkind);
+            && qkv_attn_fused_serves_o(Hr, Dh, L.dense.N, L.dense.K, L.dense.ldw, wkind, Hkvr);
     // ... and the instance that will run must be resident as a whole (occupancy query x CUs of this device >= its grid)
-    if (!qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, o_fused ? 1 : 0))
+    if (!qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, o_fused ? 1 : 0, Hkvr))
     {
         o_fused = false;
-        qkv_attn_fused = qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0);
+        qkv_attn_fused = qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0, Hkvr);
     }
     return 0;
 }

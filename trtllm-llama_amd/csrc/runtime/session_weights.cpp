@@ -148,6 +148,7 @@ tllm_session_t tllm_session_create(const char* config_text)
     auto geti = [&](const char* k, int def) { return kv.count(k) ? atoi(kv[k].c_str()) : def; };
     s->num_layers = geti("num_layers", 0);
     s->num_heads = geti("num_heads", 0);
+    s->num_kv_heads = geti("num_kv_heads", s->num_heads);
     s->hidden = geti("hidden_size", 0);
     s->inter = geti("inter_size", 0);
     s->vocab = geti("vocab_size", 0);
@@ -200,6 +201,18 @@ tllm_session_t tllm_session_create(const char* config_text)
     s->Dh = s->hidden / s->num_heads;
     s->Hr = s->num_heads / s->tp;
     s->Dr = s->Hr * s->Dh;
+    if (s->num_kv_heads < 1 || s->num_kv_heads > s->num_heads || s->num_heads % s->num_kv_heads)
+    {
+        set_error("tllm_session_create: num_kv_heads %d must divide num_heads %d", s->num_kv_heads, s->num_heads);
+        return nullptr;
+    }
+    if (s->num_kv_heads % s->tp)
+    {
+        set_error("tllm_session_create: tp_size %d must divide num_kv_heads %d (K/V head replication is not built)", s->tp, s->num_kv_heads);
+        return nullptr;
+    }
+    s->Hkvr = s->num_kv_heads / s->tp;
+    s->QKVr = (s->Hr + 2 * s->Hkvr) * s->Dh;
     s->Ir = s->inter / s->tp;
     // vocab padded to a multiple of tp (PY/_utils.py:194-195, Q/llama_model.py:244)
     s->Vr = (s->vocab + s->tp - 1) / s->tp;
@@ -211,6 +224,12 @@ tllm_session_t tllm_session_create(const char* config_text)
     if (s->int8_kv && s->fp8_kv)
     {
         set_error("tllm_session_create: quant_mode %d sets both INT8_KV_CACHE (32) and FP8_KV_CACHE (64); a cache has one element type", qm);
+        return nullptr;
+    }
+    if (s->sq && s->num_kv_heads != s->num_heads)
+    {
+        set_error("tllm_session_create: num_kv_heads %d != num_heads %d with SmoothQuant weights is not built (the o_proj smoother folds "
+                  "into v_proj rows that several query heads share)", s->num_kv_heads, s->num_heads);
         return nullptr;
     }
     s->per_token = qm & QM_PER_TOKEN;
@@ -278,7 +297,7 @@ int32_t tllm_session_finalize(tllm_session_t s)
         t = s->find(p + "post_layernorm.weight");
         RUN(s->want(t, p + "post_layernorm.weight", TLLM_HALF, D));
         L.ln2 = t->dev;
-        RUN(s->resolve_linear(p + "attention.qkv", 3 * s->Dr, D, L.qkv));
+        RUN(s->resolve_linear(p + "attention.qkv", s->QKVr, D, L.qkv));
         RUN(s->resolve_linear(p + "attention.dense", D, s->Dr, L.dense));
         RUN(s->resolve_linear(p + "mlp.fc", s->Ir, D, L.fc));
         RUN(s->resolve_linear(p + "mlp.gate", s->Ir, D, L.gate));
@@ -408,6 +427,27 @@ int verify_engine_network(tllm_session_t s, const std::vector<EngineEntry>& ents
                 pc = numel > 1 ? 1 : 0;
             }
         d.per_channel.push_back(pc);
+    }
+    // the fused QKV weight has the extent the configuration's num_kv_heads implies: (Hr + 2 Hkvr) Dh output channels (fp16: the
+    // rows of [N, K]; weight-only / SmoothQuant: one scale per output channel)
+    for (auto& e : ents)
+    {
+        const bool w = e.name.size() > 21 && e.name.compare(e.name.size() - 21, 21, ".attention.qkv.weight") == 0;
+        const bool sc = e.name.size() > 32 && e.name.compare(e.name.size() - 32, 32, ".attention.qkv.per_channel_scale") == 0;
+        int64_t numel = 1;
+        for (int i = 0; i < e.nd; ++i)
+            numel *= e.dims[i];
+        int64_t got = -1;
+        if (w && !s->sq && !s->woq && e.nd == 2)
+            got = e.dims[0];
+        else if (sc && numel > 1)
+            got = numel;
+        if (got >= 0 && got != s->QKVr)
+        {
+            set_error("engine: %s has %lld output channels, num_kv_heads = %d (num_heads %d, head size %d, tp %d) implies %d", e.name.c_str(),
+                (long long) got, s->num_kv_heads, s->num_heads, s->Dh, s->tp, s->QKVr);
+            return 1;
+        }
     }
     std::string why;
     if (runtime::verify_network(s->network_json, d, why))

@@ -17,7 +17,7 @@ from tensorrt_llm.models import LLaMAForCausalLM, smooth_quantize, weight_only_q
 from tensorrt_llm.network import net_guard  # noqa: E402
 from tensorrt_llm.quantization import QuantMode  # noqa: E402
 
-from weight import load_from_ft_llama, load_from_hf_llama, parse_ft_config  # noqa: E402
+from weight import ft_num_kv_heads, load_from_ft_llama, load_from_hf_llama, parse_ft_config  # noqa: E402
 
 MODEL_NAME = 'llama'
 
@@ -86,6 +86,20 @@ def parse_arguments(args=None):
             parse_ft_config(Path(args.model_dir) / 'config.ini')
         args.n_embd, args.n_head, args.n_layer, args.n_positions = n_embd, n_head, n_layer, n_positions
         args.vocab_size, args.hidden_act, args.inter_size, args.multi_query_mode = vocab_size, hidden_act, inter_size, mqm
+        args.n_kv_head = ft_num_kv_heads(Path(args.model_dir) / 'config.ini')
+    elif args.hf_model_dir is not None and args.n_kv_head is None and os.path.exists(os.path.join(args.hf_model_dir, 'config.json')):
+        import json
+        with open(os.path.join(args.hf_model_dir, 'config.json')) as f:
+            args.n_kv_head = json.load(f).get('num_key_value_heads')
+    if args.n_kv_head is None:
+        args.n_kv_head = args.n_head
+    if args.n_kv_head < 1 or args.n_kv_head > args.n_head or args.n_head % args.n_kv_head:
+        p.error(f'--n_kv_head {args.n_kv_head} must divide --n_head {args.n_head}')
+    if args.n_kv_head % args.world_size:
+        p.error(f'--world_size {args.world_size} must divide --n_kv_head {args.n_kv_head} (K/V head replication is not built)')
+    if args.use_smooth_quant and args.n_kv_head != args.n_head:
+        p.error(f'--use_smooth_quant with grouped K/V heads (n_kv_head {args.n_kv_head} != n_head {args.n_head}) is not built: the '
+                'o_proj smoother folds into v_proj rows that several query heads share')
     for plugin_arg in ('use_gpt_attention_plugin', 'use_gemm_plugin'):
         if not getattr(args, plugin_arg):
             logger.info(f'{plugin_arg} is not set, setting it as {args.dtype} automatically (RoPE needs the plugin).')
@@ -114,7 +128,7 @@ def build_rank_engine(builder: Builder, builder_config, engine_name, rank, args)
                              max_position_embeddings=args.n_positions, dtype=kv_dtype, mlp_hidden_size=args.inter_size,
                              neox_rotary_style=True, multi_query_mode=args.multi_query_mode,
                              tensor_parallel=args.world_size, tensor_parallel_group=list(range(args.world_size)),
-                             quant_mode=args.quant_mode)
+                             quant_mode=args.quant_mode, num_kv_heads=args.n_kv_head)
     if args.use_smooth_quant:
         model = smooth_quantize(model, args.quant_mode)
     elif args.use_weight_only:
@@ -175,7 +189,7 @@ def build(rank, args):
             max_position_embeddings=args.n_positions, max_batch_size=args.max_batch_size,
             max_input_len=args.max_input_len, max_output_len=args.max_output_len, int8=int8_trt_flag,
             opt_level=args.builder_opt, multi_query_mode=args.multi_query_mode, inter_size=args.inter_size,
-            quant_mode=int(args.quant_mode))
+            quant_mode=int(args.quant_mode), num_kv_heads=args.n_kv_head)
         engine_name = get_engine_name(MODEL_NAME, args.dtype, args.world_size, cur_rank)
         engine = build_rank_engine(builder, builder_config, engine_name, cur_rank, args)
         assert engine is not None, f'Failed to build engine for rank {cur_rank}'

@@ -97,7 +97,7 @@ def smooth_llama_model(sd, act_range, alpha, num_layers, num_heads, num_kv_heads
     """Apply SmoothQuant to the float32 state dict `sd` in place and keep `act_range` consistent with it.
     `alpha_down`: migration strength of the down_proj input alone (None = alpha), see --smoothquant-down."""
     alpha_down = alpha if alpha_down is None else alpha_down
-    assert num_kv_heads == num_heads, 'folding the o_proj smoother into v_proj needs one V head per Q head'
+    assert num_kv_heads == num_heads, 'folding the o_proj smoother into v_proj needs one V head per Q head'  # (refused at argument time)
     for l in range(num_layers):
         p = f'model.layers.{l}.'
         q, k, v, o = (sd[p + f'self_attn.{n}_proj.weight'] for n in 'qkvo')
@@ -126,10 +126,25 @@ def smooth_llama_model(sd, act_range, alpha, num_layers, num_heads, num_kv_heads
             act_range[p + n]['w'] = w.abs().clip(1e-8, None).amax(dim=1).float()
 
 
+def check_grouped_heads(args):
+    """--smoothquant with grouped K/V heads is refused from the checkpoint's config.json alone, before anything is loaded."""
+    import json
+    cfg_path = Path(args.in_file) / 'config.json'
+    if args.smoothquant is None or not cfg_path.exists():
+        return
+    with open(cfg_path) as f:
+        c = json.load(f)
+    h, hkv = c.get('num_attention_heads'), c.get('num_key_value_heads') or c.get('num_attention_heads')
+    if h != hkv:
+        raise SystemExit(f'--smoothquant with grouped K/V heads (num_key_value_heads {hkv} != num_attention_heads {h}) is not built: '
+                         'the o_proj smoother folds into v_proj rows that several query heads share')
+
+
 @torch.no_grad()
 def hf_llama_converter(args: ProgArgs):
     from transformers import LlamaForCausalLM
     infer_tp = args.tensor_parallelism
+    check_grouped_heads(args)  # before the checkpoint is loaded
     saved_dir = Path(args.out_dir) / f'{infer_tp}-gpu'
     saved_dir.mkdir(parents=True, exist_ok=True)
     device = 'cuda' if torch.cuda.is_available() else 'cpu'
@@ -139,6 +154,12 @@ def hf_llama_converter(args: ProgArgs):
     num_heads = hf_config['num_attention_heads']
     num_kv_heads = hf_config.get('num_key_value_heads') or num_heads
     multi_query_mode = False
+    grouped = num_kv_heads != num_heads
+    if grouped and args.smoothquant is not None:
+        raise SystemExit(f'--smoothquant with grouped K/V heads (num_key_value_heads {num_kv_heads} != num_attention_heads {num_heads}) '
+                         'is not built: the o_proj smoother folds into v_proj rows that several query heads share')
+    if grouped and (num_heads % infer_tp or num_kv_heads % infer_tp):
+        raise SystemExit(f'tensor parallelism {infer_tp} must divide num_attention_heads {num_heads} and num_key_value_heads {num_kv_heads}')
 
     int8_outputs = None
     if args.calibrate_kv_cache:
@@ -170,13 +191,25 @@ def hf_llama_converter(args: ProgArgs):
     npw = lambda name: sd[name].numpy()
     for l in range(num_layers):
         p = f'model.layers.{l}.'
-        # QKV in FT shape [hidden, 3, out]
-        qkv = np.stack([npw(p + f'self_attn.{n}_proj.weight').T for n in 'qkv'], axis=1)
+        # QKV in FT shape [hidden, 3, out]; grouped K/V heads: [hidden, (H + 2*Hkv)*Dh], columns q | k | v (the loader splits the
+        # three ranges per rank, weight.py::split_qkv_gqa)
+        if grouped:
+            qkv = np.concatenate([npw(p + f'self_attn.{n}_proj.weight').T for n in 'qkv'], axis=1)
+        else:
+            qkv = np.stack([npw(p + f'self_attn.{n}_proj.weight').T for n in 'qkv'], axis=1)
         qkv_range = None
         if act_range:
             r = [act_range[p + f'self_attn.{n}_proj'] for n in 'qkv']
             qkv_range = {'x': r[0]['x'], 'y': torch.cat([t['y'] for t in r]), 'w': torch.cat([t['w'] for t in r])}
-        split_and_save_weight(0, saved_dir, infer_tp, p + 'attention.query_key_value.weight', qkv, storage, qkv_range, cfg)
+        if grouped:
+            # the weight whole, and (KV-cache calibration) the one scale the int8 / fp8 cache takes: max|y| / 127 over q | k | v
+            split_and_save_weight(0, saved_dir, infer_tp, p + 'attention.query_key_value.weight', qkv, storage, None,
+                                  {'int8_outputs': None, 'multi_query_mode': False})
+            if qkv_range is not None:
+                np.array([float(qkv_range['y'].max()) / 127.0], np.float32).tofile(
+                    saved_dir / f'model.{p}attention.query_key_value.scale_y_quant_orig.bin')
+        else:
+            split_and_save_weight(0, saved_dir, infer_tp, p + 'attention.query_key_value.weight', qkv, storage, qkv_range, cfg)
         for ft, hf in (('attention.dense', 'self_attn.o_proj'), ('mlp.down_proj', 'mlp.down_proj'),
                        ('mlp.gate_proj', 'mlp.gate_proj'), ('mlp.up_proj', 'mlp.up_proj')):
             split_and_save_weight(0, saved_dir, infer_tp, p + ft + '.weight', npw(p + hf + '.weight').T, storage,

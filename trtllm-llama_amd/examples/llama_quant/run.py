@@ -64,7 +64,8 @@ def load_session(engine_dir):
                                vocab_size=bc['vocab_size'], num_layers=bc['num_layers'],
                                gpt_attention_plugin=bool(config['plugin_config']['gpt_attention_plugin']),
                                multi_query_mode=bc.get('multi_query_mode', False),
-                               remove_input_padding=config['plugin_config']['remove_input_padding'])
+                               remove_input_padding=config['plugin_config']['remove_input_padding'],
+                               num_kv_heads=bc.get('num_kv_heads', bc['num_heads']) // world_size)
     path = Path(engine_dir) / get_engine_name('llama', dtype, world_size, runtime_rank)
     with open(path, 'rb') as f:
         engine_buffer = f.read()

@@ -43,6 +43,17 @@ def split_qkv(qkv_3d_d, tp_size, idx):
     return np.ascontiguousarray(split(w, tp_size, idx, dim=1).reshape(-1, d))
 
 
+def split_qkv_gqa(qkv, tp_size, idx, n_head, n_kv_head):
+    """[(H + 2*Hkv)*Dh, D] in the block order q | k | v -> this rank's [(H + 2*Hkv)*Dh / tp, D]: the q, k and v ranges are split
+    separately (heads idx*H/tp .. of q, K/V heads idx*Hkv/tp .. of k and of v) and put back in the same block order."""
+    rows, d = qkv.shape
+    dh = rows // (n_head + 2 * n_kv_head)
+    assert dh * (n_head + 2 * n_kv_head) == rows and n_head % tp_size == 0 and n_kv_head % tp_size == 0, \
+        f'QKV weight with {rows} rows is not (n_head {n_head} + 2 * n_kv_head {n_kv_head}) * head size, or tp {tp_size} does not divide'
+    q, k, v = qkv[:n_head * dh], qkv[n_head * dh:(n_head + n_kv_head) * dh], qkv[(n_head + n_kv_head) * dh:]
+    return np.ascontiguousarray(np.concatenate([split(x, tp_size, idx, dim=0) for x in (q, k, v)], axis=0))
+
+
 def _set_linear(module, w_out_in, quant_mode, np_dtype):
     """fp16 [out, in] weight -> module parameters for the module's quantisation mode."""
     if quant_mode.is_weight_only():
@@ -77,7 +88,11 @@ def load_from_hf_llama(tensorrt_llm_llama, hf_llama, rank=0, tensor_parallel=1, 
         qkv = np.concatenate([get(p + f'self_attn.{n}_proj.weight') for n in 'qkv'], axis=0)
         layer.input_layernorm.weight.value = get(p + 'input_layernorm.weight').astype(np_dtype)
         layer.post_layernorm.weight.value = get(p + 'post_attention_layernorm.weight').astype(np_dtype)
-        _set_linear(layer.attention.qkv, split_qkv(qkv, tensor_parallel, rank), quant_mode, np_dtype)
+        # unequal q / k / v (grouped-query attention) stack in the same block order; per rank the three ranges split separately
+        n_head, n_kv_head = getattr(m, 'num_heads', None), getattr(m, 'num_kv_heads', None)
+        qkv_r = (split_qkv(qkv, tensor_parallel, rank) if n_head is None or n_kv_head in (None, n_head)
+                 else split_qkv_gqa(qkv, tensor_parallel, rank, n_head, n_kv_head))
+        _set_linear(layer.attention.qkv, qkv_r, quant_mode, np_dtype)
         _set_linear(layer.attention.dense, split(get(p + 'self_attn.o_proj.weight'), tensor_parallel, rank, dim=1),
                     quant_mode, np_dtype)
         # naming trap: fc <-> gate_proj, gate <-> up_proj, proj <-> down_proj (T/tests/test_layer.py:158-160)
@@ -115,15 +130,27 @@ def parse_ft_config(ini_file):
     return n_embd, n_head, n_layer, n_positions, vocab_size, True, hidden_act, 1.0, False, inter_size, multi_query_mode, dtype, 0, 0
 
 
+def ft_num_kv_heads(ini_file):
+    """num_key_value_heads of an FT directory's config.ini (num_attention_heads when absent or None); parse_ft_config's tuple
+    keeps the reference's 14 fields."""
+    cfg = configparser.ConfigParser()
+    cfg.read(ini_file)
+    s = cfg['llama']
+    v = s.get('num_key_value_heads', 'None')
+    return s.getint('num_attention_heads') if v in ('None', '') else int(v)
+
+
 def load_from_ft_llama(tensorrt_llm_llama, dir_path, rank=0, tensor_parallel=1, dtype='float16'):
     tensorrt_llm.logger.info('Loading weights from FT LLaMA...')
     tik = time.time()
     quant_mode = getattr(tensorrt_llm_llama, 'quant_mode', QuantMode(0))
     n_embd, n_head, n_layer, _, vocab_size, _, _, _, _, inter_size, *_ = parse_ft_config(Path(dir_path) / 'config.ini')
+    n_kv_head = ft_num_kv_heads(Path(dir_path) / 'config.ini')
     np_dtype = str_dtype_to_np(dtype)
     d = Path(dir_path)
     m = tensorrt_llm_llama
     sq = quant_mode.has_act_and_weight_quant()
+    assert not (sq and n_kv_head != n_head), 'SmoothQuant with grouped K/V heads (num_key_value_heads != num_attention_heads) is not built'
     per_ch, per_tok = quant_mode.has_per_channel_scaling(), quant_mode.has_per_token_dynamic_scaling()
 
     def fromfile(name, shape=None, dt=None):
@@ -205,9 +232,15 @@ def load_from_ft_llama(tensorrt_llm_llama, dir_path, rank=0, tensor_parallel=1, 
                 layer.post_layernorm.scale_to_int.value = f1(p + 'mlp.gate_proj.scale_x_orig_quant.bin')
                 layer.mlp.quantization_scaling_factor.value = f1(p + 'mlp.down_proj.scale_x_orig_quant.bin')
         else:
-            qkv = need(p + 'attention.query_key_value.weight.bin', [n_embd, 3, n_embd])  # [in, 3, out]
-            qkv = np.ascontiguousarray(qkv.transpose(1, 2, 0).reshape(3 * n_embd, n_embd))
-            _set_linear(layer.attention.qkv, split_qkv(qkv, tensor_parallel, rank), quant_mode, np_dtype)
+            if n_kv_head == n_head:
+                qkv = need(p + 'attention.query_key_value.weight.bin', [n_embd, 3, n_embd])  # [in, 3, out]
+                qkv = np.ascontiguousarray(qkv.transpose(1, 2, 0).reshape(3 * n_embd, n_embd))
+                qkv = split_qkv(qkv, tensor_parallel, rank)
+            else:  # grouped-query attention: [in, (H + 2*Hkv)*Dh], columns q | k | v
+                qkv_rows = (n_head + 2 * n_kv_head) * (n_embd // n_head)
+                qkv = need(p + 'attention.query_key_value.weight.bin', [n_embd, qkv_rows])
+                qkv = split_qkv_gqa(np.ascontiguousarray(qkv.T), tensor_parallel, rank, n_head, n_kv_head)
+            _set_linear(layer.attention.qkv, qkv, quant_mode, np_dtype)
             _set_linear(layer.attention.dense,
                         need(p + f'attention.dense.weight.{rank}.bin', [n_embd // tensor_parallel, n_embd]).T, quant_mode, np_dtype)
             _set_linear(layer.mlp.fc, need(p + f'mlp.gate_proj.weight.{rank}.bin', [n_embd, inter_size // tensor_parallel]).T,

@@ -95,6 +95,9 @@ class Builder():
             'tokens_per_block': int(getattr(network.plugin_config, 'tokens_per_block', 64)),
             'network_ops': ','.join(ops[:0]),  # the node list itself goes below as one JSON line
         }
+        # grouped-query attention: the key travels only when it differs, so that multi-head engines stay byte-identical
+        if int(cfg.get('num_kv_heads') or cfg['num_heads']) != int(cfg['num_heads']):
+            header['num_kv_heads'] = int(cfg['num_kv_heads'])
         tactics = self._profile_gemm_tactics(cfg, inter_size)
         if tactics:
             header['gemm_tactics'] = tactics
@@ -165,7 +168,10 @@ class Builder():
             # the fp16 tactic table is never consulted - nothing to profile
             return ''
         wtype = 3 if qm & 4 else 0  # SmoothQuant int8, else fp16
-        shapes = {(3 * D // tp, D), (D, D // tp), (inter // tp, D), (D, inter // tp)}
+        qkv_n = 3 * D  # grouped-query attention: q plus Hkv K and V heads
+        if cfg.get('num_heads') and cfg.get('num_kv_heads'):
+            qkv_n = D + 2 * int(cfg['num_kv_heads']) * (D // int(cfg['num_heads']))
+        shapes = {(qkv_n // tp, D), (D, D // tp), (inter // tp, D), (D, inter // tp)}
         ms = sorted({m_max} | {1 << i for i in range(5, 14) if (1 << i) < m_max})
         for m in ms:
             for n, k in shapes:

@@ -16,12 +16,20 @@ class Attention(Module):
                  apply_query_key_layer_scaling=False, attention_mask_type=AttentionMaskType.padding, bias=True,
                  dtype=None, position_embedding_type=PositionEmbeddingType.learned_absolute, neox_rotary_style=False,
                  use_int8_kv_cache=False, rotary_embedding_percentage=1.0, tp_group=None, tp_size=1,
-                 multi_block_mode=False, multi_query_mode=False, use_fp8_kv_cache=False):
+                 multi_block_mode=False, multi_query_mode=False, use_fp8_kv_cache=False, num_kv_heads=None):
         super().__init__()
         self.attention_mask_type = attention_mask_type
         self.attention_head_size = hidden_size // num_attention_heads
         self.num_attention_heads = num_attention_heads // tp_size
-        self.num_attention_kv_heads = 1 if multi_query_mode else self.num_attention_heads
+        # grouped-query attention: num_kv_heads K/V heads of the whole model (None: one per query head); query head h reads K/V head
+        # h // (num_attention_heads // num_kv_heads).  The fused QKV output is [q: H*Dh | k: Hkv*Dh | v: Hkv*Dh] per rank.
+        if num_kv_heads is None:
+            num_kv_heads = num_attention_heads
+        if not (1 <= num_kv_heads <= num_attention_heads) or num_attention_heads % num_kv_heads:
+            raise ValueError(f'num_kv_heads {num_kv_heads} must divide num_attention_heads {num_attention_heads}')
+        if num_kv_heads % tp_size:
+            raise ValueError(f'tp_size {tp_size} must divide num_kv_heads {num_kv_heads} (K/V head replication is not built)')
+        self.num_attention_kv_heads = num_kv_heads // tp_size
         self.hidden_size = hidden_size // tp_size
         self.max_position_embeddings = max_position_embeddings
         self.num_layers = num_layers
@@ -51,7 +59,7 @@ class Attention(Module):
             self.register_parameter('kv_quant_orig_scale', None)
         if multi_query_mode:
             raise NotImplementedError('multi_query_mode is not built (LLaMA-7B is MHA)')
-        self.qkv = ColumnLinear(hidden_size, hidden_size * 3, bias=bias, dtype=dtype, tp_group=tp_group, tp_size=tp_size,
+        self.qkv = ColumnLinear(hidden_size, hidden_size + 2 * num_kv_heads * self.attention_head_size, bias=bias, dtype=dtype, tp_group=tp_group, tp_size=tp_size,
                                 gather_output=False)
         self.dense = RowLinear(hidden_size, hidden_size, bias=bias, dtype=dtype, tp_group=tp_group, tp_size=tp_size)
 

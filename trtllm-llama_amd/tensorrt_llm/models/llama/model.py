@@ -18,9 +18,10 @@ class LLaMADecoderLayer(Module):
 
     def __init__(self, layer_id, hidden_size, num_attention_heads, max_position_embeddings, dtype=None,
                  hidden_act='silu', mlp_hidden_size=None, neox_rotary_style=True, multi_query_mode=False,
-                 tp_group=None, tp_size=1, quant_mode=QuantMode(0)):
+                 tp_group=None, tp_size=1, quant_mode=QuantMode(0), num_kv_heads=None):
         super().__init__()
         self._layer_id = layer_id
+        self.num_kv_heads = num_attention_heads if num_kv_heads is None else num_kv_heads
         # kept on the layer because smooth_quantize() rebuilds the sub-modules from them
         self.hidden_size = hidden_size
         self.num_attention_heads = num_attention_heads
@@ -43,7 +44,7 @@ class LLaMADecoderLayer(Module):
                                    neox_rotary_style=neox_rotary_style, multi_query_mode=multi_query_mode,
                                    tp_group=tp_group, tp_size=tp_size,
                                    use_int8_kv_cache=quant_mode.has_int8_kv_cache(),
-                                   use_fp8_kv_cache=quant_mode.has_fp8_kv_cache())
+                                   use_fp8_kv_cache=quant_mode.has_fp8_kv_cache(), num_kv_heads=self.num_kv_heads)
         self.mlp = GatedMLP(hidden_size=hidden_size, ffn_hidden_size=self.mlp_hidden_size, hidden_act=hidden_act,
                             dtype=dtype, bias=False, tp_group=tp_group, tp_size=tp_size)
         self.post_layernorm = RmsNorm(normalized_shape=hidden_size, dtype=dtype)
@@ -71,7 +72,7 @@ class LLaMAModel(Module):
 
     def __init__(self, num_layers, num_heads, hidden_size, vocab_size, hidden_act, max_position_embeddings, dtype,
                  mlp_hidden_size=None, neox_rotary_style=True, tensor_parallel=1, tensor_parallel_group=None,
-                 multi_query_mode=False, quant_mode=QuantMode(0)):
+                 multi_query_mode=False, quant_mode=QuantMode(0), num_kv_heads=None):
         super().__init__()
         self.vocab_embedding = Embedding(vocab_size, hidden_size, dtype=dtype)  # replicated under TP
         self.layers = ModuleList([
@@ -79,7 +80,8 @@ class LLaMAModel(Module):
                               max_position_embeddings=max_position_embeddings, dtype=dtype, hidden_act=hidden_act,
                               mlp_hidden_size=mlp_hidden_size, neox_rotary_style=neox_rotary_style,
                               multi_query_mode=multi_query_mode, tp_group=tensor_parallel_group,
-                              tp_size=tensor_parallel, quant_mode=quant_mode) for i in range(num_layers)
+                              tp_size=tensor_parallel, quant_mode=quant_mode, num_kv_heads=num_kv_heads)
+            for i in range(num_layers)
         ])
         self.ln_f = RmsNorm(normalized_shape=hidden_size, dtype=dtype)
 
@@ -111,7 +113,7 @@ class LLaMAForCausalLM(LLaMAModel):
 
     def __init__(self, num_layers, num_heads, hidden_size, vocab_size, hidden_act, max_position_embeddings, dtype,
                  mlp_hidden_size=None, neox_rotary_style=True, tensor_parallel=1, tensor_parallel_group=None,
-                 multi_query_mode=False, quant_mode=QuantMode(0)):
+                 multi_query_mode=False, quant_mode=QuantMode(0), num_kv_heads=None):
         self.kv_dtype = str_dtype_to_trt(dtype) if isinstance(dtype, str) else DataType(dtype)
         if quant_mode.has_int8_kv_cache():
             self.kv_dtype = str_dtype_to_trt('int8')
@@ -120,13 +122,14 @@ class LLaMAForCausalLM(LLaMAModel):
         self.quant_mode = quant_mode
         self.num_layers = num_layers
         self.num_heads = num_heads
+        self.num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
         self.hidden_size = hidden_size
         self.vocab_size = vocab_size
         self.tensor_parallel = tensor_parallel
         self._multi_query_mode = multi_query_mode
         super().__init__(num_layers, num_heads, hidden_size, vocab_size, hidden_act, max_position_embeddings, dtype,
                          mlp_hidden_size, neox_rotary_style, tensor_parallel, tensor_parallel_group,
-                         multi_query_mode, quant_mode)
+                         multi_query_mode, quant_mode, num_kv_heads)
         self.inter_size = mlp_hidden_size if mlp_hidden_size else hidden_size * 4
         vocab_size_padded = pad_vocab_size(vocab_size, tensor_parallel)
         self.lm_head = ColumnLinear(hidden_size, vocab_size_padded, bias=False, dtype=dtype,
@@ -152,7 +155,7 @@ class LLaMAForCausalLM(LLaMAModel):
     def prepare_inputs(self, max_batch_size, max_input_len, max_new_tokens, use_cache, max_beam_width):
         """Symbolic network inputs with the reference's tensor names (llama_model.py:289-435; generation.py:188-208)."""
         head_size = self.hidden_size // self.num_heads
-        num_heads = self.num_heads // self.tensor_parallel
+        num_heads = self.num_kv_heads // self.tensor_parallel  # the cache holds K/V heads
         max_len = max_input_len + max_new_tokens
         bb = [1, (max_batch_size * max_beam_width + 1) // 2, max_batch_size * max_beam_width]
         bs = [1, (max_batch_size + 1) // 2, max_batch_size]

@@ -24,7 +24,8 @@ def smooth_quantize(model, quant_mode):
                                                neox_rotary_style=layer.neox_rotary_style,
                                                use_int8_kv_cache=quant_mode.has_int8_kv_cache(),
                                                use_fp8_kv_cache=quant_mode.has_fp8_kv_cache(),
-                                               tp_group=layer.tp_group, tp_size=layer.tp_size, quant_mode=quant_mode)
+                                               tp_group=layer.tp_group, tp_size=layer.tp_size, quant_mode=quant_mode,
+                                               num_kv_heads=getattr(layer, 'num_kv_heads', None))
         assert hasattr(layer, 'mlp'), 'The layer has no mlp'
         layer.mlp = SmoothQuantGatedMLP(hidden_size=layer.hidden_size, ffn_hidden_size=layer.mlp_hidden_size,
                                         hidden_act=layer.hidden_act, dtype=layer.dtype, tp_group=layer.tp_group,

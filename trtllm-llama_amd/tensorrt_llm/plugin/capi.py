@@ -65,6 +65,23 @@ class PluginField:
         self.type = _NP_TO_PF[self.data.dtype] if type is None else type
 
 
+class AttentionParams(ctypes.Structure):
+    """tllm_attention_params_t (include/tllm_runtime_api.h): the argument of tllm_attention_decode / tllm_attention_context, the
+    session-free entry points of the two attention launchers with grouped-query attention (num_kv_heads)."""
+    _fields_ = [('batch', ctypes.c_int32), ('seq', ctypes.c_int32), ('num_heads', ctypes.c_int32), ('num_kv_heads', ctypes.c_int32),
+                ('head_size', ctypes.c_int32), ('rotary_dim', ctypes.c_int32), ('neox', ctypes.c_int32), ('q_scaling', ctypes.c_float),
+                ('kv_cache_type', ctypes.c_int32), ('max_seq_len', ctypes.c_int32), ('max_input_len', ctypes.c_int32),
+                ('timestep', ctypes.c_int32), ('qkv', ctypes.c_void_p), ('kv_cache', ctypes.c_void_p),
+                ('sequence_length', ctypes.c_void_p), ('input_lengths', ctypes.c_void_p), ('masked_tokens', ctypes.c_void_p),
+                ('kv_scale_orig_quant', ctypes.c_void_p), ('kv_scale_quant_orig', ctypes.c_void_p),
+                ('cache_indirection', ctypes.c_void_p), ('beam_width', ctypes.c_int32), ('cache_seq_stride', ctypes.c_int32),
+                ('block_pointers', ctypes.c_void_p), ('tokens_per_block', ctypes.c_int32), ('max_blocks_per_seq', ctypes.c_int32),
+                ('cu_seqlens', ctypes.c_void_p), ('rows_per_group', ctypes.c_int32), ('q_heads_per_workgroup', ctypes.c_int32),
+                ('combine_launch', ctypes.c_int32), ('tail_quant_scale', ctypes.c_void_p), ('tail_out_q8', ctypes.c_void_p),
+                ('out_q8', ctypes.c_void_p), ('out_q_scale', ctypes.c_void_p), ('out', ctypes.c_void_p),
+                ('workspace', ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -126,6 +143,14 @@ def load_library():
     lib.tllm_comm_init_rank.argtypes = [c.POINTER(c.c_int32), c.c_int32, c.c_int32, c.c_void_p]
     lib.tllm_comm_init_rank.restype = c.c_int32
     lib.tllm_comm_destroy_all.restype = c.c_int32
+    lib.tllm_attention_workspace_size.argtypes = [c.POINTER(AttentionParams), c.c_int32]
+    lib.tllm_attention_workspace_size.restype = c.c_size_t
+    lib.tllm_attention_decode.argtypes = [c.POINTER(AttentionParams), c.c_void_p]
+    lib.tllm_attention_decode.restype = c.c_int32
+    lib.tllm_attention_context.argtypes = [c.POINTER(AttentionParams), c.c_void_p]
+    lib.tllm_attention_context.restype = c.c_int32
+    lib.tllm_attention_decode_layout.argtypes = [c.POINTER(AttentionParams)] + [c.POINTER(c.c_int32)] * 4
+    lib.tllm_attention_decode_layout.restype = c.c_int32
     lib.tllm_symmetric_quantize_last_axis.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int32, c.c_void_p,
                                                       c.c_void_p, c.c_void_p]
     lib.tllm_symmetric_quantize_last_axis.restype = c.c_int32

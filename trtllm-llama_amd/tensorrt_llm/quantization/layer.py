@@ -214,13 +214,13 @@ class SmoothQuantAttention(Attention):
                  apply_query_key_layer_scaling=False, attention_mask_type=AttentionMaskType.causal, bias=False,
                  dtype=None, position_embedding_type=PositionEmbeddingType.rope, neox_rotary_style=True,
                  use_int8_kv_cache=False, tp_group=None, tp_size=1, multi_block_mode=False, multi_query_mode=False,
-                 quant_mode=QuantMode(0), use_fp8_kv_cache=False):
+                 quant_mode=QuantMode(0), use_fp8_kv_cache=False, num_kv_heads=None):
         super().__init__(hidden_size, num_attention_heads, max_position_embeddings, num_layers,
                          apply_query_key_layer_scaling, attention_mask_type, False, dtype, position_embedding_type,
                          neox_rotary_style, use_int8_kv_cache, 1.0, tp_group, tp_size, multi_block_mode,
-                         multi_query_mode, use_fp8_kv_cache)
+                         multi_query_mode, use_fp8_kv_cache, num_kv_heads)
         self.quant_mode = quant_mode
-        self.qkv = SmoothQuantLinear(hidden_size, hidden_size * 3, bias=bias, dtype=dtype, tp_group=tp_group,
+        self.qkv = SmoothQuantLinear(hidden_size, self.qkv.out_features * tp_size, bias=bias, dtype=dtype, tp_group=tp_group,
                                      tp_size=tp_size, gather_output=False, quant_mode=quant_mode)
         self.dense = SmoothQuantRowLinear(hidden_size, hidden_size, bias=bias, dtype=dtype, tp_group=tp_group,
                                           tp_size=tp_size, quant_mode=quant_mode)

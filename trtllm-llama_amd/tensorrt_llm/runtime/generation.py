@@ -30,6 +30,7 @@ class ModelConfig:
     paged_kv_cache: bool = False
     tokens_per_block: int = 64
     use_prompt_tuning: bool = False
+    num_kv_heads: int = None  # grouped-query attention: K/V heads of this rank (None: num_heads); the engine header is what the session runs
 
 
 @dataclass
@@ -78,6 +79,12 @@ class GenerationSession(object):
     @property
     def num_heads(self):
         return self._model_config.num_heads
+
+    @property
+    def num_kv_heads(self):
+        """K/V heads of this rank (grouped-query attention); num_heads when the configuration does not say"""
+        kv = self._model_config.num_kv_heads
+        return self._model_config.num_heads if kv is None else kv
 
     @property
     def hidden_size(self):
