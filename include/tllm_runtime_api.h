@@ -255,6 +255,10 @@ int32_t tllm_session_fused_retries(tllm_session_t s);
  * residual as a stage of that launch, bit 2 = the gated MLP (gate|up GEMV + down GEMV) in one launch (kernels/mlp_fused.hip, r06;
  * opt-in with the session key fuse_mlp = 1: bit-identical, measured slower than the two GEMVs).  -1 before setup. */
 int32_t tllm_session_decode_form(tllm_session_t s);
+/* Greedy-step launches this session has enqueued WITH the lm_head launch's arg-max pairs since its last setup (session key
+ * greedy_partials; batch 1, tp 1, greedy).  A step captured into the graph counts once, when it is captured, not per replay.
+ * 0 after generation steps = every greedy step scanned the logits.  -1: null session. */
+int64_t tllm_session_greedy_partials_used(tllm_session_t s);
 
 /* Instrumented generation steps (eager, a hipEvent pair around every launch) for the roofline report:
  * elapsed milliseconds and launch counts per class over `n_steps` steps.
@@ -294,6 +298,41 @@ typedef struct
 } tllm_gemv_params_t;
 
 int32_t tllm_gemv(const tllm_gemv_params_t* p, tllm_stream_t stream);
+/* The same launch with the two options of the lm_head launch (kernels.h GemvParams::resident_rows / argmax_part; fp16 weights,
+ * M = 1, no epilogue - anything else is refused): rows [0, resident_rows) of W load with the allocating cache policy, the rest
+ * non-temporally (results do not depend on it); argmax_part, if not NULL, receives TLLM_ARGMAX_PAIRS pairs {float value, int32
+ * index}: per wave of the launch the arg-max of the outputs it finished (ties: lowest index), {-inf, INT32_MAX} elsewhere. */
+#define TLLM_ARGMAX_PAIRS 2048
+int32_t tllm_gemv_head(const tllm_gemv_params_t* p, int32_t resident_rows, void* argmax_part, tllm_stream_t stream);
+
+/* Kernel-level entry for the greedy step that ends a generation step (kernels/decode_step.hip; kernels.h GreedyParams), for parity
+ * tests: the arg-max of logits f32 [nparts, batch, vocab_part] (ids >= vocab are padding), then the bookkeeping on the caller's
+ * device buffers - seq_len[b] += advance, finished rows emit end_id, out_ids[b, seq_len[b]] = id, cur_ids[b] = id,
+ * finished[b] |= id == end_id, the RoPE row of position seq_len[b] - (max_input_len - input_lengths[b]) and the embedding row
+ * of id.  argmax_part (batch 1, nparts 1): the pairs tllm_gemv_head left for these logits - reduced instead of the logits. */
+typedef struct
+{
+    const float* logits;
+    int32_t batch, vocab_part, nparts, vocab;
+    int32_t* cur_ids;
+    int32_t* out_ids;
+    int32_t out_stride;
+    int32_t* seq_len;
+    int32_t* finished;
+    int32_t end_id, advance;
+    float* rope_row_out;
+    int32_t* rope_pos_out;
+    const float* rope_table;
+    int32_t rope_half, rope_table_len;
+    const int32_t* input_lengths;
+    int32_t max_input_len;
+    const void* emb_table;
+    void* x_out;
+    int32_t hidden;
+    uint32_t* step_epoch;
+    const void* argmax_part;
+} tllm_greedy_params_t;
+int32_t tllm_greedy_step(const tllm_greedy_params_t* p, tllm_stream_t stream);
 /* Test/bench knob: persistent workgroups per CU (0 = occupancy query). */
 void tllm_gemv_set_blocks_per_cu(int32_t n);
 /* Test/bench knob: number of rows (sequences) from which the SmoothQuant decode GEMM runs on the matrix pipe

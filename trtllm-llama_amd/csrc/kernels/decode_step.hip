@@ -1,6 +1,7 @@
 // The kernels that end a decode step: arg-max, the greedy step, the beam-search step and token forcing (teacher forcing for
 // parity tests).  One workgroup per row.  sampling_step_kernel (sampling.hip) carries its own copy of greedy_step_kernel's
-// bookkeeping (next RoPE row, token commit, step_epoch, next input row): a change to one is a change to both.
+// bookkeeping (next RoPE row, token commit, step_epoch, next input row): a change to what is committed in one is a change to
+// both.  (How the greedy kernel gets there - the lm_head launch's arg-max partials, the step words loaded at entry - is its own.)
 #include "dev_utils.h"
 #include "kernels.h"
 #include "launch_util.h"
@@ -63,67 +64,104 @@ __global__ __launch_bounds__(1024) void argmax_kernel(int32_t* out_ids, const fl
     }
 }
 
-// Entry contract (gemv_impl.h): what the logits loads are built from leads the parameter list and is preloaded into SGPRs; the
-// struct trails it for the bookkeeping and is first read behind the first logits requests.  launch_greedy_step fills both from
-// the one GreedyParams.
-__global__ __launch_bounds__(1024) void greedy_step_kernel(const float* const hot_logits, const int hot_batch, const int hot_vocab_part,
-    const int hot_nparts, const int hot_vocab, const GreedyParams p)
+// Entry contract (gemv_impl.h): what the first loads are built from leads the parameter list and is preloaded into SGPRs - the
+// logits (or the lm_head launch's arg-max partials) and the three step words of the row; the struct trails it for the
+// bookkeeping and is first read behind those requests.  launch_greedy_step fills both from the one GreedyParams.
+//
+// hot_part (batch 1, one vocabulary part): the kArgmaxPairs {value, index} pairs the lm_head launch left, one per wave of its
+// grid (GemvParams::argmax_part).  The head had every logit in a register when it wrote it; reducing its 16 KB of pairs - two
+// loads per thread - replaces pulling all 128 KB of logits through this one CU's queue.  The rule is the scan's (greater wins,
+// ties to the lowest index) and is associative, so the token is the same.  The kernel boundary orders the two launches: no flag,
+// no wait.  hot_part null: the scan.
+//
+// seq_len[b], finished[b] and input_lengths[b] are requested here as well, as raw values (no conversion or compare next to the
+// load), and the epoch word right behind the first requests, so that thread 0's commit below contains no load: it used to chase
+// seq_len -> finished, two dependent round trips behind the reduction, and then read-modify-write the epoch.  hot_finished /
+// hot_input_lengths are never null: the launcher points an absent one at seq_len (loaded, ignored; a RoPE row without
+// input_lengths is refused).
+__global__ __launch_bounds__(1024) void greedy_step_kernel(const float* const hot_logits, const uint2* const hot_part,
+    const int32_t* const hot_seq_len, const int32_t* const hot_finished, const int32_t* const hot_input_lengths, const int hot_batch,
+    const int hot_vocab_part, const int hot_nparts, const int hot_vocab, const GreedyParams p)
 {
     __shared__ float sv[16];
     __shared__ int si[16];
     const int b = blockIdx.x;
     float best = -INFINITY;
     int bi = 0x7fffffff;
-    for (int part = 0; part < hot_nparts; ++part)
+    // raw step words, consumed behind the reduction
+    const int sl0 = hot_seq_len[b], fin0 = hot_finished[b], inlen0 = hot_input_lengths[b];
+    uint32_t epoch0 = 0; // requested behind the first logits / pairs loads: its pointer is the struct's
+    if (hot_part) // uniform, a preloaded scalar
     {
-        const float* l = hot_logits + ((int64_t) part * hot_batch + b) * hot_vocab_part;
-        const int base_id = part * hot_vocab_part;
-        if ((hot_vocab_part & 3) == 0 && (reinterpret_cast<uintptr_t>(l) & 15) == 0)
+        const uint2 pr[2] = {hot_part[threadIdx.x], hot_part[threadIdx.x + kArgmaxPairs / 2]};
+        // unconditional (no branch around a load): an absent epoch word reads a valid word, ignored
+        epoch0 = *(p.step_epoch ? p.step_epoch : reinterpret_cast<const uint32_t*>(hot_seq_len));
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
         {
-            // 16-byte loads, all of a thread's requests in flight before the compares (latency-bound otherwise)
-            constexpr int UNR = 8;
-            const int nvec = hot_vocab_part >> 2;
-            for (int v0 = threadIdx.x; v0 < nvec; v0 += blockDim.x * UNR)
-            {
-                float4 vals[UNR];
-#pragma unroll
-                for (int u = 0; u < UNR; ++u)
-                {
-                    const int vi = v0 + u * blockDim.x;
-                    vals[u] = vi < nvec ? reinterpret_cast<const float4*>(l)[vi]
-                                        : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-                }
-#pragma unroll
-                for (int u = 0; u < UNR; ++u)
-                {
-                    const int id0 = base_id + (v0 + u * blockDim.x) * 4;
-                    const float f[4] = {vals[u].x, vals[u].y, vals[u].z, vals[u].w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                    {
-                        const int id = id0 + e;
-                        if (id < hot_vocab && (f[e] > best || (f[e] == best && id < bi)))
-                        {
-                            best = f[e];
-                            bi = id;
-                        }
-                    }
-                }
-            }
-            continue;
-        }
-        for (int i = threadIdx.x; i < hot_vocab_part; i += blockDim.x)
-        {
-            const int id = base_id + i;
-            if (id >= hot_vocab)
-                break;
-            const float v = l[i];
-            if (v > best || (v == best && id < bi))
+            const float v = __uint_as_float(pr[u].x);
+            const int id = (int) pr[u].y;
+            if (id < hot_vocab && (v > best || (v == best && id < bi)))
             {
                 best = v;
                 bi = id;
             }
         }
+    }
+    else
+    {
+        for (int part = 0; part < hot_nparts; ++part)
+        {
+            const float* l = hot_logits + ((int64_t) part * hot_batch + b) * hot_vocab_part;
+            const int base_id = part * hot_vocab_part;
+            if ((hot_vocab_part & 3) == 0 && (reinterpret_cast<uintptr_t>(l) & 15) == 0)
+            {
+                // 16-byte loads, all of a thread's requests in flight before the compares (latency-bound otherwise)
+                constexpr int UNR = 8;
+                const int nvec = hot_vocab_part >> 2;
+                for (int v0 = threadIdx.x; v0 < nvec; v0 += blockDim.x * UNR)
+                {
+                    float4 vals[UNR];
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u)
+                    {
+                        const int vi = v0 + u * blockDim.x;
+                        vals[u] = vi < nvec ? reinterpret_cast<const float4*>(l)[vi]
+                                            : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+                    }
+#pragma unroll
+                    for (int u = 0; u < UNR; ++u)
+                    {
+                        const int id0 = base_id + (v0 + u * blockDim.x) * 4;
+                        const float f[4] = {vals[u].x, vals[u].y, vals[u].z, vals[u].w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                        {
+                            const int id = id0 + e;
+                            if (id < hot_vocab && (f[e] > best || (f[e] == best && id < bi)))
+                            {
+                                best = f[e];
+                                bi = id;
+                            }
+                        }
+                    }
+                }
+                continue;
+            }
+            for (int i = threadIdx.x; i < hot_vocab_part; i += blockDim.x)
+            {
+                const int id = base_id + i;
+                if (id >= hot_vocab)
+                    break;
+                const float v = l[i];
+                if (v > best || (v == best && id < bi))
+                {
+                    best = v;
+                    bi = id;
+                }
+            }
+        }
+        epoch0 = *(p.step_epoch ? p.step_epoch : reinterpret_cast<const uint32_t*>(hot_seq_len));
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1)
@@ -146,7 +184,7 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const float* const ho
     {
         // next step's position: (seq_len after this step's advance) - padding of this sequence
         const int j = threadIdx.x - 64;
-        int pos = p.seq_len[b] + (p.advance ? 1 : 0) - (p.max_input_len - p.input_lengths[b]);
+        int pos = sl0 + (p.advance ? 1 : 0) - (p.max_input_len - inlen0);
         pos = pos < 0 ? 0 : (pos >= p.rope_table_len ? p.rope_table_len - 1 : pos);
         reinterpret_cast<float2*>(p.rope_row_out)[(int64_t) b * p.rope_half + j]
             = reinterpret_cast<const float2*>(p.rope_table)[(int64_t) pos * p.rope_half + j];
@@ -164,7 +202,7 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const float* const ho
                 bi = si[w];
             }
         int id = bi == 0x7fffffff ? 0 : bi;
-        int sl = p.seq_len[b];
+        int sl = sl0;
         if (p.advance)
         {
             sl += 1;
@@ -172,7 +210,7 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const float* const ho
         }
         if (p.finished)
         {
-            if (p.finished[b])
+            if (fin0)
                 id = p.end_id;
             else if (p.end_id >= 0 && id == p.end_id)
                 p.finished[b] = 1;
@@ -182,7 +220,7 @@ __global__ __launch_bounds__(1024) void greedy_step_kernel(const float* const ho
         p.cur_ids[b] = id;
         si[0] = id;
         if (b == 0 && p.step_epoch)
-            *p.step_epoch += 1;
+            *p.step_epoch = epoch0 + 1; // (only this thread of this launch writes the word: the value read at entry is current)
     }
     if (p.emb_table) // uniform: the next step's input row, gathered here instead of by an embedding launch of its own
     {
@@ -370,7 +408,19 @@ int launch_greedy_step(const GreedyParams& p, hipStream_t stream)
         set_error("greedy step: fused embedding gather needs x_out and hidden %% 8 == 0 (got %d)", p.hidden);
         return -1;
     }
-    hipLaunchKernelGGL(greedy_step_kernel, dim3(p.batch), dim3(1024), 0, stream, p.logits, p.batch, p.vocab_part, p.nparts, p.vocab, p);
+    if (p.rope_row_out && (!p.input_lengths || !p.rope_table))
+    {
+        set_error("greedy step: the next RoPE row needs input_lengths and the RoPE table");
+        return -1;
+    }
+    if (p.argmax_part && (p.batch != 1 || p.nparts != 1 || (reinterpret_cast<uintptr_t>(p.argmax_part) & 7)))
+    {
+        set_error("greedy step: arg-max partials serve batch 1 and one vocabulary part (got batch %d, %d parts)", p.batch, p.nparts);
+        return -1;
+    }
+    hipLaunchKernelGGL(greedy_step_kernel, dim3(p.batch), dim3(1024), 0, stream, p.logits, static_cast<const uint2*>(p.argmax_part),
+        p.seq_len, p.finished ? p.finished : p.seq_len, p.input_lengths ? p.input_lengths : p.seq_len, p.batch, p.vocab_part, p.nparts,
+        p.vocab, p);
     return check_launch("greedy_step");
 }
 

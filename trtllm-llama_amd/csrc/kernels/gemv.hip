@@ -18,6 +18,11 @@ int launch_gemv(const GemvParams& p, hipStream_t stream)
         set_error("gemv: unsupported M=%d N=%d K=%d (1 <= M <= 8)", p.M, p.N, p.K);
         return -1;
     }
+    if ((p.resident_rows > 0 || p.argmax_part) && (p.wtype != W_FP16 || p.M != 1))
+    {
+        set_error("gemv: resident_rows / argmax_part are options of the lm_head launch (fp16 weights, one row)");
+        return -1;
+    }
     const bool sq = p.wtype == W_INT8_SQ;
     if (sq && p.M >= 2)
     {

@@ -147,7 +147,9 @@ __device__ __forceinline__ int dot_sq(const uint4& w, const uint4& x, int acc)
 // list as plain scalars, so that the kernarg preload puts them into SGPRs before the first instruction and the x / gamma / weight
 // loads go out without a scalar round trip to the kernarg segment.  The struct trails them for everything else (its copies of the
 // leading values are not read here); it is first touched behind the first weight tile's requests.  launch_inst fills both from
-// the one GemvArgs.
+// the one GemvArgs.  hot_w_up is the SwiGLU epilogue's second matrix; under a plain epilogue the head family (HEADK below) reads it
+// as the address of the first row that streams `nt` (GemvParams::resident_rows), so the lm_head launch needs no parameter the
+// layer launches do not have, and every other instance compiles to the code it had before the head options existed.
 template <int WT, int PK, int EK, int MB, int kNXV, int UU = tllm::kernels::gemv_detail::U>
 __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, const void* const hot_x, const void* const hot_gamma,
     const void* const hot_w_up, const int64_t hot_ldw, const int hot_N, const int hot_K, const int hot_Kp, const int hot_ngroups,
@@ -160,6 +162,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, cons
     constexpr int VEC = TR::VEC;
     constexpr bool SQ = TR::IS_SQ;
     constexpr bool SWIGLU = EK == EK_SWIGLU;
+    // the family the lm_head launch belongs to (fp16 weights, plain epilogue, one row): the only instances that carry the
+    // per-row-group cache policy and the arg-max partials of the fp32 epilogue.  Every other instance compiles without them.
+    constexpr bool HEADK = WT == W_FP16 && EK == EK_PLAIN && MB == 1;
     constexpr bool X_HALF = !(SQ && PK == PK_COPY); // the input activations are fp16 (else raw s8)
     using acc_t = typename std::conditional<SQ, int, float>::type;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -179,7 +184,14 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, cons
     // the last 16 bytes of the ROW, not of its stride: what lies between the two is the caller's (fp16 NaN bits there times a
     // zeroed activation would still be NaN)
     const int64_t last_vec = (int64_t) Kp * 16 / VEC - 16;
+    // Head family: the rows of `w` below hot_w_up (which a plain epilogue has no other use for: launch_inst puts
+    // w + resident_rows * ldw there, or null) load with the allocating policy (measured shorter on the 7B head; whether they are
+    // ever served from the Infinity Cache is open); the rows from it on stream `nt` like every other weight.  A row pair that straddles the
+    // boundary goes with its first row.  The group index is made a scalar first, so that the choice is a scalar branch.
+    bool resident = false;
     auto rows_of_group = [&](int g, const char* (&rowptr)[R]) {
+        if constexpr (HEADK)
+            resident = wbase + (int64_t) __builtin_amdgcn_readfirstlane(g) * R * hot_ldw < reinterpret_cast<const char*>(hot_w_up);
         if constexpr (SWIGLU)
         {
             const int o = g < hot_N ? g : hot_N - 1; // one output per group: gate row o, up row o
@@ -196,7 +208,11 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, cons
             }
         }
     };
-    auto load_tile = [&](const char* const (&rowptr)[R], int c, uint4 (&wv)[U][R]) {
+    // The cache policy of a weight tile is a compile-time property of the load sequence (`nt`: std::true_type streams past the
+    // temporal lines of L2 and the Infinity Cache, std::false_type allocates there).  Every instance streams `nt`; the head
+    // family alone (HEADK) also builds the allocating sequence and picks one of the two per row group - a scalar branch between
+    // two straight-line sequences, never a branch around a load.
+    auto load_tile_as = [&](const char* const (&rowptr)[R], int c, uint4 (&wv)[U][R], auto nt) {
 #pragma unroll
         for (int u = 0; u < U; ++u)
         {
@@ -207,8 +223,24 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, cons
             off = off < last_vec ? off : last_vec;
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                wv[u][r] = ld_nt16(rowptr[r] + off);
+            {
+                if constexpr (decltype(nt)::value)
+                    wv[u][r] = ld_nt16(rowptr[r] + off);
+                else
+                    wv[u][r] = *reinterpret_cast<const uint4*>(rowptr[r] + off);
+            }
         }
+    };
+    auto load_tile = [&](const char* const (&rowptr)[R], int c, uint4 (&wv)[U][R]) {
+        if constexpr (HEADK)
+        {
+            if (resident) // wave-uniform, scalar
+            {
+                load_tile_as(rowptr, c, wv, std::false_type());
+                return;
+            }
+        }
+        load_tile_as(rowptr, c, wv, std::true_type());
     };
 
     // ------------------------------------------------------------------ t = 0: every x-independent request
@@ -528,6 +560,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, cons
         }
 
     int gi_p = 0, ci_p = 0;
+    // head family, fp32 output: the running arg-max of the outputs this lane finishes (lanes 0 and 1 of a wave)
+    float am_v = -INFINITY;
+    int am_i = 0x7fffffff;
 
     auto step = [&](uint4 (&cur)[U][R], uint4 (&nxt)[U][R]) {
         const bool last = ci_p == tiles_per_group - 1;
@@ -659,7 +694,18 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, cons
             else if (p.out_dtype == DT_HALF)
                 reinterpret_cast<uint16_t*>(p.y)[oidx] = f2h(r0);
             else if (p.out_dtype == DT_FLOAT)
+            {
                 reinterpret_cast<float*>(p.y)[oidx] = r0;
+                if constexpr (HEADK)
+                {
+                    // the sampler's rule on the value just stored: greater wins, ties go to the lowest index
+                    if (r0 > am_v || (r0 == am_v && n < am_i))
+                    {
+                        am_v = r0;
+                        am_i = n;
+                    }
+                }
+            }
             else
                 reinterpret_cast<int32_t*>(p.y)[oidx] = f2i32_rni_sat(r0);
         }
@@ -672,6 +718,30 @@ __global__ __launch_bounds__(256) void gemv_kernel(const void* const hot_w, cons
             break;
         step(wv2, wv);
         ++t;
+    }
+
+    // Arg-max partials for the greedy step that follows the lm_head launch (GemvParams::argmax_part): one {value, index} pair per
+    // wave, written with a plain store - the kernel boundary orders it before the consumer.  A wave that finished no row writes
+    // the neutral pair, and the waves share out the slots beyond the grid, so that all kArgmaxPairs slots are defined whatever
+    // the grid (the launcher keeps the grid within them).
+    if constexpr (HEADK)
+    {
+        if (p.argmax_part) // uniform
+        {
+            const float ov = __shfl_xor(am_v, 1, 64);
+            const int oi = __shfl_xor(am_i, 1, 64);
+            if (ov > am_v || (ov == am_v && oi < am_i))
+            {
+                am_v = ov;
+                am_i = oi;
+            }
+            uint2* part = reinterpret_cast<uint2*>(p.argmax_part);
+            const int w = blockIdx.x * 4 + wid, nw = gridDim.x * 4;
+            if (lane == 0 && w < kArgmaxPairs)
+                part[w] = make_uint2(__float_as_uint(am_v), (uint32_t) am_i);
+            for (int j = w + nw * (1 + lane); j < kArgmaxPairs; j += nw * 64)
+                part[j] = make_uint2(__float_as_uint(-INFINITY), 0x7fffffffu);
+        }
     }
 }
 
@@ -698,7 +768,24 @@ int launch_inst(const GemvArgs& a, hipStream_t stream)
     // prologue over three row groups instead of two)
     const int fit = fit_blocks;
     const int want = EK == EK_SWIGLU ? fit : (fit < 2 ? fit : 2);
-    const int max_blocks = cus * (gemv_tune_blocks_per_cu > 0 ? gemv_tune_blocks_per_cu : want);
+    int max_blocks = cus * (gemv_tune_blocks_per_cu > 0 ? gemv_tune_blocks_per_cu : want);
+    // the lm_head options (GemvParams::resident_rows / argmax_part) exist in the head family only: anything else is an error,
+    // never a launch that quietly ignores them
+    constexpr bool HEADK = WT == W_FP16 && EK == EK_PLAIN && MB == 1;
+    const void* w_up = EK == EK_SWIGLU ? a.p.w_up : nullptr;
+    if (a.p.resident_rows > 0 || a.p.argmax_part)
+    {
+        if (!HEADK || (a.p.argmax_part && (a.p.out_dtype != DT_FLOAT || a.p.epi != EPI_NONE)))
+        {
+            set_error("gemv: resident_rows / argmax_part need fp16 weights, one row and a plain epilogue (arg-max: fp32 output)");
+            return -1;
+        }
+        // (the leading parameter a plain epilogue does not use carries the first `nt` row: see the kernel)
+        if (a.p.resident_rows > 0)
+            w_up = static_cast<const char*>(a.p.w) + (int64_t) (a.p.resident_rows < a.p.N ? a.p.resident_rows : a.p.N) * a.p.ldw;
+        if (a.p.argmax_part && max_blocks > kArgmaxPairs / 4) // one pair per wave (7B: 256 CUs x 2 = 512 workgroups, unchanged)
+            max_blocks = kArgmaxPairs / 4;
+    }
     if (blocks > max_blocks)
     {
         const int waves = max_blocks * 4;
@@ -706,7 +793,7 @@ int launch_inst(const GemvArgs& a, hipStream_t stream)
         blocks = (a.ngroups + 4 * groups_per_wave - 1) / (4 * groups_per_wave);
     }
     // the leading (preloaded) parameters are the struct's own fields: one source for every pointer and extent
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), smem, stream, a.p.w, a.p.x, a.p.gamma, a.p.w_up, a.p.ldw, a.p.N, a.p.K, a.Kp,
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), smem, stream, a.p.w, a.p.x, a.p.gamma, w_up, a.p.ldw, a.p.N, a.p.K, a.Kp,
         a.ngroups, a);
     return launch_util::check_launch("gemv");
 }

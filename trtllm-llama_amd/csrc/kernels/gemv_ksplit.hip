@@ -163,6 +163,8 @@ bool gemv_ksplit_applies(const GemvArgs& a)
     const GemvParams& p = a.p;
     if (p.M != 1 || p.pro != PRO_NONE || !(p.epi == EPI_NONE || p.epi == EPI_RESIDUAL) || p.x_pro_out || p.dyn_scale_out || p.per_token)
         return false;
+    if (p.resident_rows > 0 || p.argmax_part) // the lm_head options are the general kernel's
+        return false;
     if (!(p.out_dtype == DT_HALF || p.out_dtype == DT_FLOAT || (p.out_dtype == DT_INT32 && p.wtype == W_INT8_SQ)))
         return false;
     switch (p.wtype)

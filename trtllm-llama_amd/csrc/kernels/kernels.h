@@ -81,7 +81,19 @@ struct GemvParams
     const float* epi_scale = nullptr; // EPI_SWIGLU_QSTATIC: f32 [1]
     void* y = nullptr;
     int64_t ldy = 0; // elements
+    // The two options of the lm_head launch (fp16 weights, M = 1, no epilogue; any other call that sets one is refused):
+    //   resident_rows  rows [0, resident_rows) of W load with the allocating cache policy, the rows from it on stream non-temporally
+    //                  like every layer weight.  Measured on the 7B head: 2 us shorter from 75 % of the rows up; built so that the
+    //                  rows could stay in the Infinity Cache between steps, which the counters do NOT confirm - the cause is open
+    //                  (profiles/lm_head_residency.txt).  Rounded up to the kernel's row pair; > N means N.  0: the whole matrix
+    //                  streams.  Results do not depend on it.
+    //   argmax_part    fp32 output only: kArgmaxPairs pairs {float value, int32 index} - per wave of the grid the arg-max of the
+    //                  outputs it finished (greater value wins, ties go to the lowest index; {-inf, INT32_MAX} for none and for
+    //                  the slots beyond the grid).  launch_greedy_step reduces them instead of reading the logits again.
+    int32_t resident_rows = 0;
+    void* argmax_part = nullptr;
 };
+constexpr int kArgmaxPairs = 2048; // 16 KB: one pair per wave of 512 workgroups (two per CU of a 256-CU device)
 
 int launch_gemv(const GemvParams& p, hipStream_t stream);
 
@@ -449,6 +461,9 @@ struct GreedyParams
     void* x_out = nullptr;
     int32_t hidden = 0;
     uint32_t* step_epoch = nullptr; // optional device word, += 1 per call (tags of the in-launch hand-offs of the next step)
+    // optional (batch 1, nparts 1 only - anything else is refused): the kArgmaxPairs pairs the lm_head launch that produced
+    // `logits` left (GemvParams::argmax_part).  The kernel reduces them and does not read the logits; the token is the same.
+    const void* argmax_part = nullptr;
 };
 int launch_greedy_step(const GreedyParams& p, hipStream_t stream);
 

@@ -25,6 +25,13 @@ __device__ __forceinline__ void glds16(const void* gptr, uint32_t lds_byte)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(gptr), "s"(lds_byte) : "memory");
 }
 
+// glds16 with the nt policy (weight rows read once per token)
+__device__ __forceinline__ void glds16_nt(const void* gptr, uint32_t lds_byte)
+{
+    uint32_t m0_keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0" : "=&s"(m0_keep) : "v"(gptr), "s"(lds_byte) : "memory");
+}
+
 // the same from a wave-uniform base + a per-lane 32-bit offset
 __device__ __forceinline__ void glds16s(const char* base, uint32_t off, uint32_t lds_byte)
 {

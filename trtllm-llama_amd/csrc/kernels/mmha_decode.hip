@@ -33,6 +33,7 @@
 // Cache layout (bit-exact row A3, K/kvCacheUtils.h:114-170): [B, 2, H, Smax, Dh];
 //   element (b, kv, h, t, d) at ((b*2 + kv)*H + h)*Smax*Dh + t*Dh + d.
 #include "dev_utils.h"
+#include <type_traits>
 #include "kernels.h"
 #include "launch_util.h"
 #include <math.h>
@@ -165,35 +166,48 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
         for (int i = 0; i < NIT; ++i)
             sib[i] = (int64_t) (ci[min(t0 + i * NGRP + gid, Smax - 1)] - k_own) * seq_bytes;
     }
+    // The cache policy of the rows is a property of the load sequence (compile-time `nt`, as in gemv_kernel).  A row is read ONCE per
+    // step only by the linear cache with the whole K/V group in this tile (group == QT: one K/V head per query head, or a tile that
+    // covers its group): those rows stream `nt` and stay out of the temporal lines.  Everywhere else the same row is read again in the
+    // same launch - by the other tiles of a K/V group (the head-mapped QT = 1 form reads a group's rows `group` times and was chosen
+    // as the default BECAUSE those re-reads come from L2, profiles/gqa_attention.txt), by the sibling hypotheses of a beam, by the
+    // sequences that share a paged block - and keeps the allocating load.  `group` is a kernel argument: a scalar branch between two
+    // straight-line sequences, never a branch around a load.
+    auto load_rows = [&](auto nt) {
 #pragma unroll
-    for (int i = 0; i < NIT; ++i)
-    {
-        // no branches around the loads (a divergent `if` makes the compiler drain the queue at every one):
-        // out-of-range rows read the last row of the buffer and are masked out by `valid` below
-        const int t = min(t0 + i * NGRP + gid, Smax - 1);
-        int64_t off = ((int64_t) t * DH + li * 8) * ESZ;
-        if constexpr (BEAM)
-            off += sib[i];
-        const char *kp = kbase + off, *vp = vbase + off;
-        if constexpr (PAGED)
+        for (int i = 0; i < NIT; ++i)
         {
-            off = (((int64_t) kvh * p.tokens_per_block + (t & tpb_mask)) * DH + li * 8) * ESZ;
-            kp = kblk[i] + off;
-            vp = vblk[i] + off;
+            // no branches around the loads (a divergent `if` makes the compiler drain the queue at every one):
+            // out-of-range rows read the last row of the buffer and are masked out by `valid` below
+            const int t = min(t0 + i * NGRP + gid, Smax - 1);
+            int64_t off = ((int64_t) t * DH + li * 8) * ESZ;
+            if constexpr (BEAM)
+                off += sib[i];
+            const char *kp = kbase + off, *vp = vbase + off;
+            if constexpr (PAGED)
+            {
+                off = (((int64_t) kvh * p.tokens_per_block + (t & tpb_mask)) * DH + li * 8) * ESZ;
+                kp = kblk[i] + off;
+                vp = vblk[i] + off;
+            }
+            if constexpr (INT8KV || FP8KV)
+            {
+                const uint2 k8 = decltype(nt)::value ? ld_nt8(kp) : *reinterpret_cast<const uint2*>(kp);
+                const uint2 v8 = decltype(nt)::value ? ld_nt8(vp) : *reinterpret_cast<const uint2*>(vp);
+                kreg[i] = make_uint4(k8.x, k8.y, 0, 0);
+                vreg[i] = make_uint4(v8.x, v8.y, 0, 0);
+            }
+            else
+            {
+                kreg[i] = decltype(nt)::value ? ld_nt16(kp) : *reinterpret_cast<const uint4*>(kp);
+                vreg[i] = decltype(nt)::value ? ld_nt16(vp) : *reinterpret_cast<const uint4*>(vp);
+            }
         }
-        if constexpr (INT8KV || FP8KV)
-        {
-            const uint2 k8 = *reinterpret_cast<const uint2*>(kp);
-            const uint2 v8 = *reinterpret_cast<const uint2*>(vp);
-            kreg[i] = make_uint4(k8.x, k8.y, 0, 0);
-            vreg[i] = make_uint4(v8.x, v8.y, 0, 0);
-        }
-        else
-        {
-            kreg[i] = *reinterpret_cast<const uint4*>(kp);
-            vreg[i] = *reinterpret_cast<const uint4*>(vp);
-        }
-    }
+    };
+    if (CACHE == CACHE_LINEAR && group == QT) // uniform: a kernel argument
+        load_rows(std::true_type());
+    else
+        load_rows(std::false_type());
     // ---- 2. the new token's q, k, v, the step scalars, the padding-mask words and the RoPE row: all requested
     //         here, before anything is consumed (one memory round trip for the whole prologue)
     const uint16_t* qkv = reinterpret_cast<const uint16_t*>(p.qkv) + (int64_t) b * (H + 2 * Hkv) * DH; // q: H | k: Hkv | v: Hkv

@@ -453,8 +453,10 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
     {
         const int t = min(t0 + i * NGRP + gid, Smax - 1); // clamped, dropped by the validity mask: no branch around a load
         const int64_t off = ((int64_t) t * kDH + li * EPL) * ESZ;
-        kreg[i] = *reinterpret_cast<const uint4*>(kbase + off);
-        vreg[i] = *reinterpret_cast<const uint4*>(vbase + off);
+        // read once per step and never handed off inside the launch: `nt`, like the weights, so that the cache rows of 32 layers
+        // (268 MB at the bench context) do not push the resident lm_head rows out of the Infinity Cache
+        kreg[i] = ld_nt16(kbase + off);
+        vreg[i] = ld_nt16(vbase + off);
         // unconditional (a load inside a conditional block ends in a full s_waitcnt - here: behind the whole weight stream):
         // without a mask the word read is sequence_length[0], valid and ignored
         mk[i] = mask_ptr[has_mask ? t : 0];
@@ -801,7 +803,7 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
             {
 #pragma unroll
                 for (int u = 0; u < KCT; ++u)
-                    glds16(owb + (int64_t) (o_r0 + slot) * p.o_ldw + u * 1024 + lane * 16, wo_base + (slot * KCT + u) * 1024);
+                    glds16_nt(owb + (int64_t) (o_r0 + slot) * p.o_ldw + u * 1024 + lane * 16, wo_base + (slot * KCT + u) * 1024);
             }
         }
     }

@@ -242,10 +242,8 @@ int32_t tllm_attention_context(const tllm_attention_params_t* q, tllm_stream_t s
     return launch_context_attention(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
-int32_t tllm_gemv(const tllm_gemv_params_t* q, tllm_stream_t stream)
+static GemvParams gemv_params(const tllm_gemv_params_t* q)
 {
-    if (!q)
-        return 1;
     GemvParams p;
     p.wtype = q->wtype;
     p.pro = q->pro;
@@ -271,7 +269,65 @@ int32_t tllm_gemv(const tllm_gemv_params_t* q, tllm_stream_t stream)
     p.epi_scale = q->epi_scale;
     p.y = q->y;
     p.ldy = q->ldy;
+    return p;
+}
+
+int32_t tllm_gemv(const tllm_gemv_params_t* q, tllm_stream_t stream)
+{
+    if (!q)
+        return 1;
+    return launch_gemv(gemv_params(q), reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gemv_head(const tllm_gemv_params_t* q, int32_t resident_rows, void* argmax_part, tllm_stream_t stream)
+{
+    static_assert(TLLM_ARGMAX_PAIRS == kArgmaxPairs, "the header's constant is the kernels'");
+    if (!q || resident_rows < 0)
+    {
+        set_error("tllm_gemv_head: bad arguments");
+        return 1;
+    }
+    GemvParams p = gemv_params(q);
+    p.resident_rows = resident_rows;
+    p.argmax_part = argmax_part;
     return launch_gemv(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_greedy_step(const tllm_greedy_params_t* q, tllm_stream_t stream)
+{
+    if (!q || !q->logits || !q->cur_ids || !q->out_ids || !q->seq_len || q->batch < 1 || q->nparts < 1 || q->vocab_part < 1
+        || q->vocab < 1 || (int64_t) q->nparts * q->vocab_part < q->vocab
+        || (q->rope_row_out && (q->rope_half < 1 || q->rope_half > 960 || q->rope_table_len < 1))) // (the launcher checks the rest)
+    {
+        set_error("tllm_greedy_step: bad arguments");
+        return 1;
+    }
+    GreedyParams g;
+    g.logits = q->logits;
+    g.batch = q->batch;
+    g.vocab_part = q->vocab_part;
+    g.nparts = q->nparts;
+    g.vocab = q->vocab;
+    g.cur_ids = q->cur_ids;
+    g.out_ids = q->out_ids;
+    g.out_stride = q->out_stride;
+    g.seq_len = q->seq_len;
+    g.finished = q->finished;
+    g.end_id = q->end_id;
+    g.advance = q->advance;
+    g.rope_row_out = q->rope_row_out;
+    g.rope_pos_out = q->rope_pos_out;
+    g.rope_table = q->rope_table;
+    g.rope_half = q->rope_half;
+    g.rope_table_len = q->rope_table_len;
+    g.input_lengths = q->input_lengths;
+    g.max_input_len = q->max_input_len;
+    g.emb_table = q->emb_table;
+    g.x_out = q->x_out;
+    g.hidden = q->hidden;
+    g.step_epoch = q->step_epoch;
+    g.argmax_part = q->argmax_part;
+    return launch_greedy_step(g, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
 int32_t tllm_gemm(const tllm_gemm_params_t* q, tllm_stream_t stream)

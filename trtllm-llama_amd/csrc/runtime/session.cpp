@@ -616,6 +616,11 @@ int32_t tllm_session_time_kernel(tllm_session_t s, int32_t which, int32_t sweeps
     return rc;
 }
 
+int64_t tllm_session_greedy_partials_used(tllm_session_t s)
+{
+    return s ? s->greedy_partials_used : -1;
+}
+
 int32_t tllm_session_decode_form(tllm_session_t s)
 {
     if (!s || !s->B)

@@ -215,6 +215,21 @@ struct tllm_session
     uint64_t* fused_timing = nullptr; // session key fused_timeline = 1: stage clock of the fused launch, [Hr * 8][16] ticks
     bool fused_timeline = false;
     void* ctx_q8 = nullptr;
+    // The tail of a generation step ("The tail of the step").
+    // Rows [0, head_resident_rows) of this rank's lm_head shard load with the allocating cache policy in the one-row head launch,
+    // the rest streams `nt` (GemvParams::resident_rows): measured 2 us shorter at 7B, cause open - not shown to be Infinity Cache
+    // hits.  Session key head_resident_pct: -1 = the rule of decide_head_residency (setup), 0 .. 100 = that share of the rows.
+    int head_resident_cfg = -1;
+    int head_resident_rows = 0; // decided at setup
+    // Greedy, batch 1, one vocabulary part: the head launch leaves per-wave arg-max pairs and the greedy step reduces those
+    // instead of reading the logits again.  Session key greedy_partials = 0: the scan.
+    int greedy_partials_cfg = 1;
+    void* argmax_part = nullptr;     // kArgmaxPairs pairs
+    bool head_partials_live = false; // the last head launch wrote them and no sampler has run since
+    int64_t greedy_partials_used = 0; // greedy-step launches ENQUEUED with the pairs since setup (a captured step counts once per
+                                      // capture, not per replay): tllm_session_greedy_partials_used, so that a test sees a quiet fall-back
+    int gemv_resident_rows = 0;      // the two lm_head options of the next gemv() call (run_head sets and clears them)
+    void* gemv_argmax_part = nullptr;
     int end_id = -1;
     bool sampling_on = false;       // tllm_session_set_sampling: run_sampler launches kernels/sampling.hip with `sampling`
     tllm::kernels::SamplingParams sampling; // configuration fields only; pointers and shapes are filled per launch
@@ -289,6 +304,7 @@ struct tllm_session
     void drop_graph(); // the captured step no longer matches what an eager step would issue
     int alloc_buffers();
     int decide_decode_form();       // attention split layout, qkv_attn_fused / o_fused / mlp_fused_dec
+    void decide_head_residency();   // head_resident_rows
     int alloc_decode_form_buffers(); // what the forms decide_decode_form chose need
     // After a stream synchronisation: did a fused decode launch or a peer-to-peer collective of this session time out?  Fails
     // the call then, and withdraws the decode form / the transport that timed out.

@@ -64,6 +64,8 @@ int tllm_session::gemv(const Linear& L, int M, int pro, int epi, const void* xin
     p.y = y;
     p.ldy = ldy;
     p.x_pro_out = tap;
+    p.resident_rows = gemv_resident_rows;
+    p.argmax_part = gemv_argmax_part;
     if (up)
     {
         p.w_up = up->w;
@@ -136,9 +138,19 @@ int tllm_session::run_head(const void* h, int rows, hipStream_t st, bool normali
 {
     logit_rows = rows;
     gemv_cls = PC_GEMV_HEAD;
+    // one row: the launch of a batch-1 step (and of a single prompt) - the instance that takes the two lm_head options
+    const bool one_row = rows == 1 && head.wtype == W_FP16;
+    const bool greedy = beam == 1 && !(sampling_on && !sampling_is_greedy(sampling));
+    head_partials_live = one_row && greedy && B == 1 && tp == 1 && !force_comm && greedy_partials_cfg != 0 && argmax_part;
+    gemv_resident_rows = one_row ? head_resident_rows : 0;
+    gemv_argmax_part = head_partials_live ? argmax_part : nullptr;
     const int head_rc = gemv(head, rows, normalised ? PRO_NONE : PRO_RMSNORM, EPI_NONE, h, hidden, lnf, nullptr, nullptr, nullptr,
         logits_local, Vr, DT_FLOAT, nullptr, st);
+    gemv_resident_rows = 0;
+    gemv_argmax_part = nullptr;
     gemv_cls = PC_GEMV_LAYER;
+    if (head_rc)
+        head_partials_live = false;
     RUN(head_rc);
     if ((tp > 1 || force_comm) && !no_comm)
     {
@@ -156,6 +168,9 @@ int tllm_session::run_head(const void* h, int rows, hipStream_t st, bool normali
 
 int tllm_session::run_sampler(int advance, hipStream_t st)
 {
+    // the partials belong to the logits of the head launch just before this sampler, and to no later one
+    const bool partials = head_partials_live;
+    head_partials_live = false;
     if (beam > 1)
     {
         BeamParams bp;
@@ -221,6 +236,11 @@ int tllm_session::run_sampler(int advance, hipStream_t st)
         sp.history_stride = Smax;
         sp.g_base = max_in;
         return timed(PC_OTHER, st, [&] { return launch_sampling_step(sp, st) ? 1 : 0; });
+    }
+    if (partials && B == 1 && tp == 1 && !force_comm) // every other shape scans the logits
+    {
+        gp.argmax_part = argmax_part;
+        ++greedy_partials_used;
     }
     return timed(PC_OTHER, st, [&] { return launch_greedy_step(gp, st) ? 1 : 0; });
 }

@@ -2,6 +2,7 @@
 // layer runs on them.  check_comm, the only code that withdraws that decision again, sits next to it.
 #include "session.h"
 #include <algorithm>
+#include <string>
 
 using namespace tllm;
 using namespace tllm::kernels;
@@ -212,8 +213,52 @@ int tllm_session::decide_decode_form()
     return 0;
 }
 
+// HIP reports no last-level cache size (l2CacheSize is one XCD's L2, or 0), so the Infinity Cache is taken from the architecture:
+// 256 MiB on gfx942 / gfx950, none known otherwise - and then nothing is made resident.
+static int64_t infinity_cache_bytes()
+{
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
+        return 0;
+    const std::string arch = prop.gcnArchName;
+    return (arch.rfind("gfx950", 0) == 0 || arch.rfind("gfx942", 0) == 0) ? (int64_t) 256 << 20 : 0;
+}
+
+// How many rows of the lm_head shard the one-row head launch loads with the allocating policy ("The tail
+// of the step").  What is measured (profiles/lm_head_residency.txt, one run per setting): the 7B head launch takes 38.4 - 38.9 us
+// from 75 % of the rows up against 40.5 - 41.0 us at 0 %, and its FETCH_SIZE is the whole table at every setting - so the gain
+// is kept on its own A/B and NOT explained: Infinity Cache hits are not shown.  The rule below is the one the mechanism would
+// want, and for 7B it lands in the measured range (31744 of 32000 rows): the cache of the architecture less 8 MiB for what else
+// allocates in a step (audited in DESIGN.md), whole shard if it fits, else as many rows as do; under 64 MiB of such rows the launch
+// stays exactly the streaming one.  Both figures are assumptions of that unconfirmed mechanism, not tuned values.
+void tllm_session::decide_head_residency()
+{
+    constexpr int64_t kStepAllocBytes = (int64_t) 8 << 20, kMinResidentBytes = (int64_t) 64 << 20;
+    head_resident_rows = 0;
+    if (head.wtype != W_FP16 || !head.w || head.ldw <= 0)
+        return;
+    if (head_resident_cfg >= 0)
+    {
+        head_resident_rows = (int) ((int64_t) head.N * std::min(head_resident_cfg, 100) / 100);
+        return;
+    }
+    const int64_t budget = infinity_cache_bytes() - kStepAllocBytes;
+    const int64_t rows = budget <= 0 ? 0 : std::min<int64_t>(head.N, budget / head.ldw);
+    if (rows * head.ldw >= kMinResidentBytes)
+        head_resident_rows = (int) rows;
+}
+
 int tllm_session::alloc_decode_form_buffers()
 {
+    argmax_part = nullptr;
+    head_partials_live = false;
+    greedy_partials_used = 0;
+    if (B == 1 && beam == 1 && tp == 1 && greedy_partials_cfg != 0)
+    {
+        RUN(dalloc(&argmax_part, (size_t) kArgmaxPairs * 8));
+        HIP_OK(hipMemset(argmax_part, 0, (size_t) kArgmaxPairs * 8));
+    }
     attn_tickets = nullptr;
     ctx_q8 = nullptr;
     fused_xchg = nullptr;
@@ -356,6 +401,7 @@ int32_t tllm_session_setup_beam(tllm_session_t s, int32_t batch_size, int32_t be
     s->Smax = max_input_len + max_new_tokens; // generation.py:450-461
     RUN(s->alloc_buffers());
     RUN(s->decide_decode_form());
+    s->decide_head_residency();
     return s->alloc_decode_form_buffers();
 }
 

@@ -164,6 +164,8 @@ tllm_session_t tllm_session_create(const char* config_text)
     s->fuse_o_cfg = geti("fuse_o_projection", -1);
     s->fuse_mlp_cfg = geti("fuse_mlp", 0);
     s->fused_max_spins = geti("fused_max_spins", -1);
+    s->head_resident_cfg = geti("head_resident_pct", -1);
+    s->greedy_partials_cfg = geti("greedy_partials", 1);
     s->dual_mlp_cfg = geti("dual_mlp_gemm", -1);
     s->score_chunk_cfg = geti("score_chunk_rows", 0);
     s->fused_timeline = geti("fused_timeline", 0) != 0;

@@ -79,6 +79,8 @@ def _lib():
     lib.tllm_session_fused_retries.restype = c.c_int32
     lib.tllm_session_decode_form.argtypes = [c.c_void_p]
     lib.tllm_session_decode_form.restype = c.c_int32
+    lib.tllm_session_greedy_partials_used.argtypes = [c.c_void_p]
+    lib.tllm_session_greedy_partials_used.restype = c.c_int64
     lib.tllm_session_destroy.argtypes = [c.c_void_p]
     lib.tllm_session_destroy.restype = None
     lib.tllm_session_set_sampling.argtypes = [c.c_void_p, c.POINTER(SamplingConfigC)]
@@ -302,6 +304,10 @@ class NativeSession:
     def decode_form(self) -> int:
         """bit 0: QKV projection + attention in one launch, bit 1: + the O-projection stage, bit 2: the gated MLP in one launch"""
         return int(_lib().tllm_session_decode_form(self._h))
+
+    def greedy_partials_used(self) -> int:
+        """greedy-step launches enqueued with the lm_head launch's arg-max pairs since setup (a captured step counts once)"""
+        return int(_lib().tllm_session_greedy_partials_used(self._h))
 
     def time_kernel(self, which: str, sweeps: int = 4, stream: int = 0):
         """(average microseconds per launch, launches) of one per-layer kernel launched back to back over all layers."""
