@@ -79,16 +79,15 @@ class Call:
         return rc
 
 
-def decode_case(kind, H, Hkv, Dh, L, seed, smax=None):
-    """The padded second prompt of test_mmha_decode_vs_oracle, on an [B, 2, Hkv, Smax, Dh] cache."""
+def decode_case(kind, H, Hkv, Dh, L, seed, smax=None, B=2):
+    """The padded second prompt of test_mmha_decode_vs_oracle, on an [B, 2, Hkv, Smax, Dh] cache (B = 1: the first prompt alone)."""
     r = np.random.default_rng(seed)
-    B = 2
     if smax is None:
         smax = 1152 if L < 1152 else (2048 if L < 2048 else 4096)
     max_in = max(L - 3, 1) if L > 4 else L
-    in_len = [max_in, max(max_in // 2, 1)]
+    in_len = [max_in, max(max_in // 2, 1)][:B]
     masked = np.zeros((B, smax), dtype=np.int32)
-    masked[1, in_len[1]:max_in] = 1
+    masked[1:, in_len[-1]:max_in] = 1
     past = r.standard_normal((B, 2, Hkv, smax, Dh)).astype(np.float32)
     past[:, :, :, L:] = 0
     cache_np = store(kind, past)
@@ -430,6 +429,39 @@ def test_decode_with_hkv_equal_to_h_is_the_plugin_bit_for_bit(lib, kind, hkv, H,
     out_b = c.set('out', torch.empty((B, H * Dh), dtype=torch.float16, device='cuda'))
     assert c.run() == 0, capi.last_error()
     assert torch.equal(out_a[:, 0], out_b) and torch.equal(cache_a, cache_b)
+
+
+# capacity -> (tchunk, nsplit, in_launch_merge) at head size 128: the last cache that takes 12 rows per lane group (8 splits), the
+# first that takes 16; the last that merges inside the launch (16 splits of 16 rows), the first on the finest split + combine launch
+PLAN_EDGES = {1536: (192, 8, 1), 1537: (256, 7, 1), 4096: (256, 16, 1), 4097: (64, 65, 0)}
+
+
+@pytest.mark.parametrize('smax', sorted(PLAN_EDGES))
+def test_plugin_and_entry_point_run_one_plan_at_the_rule_boundaries(lib, smax):
+    """rows_per_group left open, the cache two slots short of full: the GPTAttention enqueue and tllm_attention_decode resolve the
+    same split-KV plan - bit-identical context and appended row - and both stay within the decode tolerance of the oracle."""
+    kind, H, Dh, L = 'fp16', 2, 128, smax - 2
+    B, smax, max_in, in_len, masked, cache_np, qkv = decode_case(kind, H, H, Dh, L, 1300 + smax, smax, B=1)
+    ref, ref_cache = decode_reference(kind, qkv, cache_np, L, in_len, max_in, masked, H, H, Dh)
+    cache_a = torch.from_numpy(cache_np.copy()).cuda()
+    out_a = run_attention_plugin(attention_plugin(H, Dh, 0), qkv[:, None].contiguous(), cache_a, [L] * B, L, False, masked, in_len,
+                                 max_in, smax, None)
+    c = Call(lib, kind, B, H, H, Dh, smax, max_input_len=max_in, rows_per_group=0)
+    c.p.timestep = L
+    c.set('qkv', qkv)
+    cache_b = c.set('kv_cache', torch.from_numpy(cache_np.copy()).cuda())
+    c.set('sequence_length', dev_i32([L] * B))
+    c.set('input_lengths', dev_i32(in_len))
+    c.set('masked_tokens', dev_i32(masked))
+    out_b = c.set('out', torch.full((B, H * Dh), float('nan'), dtype=torch.float16, device='cuda'))
+    lay = c.layout()
+    assert (lay[0], lay[1], lay[3]) == PLAN_EDGES[smax], lay
+    assert c.run() == 0, capi.last_error()
+    assert torch.equal(out_a[:, 0], out_b) and torch.equal(cache_a, cache_b)
+    what = f'capacity {smax} L={L} layout={lay}'
+    print(f'{what}: max |ctx - ref| = {np.abs(as_f32(out_b) - ref).max():.3e}')
+    np.testing.assert_allclose(as_f32(out_b), ref, atol=2e-3, rtol=0, err_msg=what)
+    check_appended_rows(kind, cache_b.cpu().numpy(), ref_cache, cache_np, L, what)
 
 
 @pytest.mark.parametrize('kind', ['fp16', 'int8'])

@@ -154,7 +154,7 @@ __device__ __forceinline__ uint4 rope_kv_finish(const ContextAttnParams& p, int 
     }
     if (s < p.max_seq_len && r.has_kv)
     {
-        const int esz = (p.int8_kv || p.fp8_kv) ? 1 : 2;
+        const int esz = p.kv_dtype == DT_HALF ? 2 : 1;
         char* kc = reinterpret_cast<char*>(p.kv_cache)
             + (((int64_t) (b * p.cache_seq_stride * 2 + 0) * Hkv + h) * p.max_seq_len + s) * DH * esz + li * 8 * esz;
         char* vc = reinterpret_cast<char*>(p.kv_cache)
@@ -174,13 +174,13 @@ __device__ __forceinline__ uint4 rope_kv_finish(const ContextAttnParams& p, int 
         }
         if (!mapped)
             return v4;
-        if (p.int8_kv)
+        if (p.kv_dtype == DT_INT8)
         {
             const float sc = p.kv_scale_orig_quant[0];
             *reinterpret_cast<uint2*>(kc) = quant8(k4, sc);
             *reinterpret_cast<uint2*>(vc) = quant8(v4, sc);
         }
-        else if (p.fp8_kv)
+        else if (p.kv_dtype == DT_FP8)
         {
             const float sc = p.kv_scale_orig_quant[0];
             *reinterpret_cast<uint2*>(kc) = quant8_fp8(k4, sc);
@@ -809,17 +809,8 @@ int launch_context_attention(const ContextAttnParams& pin, hipStream_t stream)
         set_error("context attention: bad rotary configuration");
         return -1;
     }
-    if (p.int8_kv && !p.kv_scale_orig_quant)
-    {
-        set_error("context attention: int8 KV cache needs kv_scale_orig_quant");
+    if (launch_util::check_kv_dtype("context attention", p.kv_dtype, p.kv_scale_orig_quant != nullptr))
         return -1;
-    }
-    if (p.fp8_kv && (p.int8_kv || !p.kv_scale_orig_quant))
-    {
-        set_error(p.int8_kv ? "context attention: int8_kv and fp8_kv are exclusive"
-                            : "context attention: fp8 KV cache needs kv_scale_orig_quant");
-        return -1;
-    }
     if (p.block_pointers)
     {
         const int t = p.tokens_per_block;

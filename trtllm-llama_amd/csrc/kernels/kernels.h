@@ -147,9 +147,8 @@ struct MmhaParams
     int32_t batch = 0, num_heads = 0, head_size = 0;
     int32_t rotary_dim = 0, neox = 1;
     float inv_sqrt_dh = 1.f;
-    int32_t int8_kv = 0;
-    int32_t fp8_kv = 0;        // OCP E4M3 cache (one byte per element, the two scales of int8_kv); exclusive with int8_kv
-    int32_t max_seq_len = 0;   // cache capacity Smax
+    int32_t kv_dtype = DT_HALF; // cache element: DT_HALF, DT_INT8 or DT_FP8 (one byte per element, the two scales below)
+    int32_t max_seq_len = 0;    // cache capacity Smax
     int32_t max_input_len = 0; // padded prompt length (RoPE position = timestep - (max_input_len - input_len[b]))
     const void* qkv = nullptr; // fp16 [B, 3*H*Dh] (q | k | v)
     void* kv_cache = nullptr;  // [B, 2, H, Smax, Dh] fp16, s8 or e4m3
@@ -163,7 +162,8 @@ struct MmhaParams
     int32_t rope_table_len = 0;
     const float* rope_row = nullptr; // optional f32 [B, rotary_dim/2, 2]: this step's cos/sin row, prepared on the
                                      // device by the sampler (removes the length -> position -> table dependency)
-    int32_t rows_per_group = 0;      // cache rows per lane group and split: 4 (finest split), 12 or 16; 0 = chosen by the launcher
+    int32_t rows_per_group = 0;      // cache rows per lane group and split: 4 (finest split), 12 or 16 - MmhaPlan::rows_per_group,
+                                     // set by mmha_bind_workspace; the launcher refuses 0
     // beam search (MM/...Template.h:1137-1146, :1624-1631): `batch` counts batch x beam sequences; sequence bb = b * beam_width
     // + k reads the K/V of timestep t from the cache rows of sequence b * beam_width + cache_indirection[bb, t]
     const int32_t* cache_indirection = nullptr; // int32 [batch, max_seq_len]
@@ -180,7 +180,7 @@ struct MmhaParams
     const float* tail_quant_scale = nullptr; // f32 [1]: SmoothQuant static activation scale of the O-projection's input
     void* tail_out_q8 = nullptr;             // s8 [B, H*Dh]
     void* out = nullptr;       // fp16 [B, H*Dh]
-    void* workspace = nullptr; // mmha_workspace_size bytes
+    void* workspace = nullptr; // the partials: MmhaPlan::ticket_bytes into the caller's workspace (mmha_bind_workspace)
     // grouped-query attention: Hkv K/V heads, 1 <= Hkv <= H, H % Hkv == 0, query head h reads K/V head h / (H / Hkv); 0 = num_heads.
     // With Hkv != H:  qkv is fp16 [B, (H + 2*Hkv)*Dh] (q: H*Dh | k: Hkv*Dh | v: Hkv*Dh), the cache [B, 2, Hkv, Smax, Dh], paged
     // blocks [Hkv, tokens_per_block, Dh]; tickets, workspace and `out` stay per QUERY head.
@@ -193,16 +193,34 @@ struct MmhaParams
 int mmha_default_q_tile(int32_t num_heads, int32_t num_kv_heads);
 // num_kv_heads / q_heads_per_workgroup of p resolved (0 -> num_heads / the default tile) and checked; non-zero: refused, error set
 int mmha_resolve_grouping(MmhaParams& p);
-// Split geometry for a given rows_per_group: timesteps per split, number of splits for max_seq_len, and the byte
-// offset of the partial outputs inside the workspace ({max,sum} float2 [B,H,ns] first, then out f32 [B,H,ns,Dh]).
-int mmha_split_layout(int32_t head_size, int32_t max_seq_len, int32_t rows_per_group, int32_t batch, int32_t num_heads,
-    int32_t* tchunk, int32_t* nsplit, size_t* out_offset);
-size_t mmha_workspace_size(int32_t batch, int32_t num_heads, int32_t head_size, int32_t max_seq_len);
-size_t mmha_ticket_bytes(int32_t batch, int32_t num_heads); // the merge tickets at the head of a plugin's workspace
+// The split-KV plan of a decode attention launch - the geometry, the launch rule and the workspace layout, stated once:
+//   tchunk = (2048 / head_size) * rows_per_group cache slots per split (4 waves x 64 / (head_size / 8) lane groups x rows),
+//   nsplit = ceil(max_seq_len / tchunk) splits per (sequence, head), at most kMmhaMaxSplits;
+//   rows requested as 0: 16 while that needs <= kMmhaTailSlots splits - 12 while those need <= 8 (7 x 32 instead of 5 x 32
+//   workgroups at the 1024-token bench context) - with the merge inside the launch (mmha_decode.hip step 6), else the finest
+//   split, 4, with the combine launch;  4 / 12 / 16 requested: the in-launch merge iff nsplit <= kMmhaTailSlots;
+//   force_combine: the combine launch whatever the split count.
+// Workspace: the merge tickets uint32 [B, H] | {max, sum} float2 [B, H, nsplit] | out f32 [B, H, nsplit, Dh], the first two
+// rounded up to 256 bytes; workspace_bytes covers the finest split, so one allocation serves every plan of the shape.
+// A head size whose cache row is not a whole fraction of a wave (64 % (head_size / 8) != 0) or rows other than 0 / 4 / 12 / 16
+// give the empty plan (rows_per_group 0, workspace_bytes 0).
+constexpr int kMmhaTailSlots = 16;  // partials the in-launch merge takes
+constexpr int kMmhaMaxSplits = 256; // partials the combine launch takes (one per thread)
+struct MmhaPlan
+{
+    int32_t rows_per_group = 0, tchunk = 0, nsplit = 0;
+    bool in_launch_merge = false;
+    size_t ticket_bytes = 0;    // the tickets at the head of the workspace = the offset of {max, sum}
+    size_t ml_bytes = 0;        // {max, sum} of this plan's split = the offset of `out` behind them
+    size_t workspace_bytes = 0;
+};
+MmhaPlan mmha_plan(int32_t head_size, int32_t max_seq_len, int32_t batch, int32_t num_heads, int32_t rows_per_group = 0,
+    bool force_combine = false);
+// p.rows_per_group, p.tail_tickets and p.workspace from a plan (p.batch and p.num_heads set).  The tickets must be zero before
+// the FIRST launch on a workspace (every launch re-arms them): reset_tickets enqueues that memset - the plugins per enqueue; the
+// session zeroes its workspace at setup and with every prompt instead.
+int mmha_bind_workspace(MmhaParams& p, const MmhaPlan& plan, void* workspace, bool reset_tickets, hipStream_t stream);
 int launch_mmha(const MmhaParams& p, hipStream_t stream);
-// The split-merge tickets at the head of the workspace must be zero before the FIRST launch on it (every launch
-// re-arms them): plugins call this per enqueue, the session once per setup.
-int mmha_reset_workspace(void* workspace, int32_t batch, int32_t num_heads, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // Decode step, batch 1: the QKV projection (SmoothQuant int8, RMSNorm + quantiser prologue) of head h, RoPE, the cache append
@@ -219,12 +237,13 @@ struct FusedQkvAttnParams
     int64_t ldw = 0;         // bytes
     const void* scale_col = nullptr; // SmoothQuant: f32 [3 * H * Dh] (per_channel) or [1]; weight-only: fp16 [3 * H * Dh]
     int32_t per_channel = 0;
-    int32_t woq8 = 0; // 1: weight-only int8 rows (u8 = q + 128) against the normalised fp16 row; no quantiser
-    int32_t woq4 = 0;   // 1 (r06): weight-only int4 rows (ldw = K / 2 bytes, fp16 scales) against the normalised fp16 row; two-stage form
-    int32_t fp16_w = 0; // 1 (r06): fp16 rows (ldw = 2 K bytes, no scales) against the normalised fp16 row; no quantiser, no O-projection stage
+    // W_INT8_SQ; W_INT8_WOQ: weight-only int8 rows (u8 = q + 128) against the normalised fp16 row, no quantiser; W_INT4_WOQ (r06):
+    // int4 rows (ldw = K / 2 bytes, fp16 scales), two-stage form; W_FP16 (r06): fp16 rows (ldw = 2 K bytes, no scales), no quantiser,
+    // no O-projection stage
+    int32_t wtype = W_INT8_SQ;
     const float* act_quant_scale = nullptr;   // f32 [1]: static quantiser of the normalised row; null -> per-token (amax / 127)
     const float* act_dequant_scale = nullptr; // f32 [1]: the static activation scale of the dequantisation
-    int32_t int8_kv = 0, max_seq_len = 0;
+    int32_t kv_dtype = DT_HALF, max_seq_len = 0; // DT_HALF or DT_INT8 (no E4M3 instance)
     float inv_sqrt_dh = 1.f;
     void* kv_cache = nullptr;                 // [2, H, Smax, Dh] fp16 or s8 (batch 1)
     const int32_t* sequence_length = nullptr; // [1] device: slots in use
@@ -257,13 +276,13 @@ struct FusedQkvAttnParams
     void* x_out = nullptr;                 // fp16 [o_n]: may be x itself (every workgroup has consumed x long before)
 };
 size_t qkv_attn_fused_xchg_bytes(int32_t num_heads);
-bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t weight_kind = 0,
+bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t wtype = W_INT8_SQ,
     int32_t num_kv_heads = 0);
-// (woq8 / o_stage decide the instance and its dynamic LDS: the residency check - occupancy query x CUs of the current device >= grid
+// (wtype / o_stage decide the instance and its dynamic LDS: the residency check - occupancy query x CUs of the current device >= grid
 // - is made for exactly the launch that will run)
-// weight_kind: 0 SmoothQuant int8, 1 weight-only int8, 2 fp16, 3 weight-only int4
-bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int32_t max_seq_len, int32_t int8_kv, int32_t weight_kind = 0,
-    int32_t o_stage = 0, int32_t num_kv_heads = 0); // num_kv_heads != num_heads (and != 0): not served
+// kv_dtype DT_FP8, num_kv_heads != num_heads (and != 0): not served
+bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int32_t max_seq_len, int32_t kv_dtype,
+    int32_t wtype = W_INT8_SQ, int32_t o_stage = 0, int32_t num_kv_heads = 0);
 int launch_qkv_attn_fused(const FusedQkvAttnParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
@@ -317,8 +336,7 @@ struct ContextAttnParams
     int32_t batch = 0, seq = 0, num_heads = 0, head_size = 0;
     int32_t rotary_dim = 0, neox = 1;
     float inv_sqrt_dh = 1.f;
-    int32_t int8_kv = 0, max_seq_len = 0;
-    int32_t fp8_kv = 0; // OCP E4M3 cache (kv_scale_orig_quant as for int8_kv); exclusive with int8_kv
+    int32_t kv_dtype = DT_HALF, max_seq_len = 0; // DT_HALF, DT_INT8 or DT_FP8 (the one-byte types with kv_scale_orig_quant)
     void* qkv = nullptr;      // fp16 [B, S, 3*H*Dh]; q,k rewritten in place with RoPE applied (reference :1401-1403)
     void* kv_cache = nullptr; // [B, 2, H, Smax, Dh]
     const int32_t* input_lengths = nullptr; // [B]

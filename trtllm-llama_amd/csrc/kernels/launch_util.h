@@ -1,7 +1,7 @@
 // Host-side launch state keyed by DEVICE (a process may hold sessions on devices with different CU counts, and a
 // function attribute raised on one device says nothing about another): CU count, "dynamic-LDS attribute raised for this kernel on
 // this device", occupancy of an instance.  Header-only; the statics of an inline function are one object per shared library.
-// And the check every launcher ends with.
+// And the checks the launchers share: the launch status every one ends with, the KV cache element type of the attention ones.
 #pragma once
 #include "kernels.h"
 #include <hip/hip_runtime.h>
@@ -79,6 +79,21 @@ inline int check_launch(const char* what)
     if (e != hipSuccess)
     {
         set_error("%s launch failed: %s", what, hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+// the KV cache element of a launch: DT_HALF, DT_INT8 or DT_FP8, the one-byte types with the scales the launch reads
+inline int check_kv_dtype(const char* what, int32_t kv_dtype, bool has_scales)
+{
+    if (kv_dtype != DT_HALF && kv_dtype != DT_INT8 && kv_dtype != DT_FP8)
+    {
+        set_error("%s: kv_dtype %d is not DT_HALF, DT_INT8 or DT_FP8", what, kv_dtype);
+        return -1;
+    }
+    if (kv_dtype != DT_HALF && !has_scales)
+    {
+        set_error("%s: %s KV cache needs its scales", what, kv_dtype == DT_INT8 ? "int8" : "fp8");
         return -1;
     }
     return 0;

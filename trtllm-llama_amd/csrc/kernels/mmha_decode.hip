@@ -48,15 +48,21 @@ namespace
 {
 
 constexpr int kWaves = 4; // 256-thread workgroups
-constexpr int kTailSlots = 16; // partials the in-launch merge takes (MmhaParams::tail_tickets)
+constexpr int kTailSlots = kMmhaTailSlots; // partials the in-launch merge takes (MmhaParams::tail_tickets)
+
+// lane groups per workgroup: head_size / 8 lanes own a cache row (8 elements per lane), 64 / that rows per wave instruction
+constexpr int mmha_lane_groups(int head_size)
+{
+    return kWaves * (64 / (head_size / 8));
+}
 
 template <int DH, int NIT>
 struct MmhaGeom
 {
-    static constexpr int LPR = DH / 8;        // lanes per cache row (8 elements per lane)
-    static constexpr int RPW = 64 / LPR;      // rows per wave instruction = lane groups per wave
-    static constexpr int NGRP = kWaves * RPW; // lane groups per workgroup
-    static constexpr int TCHUNK = NGRP * NIT; // timesteps per workgroup (NIT rows of K and of V per lane group)
+    static constexpr int LPR = DH / 8;        // lanes per cache row
+    static constexpr int RPW = 64 / LPR;      // lane groups per wave
+    static constexpr int NGRP = mmha_lane_groups(DH);
+    static constexpr int TCHUNK = NGRP * NIT; // timesteps per workgroup (NIT rows of K and of V per lane group): MmhaPlan::tchunk
 };
 
 // 8 cached int8 -> 8 fp16: fp16(float(q) * s)   (…Utils.h:2358-2365)
@@ -634,127 +640,110 @@ __global__ __launch_bounds__(256) void mmha_combine_kernel(const MmhaParams p, c
     }
 }
 
-template <int DH, int NIT, int QT>
-int launch_qt(const MmhaParams& p, hipStream_t stream)
+// the cache mode of the launch: paged, through the beam indirection, or the sequence's own rows
+template <int DH, int NIT, int QT, int KV>
+void launch_partial(const MmhaParams& p, const MmhaPlan& plan, float2* ws_ml, float* ws_o, hipStream_t stream)
 {
-    using G = MmhaGeom<DH, NIT>;
-    const int ns = (p.max_seq_len + G::TCHUNK - 1) / G::TCHUNK;
-    if (ns > 256)
-    {
-        set_error("mmha: max_seq_len %d needs more than 256 splits", p.max_seq_len);
-        return -1;
-    }
-    if (p.tail_tickets && (ns > kTailSlots || (p.tail_out_q8 && !p.tail_quant_scale)))
-    {
-        set_error("mmha: the in-launch merge takes at most %d splits (got %d) and a scale with its int8 output", kTailSlots, ns);
-        return -1;
-    }
-    char* ws = reinterpret_cast<char*>(p.workspace);
-    float2* ws_ml = reinterpret_cast<float2*>(ws);
-    const size_t ml_bytes = ((size_t) p.batch * p.num_heads * ns * sizeof(float2) + 255) / 256 * 256;
-    float* ws_o = reinterpret_cast<float*>(ws + ml_bytes);
-    dim3 grid(ns, p.num_heads / QT, p.batch);
+    const dim3 grid(plan.nsplit, p.num_heads / QT, p.batch);
     const int group = p.num_heads / p.num_kv_heads;
     const uint32_t kv_magic = (uint32_t) (((1u << 24) + group - 1) / group);
-    const bool beam = p.beam_width > 1 && p.cache_indirection;
-    const int mode = p.block_pointers ? CACHE_PAGED : (beam ? CACHE_BEAM : CACHE_LINEAR);
-#define TLLM_MMHA_LAUNCH(ELEM, MODE)                                                                                   \
-    hipLaunchKernelGGL((mmha_partial_kernel<DH, NIT, ELEM, MODE, QT>), grid, dim3(256), 0, stream, p, ws_ml, ws_o, ns, kv_magic, group)
-    if (p.int8_kv)
-    {
-        if (mode == CACHE_PAGED)
-            TLLM_MMHA_LAUNCH(KV_I8, CACHE_PAGED);
-        else if (mode == CACHE_BEAM)
-            TLLM_MMHA_LAUNCH(KV_I8, CACHE_BEAM);
-        else
-            TLLM_MMHA_LAUNCH(KV_I8, CACHE_LINEAR);
-    }
-    else if (p.fp8_kv)
-    {
-        if (mode == CACHE_PAGED)
-            TLLM_MMHA_LAUNCH(KV_F8, CACHE_PAGED);
-        else if (mode == CACHE_BEAM)
-            TLLM_MMHA_LAUNCH(KV_F8, CACHE_BEAM);
-        else
-            TLLM_MMHA_LAUNCH(KV_F8, CACHE_LINEAR);
-    }
+#define TLLM_MMHA_LAUNCH(MODE)                                                                                         \
+    hipLaunchKernelGGL((mmha_partial_kernel<DH, NIT, KV, MODE, QT>), grid, dim3(256), 0, stream, p, ws_ml, ws_o, plan.nsplit, kv_magic, group)
+    if (p.block_pointers)
+        TLLM_MMHA_LAUNCH(CACHE_PAGED);
+    else if (p.beam_width > 1 && p.cache_indirection)
+        TLLM_MMHA_LAUNCH(CACHE_BEAM);
     else
-    {
-        if (mode == CACHE_PAGED)
-            TLLM_MMHA_LAUNCH(KV_F16, CACHE_PAGED);
-        else if (mode == CACHE_BEAM)
-            TLLM_MMHA_LAUNCH(KV_F16, CACHE_BEAM);
-        else
-            TLLM_MMHA_LAUNCH(KV_F16, CACHE_LINEAR);
-    }
+        TLLM_MMHA_LAUNCH(CACHE_LINEAR);
 #undef TLLM_MMHA_LAUNCH
+}
+
+template <int DH, int NIT, int QT>
+int launch_qt(const MmhaParams& p, const MmhaPlan& plan, hipStream_t stream)
+{
+    float2* ws_ml = reinterpret_cast<float2*>(p.workspace);
+    float* ws_o = reinterpret_cast<float*>(reinterpret_cast<char*>(p.workspace) + plan.ml_bytes);
+    switch (p.kv_dtype) // checked by launch_mmha
+    {
+    case DT_INT8: launch_partial<DH, NIT, QT, KV_I8>(p, plan, ws_ml, ws_o, stream); break;
+    case DT_FP8: launch_partial<DH, NIT, QT, KV_F8>(p, plan, ws_ml, ws_o, stream); break;
+    default: launch_partial<DH, NIT, QT, KV_F16>(p, plan, ws_ml, ws_o, stream);
+    }
     if (!p.tail_tickets)
-        hipLaunchKernelGGL((mmha_combine_kernel<DH, NIT>), dim3(p.num_heads, p.batch), dim3(256), 0, stream, p, ws_ml, ws_o, ns);
+        hipLaunchKernelGGL((mmha_combine_kernel<DH, NIT>), dim3(p.num_heads, p.batch), dim3(256), 0, stream, p, ws_ml, ws_o, plan.nsplit);
     return launch_util::check_launch("mmha");
 }
 
 template <int DH, int NIT>
-int launch_nit(const MmhaParams& p, hipStream_t stream)
+int launch_nit(const MmhaParams& p, const MmhaPlan& plan, hipStream_t stream)
 {
     switch (p.q_heads_per_workgroup) // resolved and checked by launch_mmha
     {
-    case 1: return launch_qt<DH, NIT, 1>(p, stream);
-    case 2: return launch_qt<DH, NIT, 2>(p, stream);
-    case 4: return launch_qt<DH, NIT, 4>(p, stream);
-    default: return launch_qt<DH, NIT, 8>(p, stream);
+    case 1: return launch_qt<DH, NIT, 1>(p, plan, stream);
+    case 2: return launch_qt<DH, NIT, 2>(p, plan, stream);
+    case 4: return launch_qt<DH, NIT, 4>(p, plan, stream);
+    default: return launch_qt<DH, NIT, 8>(p, plan, stream);
     }
 }
 
 template <int DH>
 int launch_dh(const MmhaParams& p, hipStream_t stream)
 {
-    if (p.rows_per_group == 16)
-        return launch_nit<DH, 16>(p, stream);
-    if (p.rows_per_group == 12)
-        return launch_nit<DH, 12>(p, stream);
-    return launch_nit<DH, 4>(p, stream);
+    const MmhaPlan plan = mmha_plan(DH, p.max_seq_len, p.batch, p.num_heads, p.rows_per_group);
+    if (p.rows_per_group == 0 || plan.rows_per_group != p.rows_per_group)
+    {
+        set_error("mmha: rows_per_group %d is not 4, 12 or 16 (0 is resolved by mmha_plan, before the launch)", p.rows_per_group);
+        return -1;
+    }
+    if (plan.nsplit > kMmhaMaxSplits)
+    {
+        set_error("mmha: max_seq_len %d needs more than %d splits", p.max_seq_len, kMmhaMaxSplits);
+        return -1;
+    }
+    if (p.tail_tickets && (plan.nsplit > kTailSlots || (p.tail_out_q8 && !p.tail_quant_scale)))
+    {
+        set_error("mmha: the in-launch merge takes at most %d splits (got %d) and a scale with its int8 output", kTailSlots, plan.nsplit);
+        return -1;
+    }
+    switch (plan.rows_per_group)
+    {
+    case 16: return launch_nit<DH, 16>(p, plan, stream);
+    case 12: return launch_nit<DH, 12>(p, plan, stream);
+    default: return launch_nit<DH, 4>(p, plan, stream);
+    }
 }
 
 } // namespace
 
-size_t mmha_ticket_bytes(int32_t batch, int32_t num_heads)
+MmhaPlan mmha_plan(int32_t head_size, int32_t max_seq_len, int32_t batch, int32_t num_heads, int32_t rows_per_group, bool force_combine)
 {
-    return ((size_t) batch * num_heads * sizeof(uint32_t) + 255) / 256 * 256;
-}
-
-size_t mmha_workspace_size(int32_t batch, int32_t num_heads, int32_t head_size, int32_t max_seq_len)
-{
-    // the merge tickets, then the partials sized for the finest split (NIT = 4)
+    MmhaPlan plan;
     const int lpr = head_size / 8;
-    if (lpr <= 0 || 64 % lpr)
-        return 0;
-    const int tchunk = kWaves * (64 / lpr) * 4;
-    const int ns = (max_seq_len + tchunk - 1) / tchunk;
-    const size_t ml = ((size_t) batch * num_heads * ns * sizeof(float2) + 255) / 256 * 256;
-    return mmha_ticket_bytes(batch, num_heads) + ml + (size_t) batch * num_heads * ns * head_size * sizeof(float);
+    if (lpr <= 0 || 64 % lpr || (rows_per_group != 0 && rows_per_group != 4 && rows_per_group != 12 && rows_per_group != 16))
+        return plan;
+    const int ngrp = mmha_lane_groups(head_size);
+    auto nsplit = [&](int rows) { return (max_seq_len + ngrp * rows - 1) / (ngrp * rows); };
+    auto up256 = [](size_t n) { return (n + 255) / 256 * 256; };
+    if (rows_per_group == 0)
+        rows_per_group = nsplit(16) > kMmhaTailSlots ? 4 : (nsplit(12) <= 8 ? 12 : 16);
+    const size_t bh = (size_t) batch * num_heads;
+    plan.rows_per_group = rows_per_group;
+    plan.tchunk = ngrp * rows_per_group;
+    plan.nsplit = nsplit(rows_per_group);
+    plan.in_launch_merge = plan.nsplit <= kMmhaTailSlots && !force_combine;
+    plan.ticket_bytes = up256(bh * sizeof(uint32_t));
+    plan.ml_bytes = up256(bh * plan.nsplit * sizeof(float2));
+    plan.workspace_bytes = plan.ticket_bytes + up256(bh * nsplit(4) * sizeof(float2)) + bh * nsplit(4) * head_size * sizeof(float);
+    return plan;
 }
 
-int mmha_split_layout(int32_t head_size, int32_t max_seq_len, int32_t rows_per_group, int32_t batch, int32_t num_heads,
-    int32_t* tchunk, int32_t* nsplit, size_t* out_offset)
+int mmha_bind_workspace(MmhaParams& p, const MmhaPlan& plan, void* workspace, bool reset_tickets, hipStream_t stream)
 {
-    const int lpr = head_size / 8;
-    if (lpr <= 0 || 64 % lpr)
-        return -1;
-    const int nit = rows_per_group == 16 ? 16 : (rows_per_group == 12 ? 12 : 4);
-    const int tc = kWaves * (64 / lpr) * nit;
-    const int ns = (max_seq_len + tc - 1) / tc;
-    if (tchunk)
-        *tchunk = tc;
-    if (nsplit)
-        *nsplit = ns;
-    if (out_offset)
-        *out_offset = ((size_t) batch * num_heads * ns * sizeof(float2) + 255) / 256 * 256;
-    return 0;
-}
-
-int mmha_reset_workspace(void* workspace, int32_t batch, int32_t num_heads, hipStream_t stream)
-{
-    if (hipMemsetAsync(workspace, 0, (size_t) batch * num_heads * sizeof(unsigned), stream) != hipSuccess)
+    p.rows_per_group = plan.rows_per_group;
+    p.tail_tickets = plan.in_launch_merge ? static_cast<uint32_t*>(workspace) : nullptr;
+    p.workspace = static_cast<char*>(workspace) + plan.ticket_bytes;
+    if (reset_tickets && p.tail_tickets
+        && hipMemsetAsync(workspace, 0, (size_t) p.batch * p.num_heads * sizeof(uint32_t), stream) != hipSuccess)
     {
         set_error("mmha: hipMemsetAsync(tickets) failed");
         return -1;
@@ -836,21 +825,8 @@ int launch_mmha(const MmhaParams& pin, hipStream_t stream)
             return -1;
         }
     }
-    if (p.int8_kv && (!p.kv_scale_orig_quant || !p.kv_scale_quant_orig))
-    {
-        set_error("mmha: int8 KV cache needs both scales");
+    if (launch_util::check_kv_dtype("mmha", p.kv_dtype, p.kv_scale_orig_quant && p.kv_scale_quant_orig))
         return -1;
-    }
-    if (p.fp8_kv && p.int8_kv)
-    {
-        set_error("mmha: int8_kv and fp8_kv are exclusive");
-        return -1;
-    }
-    if (p.fp8_kv && (!p.kv_scale_orig_quant || !p.kv_scale_quant_orig))
-    {
-        set_error("mmha: fp8 KV cache needs both scales");
-        return -1;
-    }
     if (p.timestep_host >= p.max_seq_len)
     {
         set_error("mmha: timestep %d exceeds cache capacity %d (circular cache not supported)", p.timestep_host,

@@ -1140,14 +1140,16 @@ const void* fused_kernel_of(int nit)
     }
 }
 
-const void* fused_kernel(int nit, bool int8_kv, int wk)
+// the one place a WType becomes the WK template argument
+const void* fused_kernel(int nit, bool kv8, int32_t wtype)
 {
-    switch (wk)
+    switch (wtype)
     {
-    case WK_WOQ8: return int8_kv ? fused_kernel_of<true, WK_WOQ8>(nit) : fused_kernel_of<false, WK_WOQ8>(nit);
-    case WK_FP16: return int8_kv ? fused_kernel_of<true, WK_FP16>(nit) : fused_kernel_of<false, WK_FP16>(nit);
-    case WK_WOQ4: return int8_kv ? fused_kernel_of<true, WK_WOQ4>(nit) : fused_kernel_of<false, WK_WOQ4>(nit);
-    default: return int8_kv ? fused_kernel_of<true, WK_SQ>(nit) : fused_kernel_of<false, WK_SQ>(nit);
+    case W_INT8_WOQ: return kv8 ? fused_kernel_of<true, WK_WOQ8>(nit) : fused_kernel_of<false, WK_WOQ8>(nit);
+    case W_FP16: return kv8 ? fused_kernel_of<true, WK_FP16>(nit) : fused_kernel_of<false, WK_FP16>(nit);
+    case W_INT4_WOQ: return kv8 ? fused_kernel_of<true, WK_WOQ4>(nit) : fused_kernel_of<false, WK_WOQ4>(nit);
+    case W_INT8_SQ: return kv8 ? fused_kernel_of<true, WK_SQ>(nit) : fused_kernel_of<false, WK_SQ>(nit);
+    default: return nullptr;
     }
 }
 
@@ -1176,29 +1178,31 @@ size_t qkv_attn_fused_xchg_bytes(int32_t num_heads)
 
 // the O-projection stage: K = H * Dh = 4 KiB rows (the context row is swept by 512 threads x two granules), every row worker's
 // share of the rows fits its LDS area
-bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t weight_kind,
+bool qkv_attn_fused_serves_o(int32_t num_heads, int32_t head_size, int32_t o_n, int32_t o_k, int64_t o_ldw, int32_t wtype,
     int32_t num_kv_heads)
 {
     if (num_kv_heads != 0 && num_kv_heads != num_heads)
         return false; // grouped K/V heads: the front is built for one K/V head per query head
     const int workers = (kMembers - 1) * num_heads;
-    const int64_t row_bytes = weight_kind == WK_WOQ4 ? o_k / 2 : o_k; // (int8 kinds; fp16 has no such stage)
+    const int64_t row_bytes = wtype == W_INT4_WOQ ? o_k / 2 : o_k; // (int8 kinds; fp16 has no such stage)
     return head_size == kDH && o_k == num_heads * head_size && o_k == kKChunks * 1024 && num_heads * kCtxGranules == 1024
-        && o_ldw % 16 == 0 && o_ldw >= row_bytes && o_n > 0 && (o_n + workers - 1) / workers <= kORowsMax && weight_kind != WK_FP16;
+        && o_ldw % 16 == 0 && o_ldw >= row_bytes && o_n > 0 && (o_n + workers - 1) / workers <= kORowsMax && wtype != W_FP16;
 }
 
-bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int32_t max_seq_len, int32_t int8_kv, int32_t weight_kind,
+bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int32_t max_seq_len, int32_t kv_dtype, int32_t wtype,
     int32_t o_stage, int32_t num_kv_heads)
 {
     if (num_kv_heads != 0 && num_kv_heads != num_heads)
         return false; // grouped K/V heads: the q | k | v row and the cache of the front are those of one K/V head per query head
-    const int nit = pick_nit(max_seq_len, int8_kv != 0);
+    if (kv_dtype != DT_HALF && kv_dtype != DT_INT8)
+        return false; // no E4M3 instance: such a cache runs the separate launches
+    const int nit = pick_nit(max_seq_len, kv_dtype == DT_INT8);
     // (K = 4096 elements: rows of 4 KiB int8 / 8 KiB fp16 = one / two tiles of 4 x 1 KiB chunks x 2 rows)
-    if (K != kKChunks * 1024 || head_size != kDH || nit == 0 || weight_kind < WK_SQ || weight_kind > WK_WOQ4)
+    if (K != kKChunks * 1024 || head_size != kDH || nit == 0)
         return false;
-    if (weight_kind == WK_FP16 && o_stage)
+    if (wtype == W_FP16 && o_stage)
         return false; // the row worker's share of an fp16 dense projection does not fit its LDS
-    const void* kfn = fused_kernel(nit, int8_kv != 0, weight_kind);
+    const void* kfn = fused_kernel(nit, kv_dtype == DT_INT8, wtype);
     if (!kfn)
         return false;
     // every workgroup of a head waits for its siblings (and the row workers for every head's merger): the whole grid must be
@@ -1219,44 +1223,45 @@ bool qkv_attn_fused_serves(int32_t K, int32_t num_heads, int32_t head_size, int3
 int launch_qkv_attn_fused(const FusedQkvAttnParams& p, hipStream_t stream)
 {
     const bool o_stage = p.o_w != nullptr;
-    const int wk = p.fp16_w ? WK_FP16 : (p.woq4 ? WK_WOQ4 : (p.woq8 ? WK_WOQ8 : WK_SQ));
-    if (!qkv_attn_fused_serves(p.K, p.num_heads, p.head_size, p.max_seq_len, p.int8_kv, wk, o_stage ? 1 : 0))
+    const bool sq = p.wtype == W_INT8_SQ, w16 = p.wtype == W_FP16, kv8 = p.kv_dtype == DT_INT8;
+    if (!qkv_attn_fused_serves(p.K, p.num_heads, p.head_size, p.max_seq_len, p.kv_dtype, p.wtype, o_stage ? 1 : 0))
     {
         set_error("fused QKV + attention: shape not served or grid not resident (K %d, heads %d x %d, cache %d, O stage %d)", p.K,
             p.num_heads, p.head_size, p.max_seq_len, o_stage ? 1 : 0);
         return -1;
     }
-    if (!p.x || !p.gamma || !p.w || (!p.scale_col && !p.fp16_w) || !p.kv_cache || !p.sequence_length || !p.rope_row || !p.xchg || !p.error || !p.out
-        || !p.epoch || (p.act_quant_scale && !p.act_dequant_scale) || (p.out_q8 && !p.out_quant_scale)
-        || (p.int8_kv && (!p.kv_scale_orig_quant || !p.kv_scale_quant_orig)) || p.ldw % 16)
+    if (launch_util::check_kv_dtype("fused QKV + attention", p.kv_dtype, p.kv_scale_orig_quant && p.kv_scale_quant_orig))
+        return -1;
+    if (!p.x || !p.gamma || !p.w || (!p.scale_col && !w16) || !p.kv_cache || !p.sequence_length || !p.rope_row || !p.xchg || !p.error || !p.out
+        || !p.epoch || (p.act_quant_scale && !p.act_dequant_scale) || (p.out_q8 && !p.out_quant_scale) || p.ldw % 16)
     {
         set_error("fused QKV + attention: missing operand");
         return -1;
     }
     if (p.o_w
-        && ((!p.woq8 && !p.woq4 && (!p.out_q8 || !p.o_scale_row)) || !p.o_scale_col || !p.x_out
-            || !qkv_attn_fused_serves_o(p.num_heads, p.head_size, p.o_n, p.num_heads * p.head_size, p.o_ldw, wk)))
+        && ((sq && (!p.out_q8 || !p.o_scale_row)) || !p.o_scale_col || !p.x_out
+            || !qkv_attn_fused_serves_o(p.num_heads, p.head_size, p.o_n, p.num_heads * p.head_size, p.o_ldw, p.wtype)))
     {
         set_error("fused QKV + attention: the O-projection stage needs the static int8 context row and a dense projection of %d x %d",
             p.num_heads * p.head_size, p.num_heads * p.head_size);
         return -1;
     }
-    if ((p.woq8 || p.fp16_w || p.woq4) && (p.out_q8 || p.act_quant_scale))
+    if (!sq && (p.out_q8 || p.act_quant_scale))
     {
         set_error("fused QKV + attention: the weight-only / fp16 forms have no quantiser");
         return -1;
     }
-    if (p.fp16_w && (p.woq8 || p.woq4 || p.ldw != (int64_t) p.K * 2))
+    if (w16 && p.ldw != (int64_t) p.K * 2)
     {
         set_error("fused QKV + attention: fp16 weights are dense rows of K halfs");
         return -1;
     }
-    if (p.woq4 && (p.woq8 || p.ldw != (int64_t) p.K / 2))
+    if (p.wtype == W_INT4_WOQ && p.ldw != (int64_t) p.K / 2)
     {
         set_error("fused QKV + attention: int4 weights are dense rows of K / 2 bytes");
         return -1;
     }
-    const void* kfn = fused_kernel(pick_nit(p.max_seq_len, p.int8_kv != 0), p.int8_kv != 0, wk);
+    const void* kfn = fused_kernel(pick_nit(p.max_seq_len, kv8), kv8, p.wtype);
     const dim3 grid(p.num_heads * kMembers), block(64 * kWavesF);
     FusedQkvAttnParams q = p;
     // the leading (preloaded) parameters are the struct's own fields: one source for every pointer

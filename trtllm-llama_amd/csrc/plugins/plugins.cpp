@@ -193,6 +193,7 @@ public:
     }
 
     bool quant_kv() const { return c.int8_kv_cache || c.fp8_kv_cache; } // one-byte cache elements + the two scale inputs
+    int32_t kv_dtype() const { return c.int8_kv_cache ? DT_INT8 : (c.fp8_kv_cache ? DT_FP8 : DT_HALF); }
     int block_pointers_idx() const { return quant_kv() ? 10 : 8; } // gptAttentionPlugin.h:156-159
 
     size_t workspaceSize(const Desc* in, int nin, const Desc* out, int nout) const override
@@ -202,7 +203,7 @@ public:
         const int S = c.remove_input_padding ? in[6].dims.d[0] : in[0].dims.d[1];
         const int Smax = c.paged_kv_cache ? in[7].dims.d[2] : in[1].dims.d[3];
         // max(context, generation), like the reference (gptAttentionPlugin.cpp:132-144)
-        const size_t gen = mmha_workspace_size(B, c.num_heads, c.head_size, Smax) + 256;
+        const size_t gen = mmha_plan(c.head_size, Smax, B, c.num_heads).workspace_bytes + 256;
         const size_t ctx = context_attention_workspace_size(B, c.num_heads, c.head_size, S) + 256 + kCuBytes;
         return gen > ctx ? gen : ctx;
     }
@@ -210,8 +211,12 @@ public:
     int enqueue(const Desc* inDesc, const Desc* outDesc, const void* const* in, void* const* out, void* ws,
         hipStream_t stream) override
     {
-        const int nin_expected = 8 + (quant_kv() ? 2 : 0);
-        (void) nin_expected;
+        // (validate() refuses the pair at creation; a deserialised configuration is not validated)
+        if (c.int8_kv_cache && c.fp8_kv_cache)
+        {
+            set_error("GPTAttention: int8_kv_cache and fp8_kv_cache are exclusive");
+            return 1;
+        }
         const bool packed = c.remove_input_padding != 0; // tokens of all sequences back to back (gptAttentionPlugin.cpp:344-356)
         const int B = packed ? inDesc[5].dims.d[0] : inDesc[0].dims.d[0];
         int S = packed ? 1 : inDesc[0].dims.d[1];
@@ -292,8 +297,7 @@ public:
             p.rotary_dim = rot;
             p.neox = c.neox_rotary_style;
             p.inv_sqrt_dh = inv_sqrt_dh;
-            p.int8_kv = c.int8_kv_cache;
-            p.fp8_kv = c.fp8_kv_cache;
+            p.kv_dtype = kv_dtype();
             p.max_seq_len = Smax;
             p.qkv = const_cast<void*>(in[0]);
             p.kv_cache = out[1];
@@ -327,8 +331,7 @@ public:
         p.rotary_dim = rot;
         p.neox = c.neox_rotary_style;
         p.inv_sqrt_dh = inv_sqrt_dh;
-        p.int8_kv = c.int8_kv_cache;
-        p.fp8_kv = c.fp8_kv_cache;
+        p.kv_dtype = kv_dtype();
         p.max_seq_len = Smax;
         p.max_input_len = max_input_len;
         p.qkv = in[0];
@@ -361,27 +364,14 @@ public:
         p.rope_table = table;
         p.rope_table_len = table_len;
         p.out = out[0];
-        p.workspace = ws;
         if (!ws)
         {
             set_error("GPTAttention: workspace is null");
             return 1;
         }
-        // the split merge runs inside the attention launch (the last split of a head to arrive: mmha_decode.hip step 6) - the same
-        // code path as the session's decode step; its tickets sit at the head of the workspace and are zeroed per enqueue.  Caches
-        // that need more than 16 splits take the finest split with its combine launch.
-        int tc = 0, ns = 0;
-        const size_t tick = mmha_ticket_bytes(B, c.num_heads);
-        if (mmha_split_layout(c.head_size, Smax, 16, B, c.num_heads, &tc, &ns, nullptr) == 0 && ns <= 16)
-        {
-            p.rows_per_group = 16;
-            if (mmha_split_layout(c.head_size, Smax, 12, B, c.num_heads, &tc, &ns, nullptr) == 0 && ns <= 8)
-                p.rows_per_group = 12;
-            if (mmha_reset_workspace(ws, B, c.num_heads, stream))
-                return 1;
-            p.tail_tickets = static_cast<uint32_t*>(ws);
-        }
-        p.workspace = static_cast<char*>(ws) + tick;
+        // the same plan and code path as the session's decode step; the tickets of the in-launch merge are zeroed per enqueue
+        if (mmha_bind_workspace(p, mmha_plan(c.head_size, Smax, B, c.num_heads), ws, true, stream))
+            return 1;
         return launch_mmha(p, stream) ? 1 : 0;
     }
 

@@ -51,11 +51,11 @@ static GemmParams gemm_params(const tllm_gemm_params_t* q)
     return g;
 }
 
-// tllm_attention_params_t -> the decode launcher's struct, with the launch shape the GPTAttention plugin picks where the caller
-// left it open (rows_per_group 16 / 12 and the in-launch merge while the cache fits 16 splits, else the finest split and the
-// combine launch).  in_launch: the splits are merged inside the launch (tickets at the head of the workspace).
-static int attention_decode_params(const tllm_attention_params_t* q, MmhaParams& p, bool& in_launch)
+// tllm_attention_params_t -> the decode launcher's struct and the split-KV plan of the launch (mmha_plan: the GPTAttention plugin's
+// where the caller left rows_per_group open)
+static int attention_decode_params(const tllm_attention_params_t* q, MmhaParams& p, MmhaPlan& plan)
 {
+    static_assert((int) TLLM_HALF == DT_HALF && (int) TLLM_INT8 == DT_INT8 && (int) TLLM_FP8 == DT_FP8, "kv_cache_type is a DType");
     if (!q || q->batch < 1 || q->num_heads < 1 || q->head_size < 1 || q->max_seq_len < 1)
     {
         set_error("tllm_attention_decode: bad arguments (batch, num_heads, head_size, max_seq_len)");
@@ -76,13 +76,18 @@ static int attention_decode_params(const tllm_attention_params_t* q, MmhaParams&
         set_error("tllm_attention_decode: kv_cache_type %d is not TLLM_HALF, TLLM_INT8 or TLLM_FP8", q->kv_cache_type);
         return 1;
     }
+    plan = mmha_plan(q->head_size, q->max_seq_len, q->batch, q->num_heads, q->rows_per_group, q->combine_launch != 0);
+    if (plan.rows_per_group == 0)
+    {
+        set_error("tllm_attention_decode: head_size %d not supported", q->head_size);
+        return 1;
+    }
     p.batch = q->batch;
     p.head_size = q->head_size;
     p.rotary_dim = q->rotary_dim;
     p.neox = q->neox;
     p.inv_sqrt_dh = 1.f / (sqrtf((float) q->head_size) * (q->q_scaling != 0.f ? q->q_scaling : 1.f));
-    p.int8_kv = q->kv_cache_type == TLLM_INT8;
-    p.fp8_kv = q->kv_cache_type == TLLM_FP8;
+    p.kv_dtype = q->kv_cache_type ? q->kv_cache_type : DT_HALF; // (TLLM_* and DT_* share their values)
     p.max_seq_len = q->max_seq_len;
     p.max_input_len = q->max_input_len;
     p.qkv = q->qkv;
@@ -104,24 +109,6 @@ static int attention_decode_params(const tllm_attention_params_t* q, MmhaParams&
     p.tail_quant_scale = q->tail_quant_scale;
     p.tail_out_q8 = q->tail_out_q8;
     p.out = q->out;
-    // the plugin's rule (plugins.cpp, GPTAttention enqueue)
-    int tc = 0, ns = 0;
-    in_launch = false;
-    p.rows_per_group = q->rows_per_group;
-    if (q->rows_per_group == 0)
-    {
-        if (mmha_split_layout(q->head_size, q->max_seq_len, 16, q->batch, q->num_heads, &tc, &ns, nullptr) == 0 && ns <= 16)
-        {
-            p.rows_per_group = 16;
-            if (mmha_split_layout(q->head_size, q->max_seq_len, 12, q->batch, q->num_heads, &tc, &ns, nullptr) == 0 && ns <= 8)
-                p.rows_per_group = 12;
-            in_launch = true;
-        }
-    }
-    else if (mmha_split_layout(q->head_size, q->max_seq_len, q->rows_per_group, q->batch, q->num_heads, &tc, &ns, nullptr) == 0)
-        in_launch = ns <= 16;
-    if (q->combine_launch)
-        in_launch = false;
     return 0;
 }
 
@@ -133,38 +120,32 @@ size_t tllm_attention_workspace_size(const tllm_attention_params_t* q, int32_t i
         return 0;
     if (is_context)
         return context_attention_workspace_size(q->batch, q->num_heads, q->head_size, q->seq) + 256;
-    return mmha_workspace_size(q->batch, q->num_heads, q->head_size, q->max_seq_len) + 256;
+    return mmha_plan(q->head_size, q->max_seq_len, q->batch, q->num_heads).workspace_bytes + 256;
 }
 
 int32_t tllm_attention_decode_layout(const tllm_attention_params_t* q, int32_t* tchunk, int32_t* nsplit, int32_t* q_tile,
     int32_t* in_launch_merge)
 {
     MmhaParams p;
-    bool in_launch = false;
-    if (attention_decode_params(q, p, in_launch))
+    MmhaPlan plan;
+    if (attention_decode_params(q, p, plan))
         return 1;
-    int tc = 0, ns = 0;
-    if (mmha_split_layout(p.head_size, p.max_seq_len, p.rows_per_group, p.batch, p.num_heads, &tc, &ns, nullptr))
-    {
-        set_error("tllm_attention_decode: head_size %d not supported", p.head_size);
-        return 1;
-    }
     if (tchunk)
-        *tchunk = tc;
+        *tchunk = plan.tchunk;
     if (nsplit)
-        *nsplit = ns;
+        *nsplit = plan.nsplit;
     if (q_tile)
         *q_tile = p.q_heads_per_workgroup;
     if (in_launch_merge)
-        *in_launch_merge = in_launch ? 1 : 0;
+        *in_launch_merge = plan.in_launch_merge ? 1 : 0;
     return 0;
 }
 
 int32_t tllm_attention_decode(const tllm_attention_params_t* q, tllm_stream_t stream)
 {
     MmhaParams p;
-    bool in_launch = false;
-    if (attention_decode_params(q, p, in_launch))
+    MmhaPlan plan;
+    if (attention_decode_params(q, p, plan))
         return 1;
     // paged: kv_cache is the pool itself - the rows of a block the table does not map yet are still loaded (and masked), from there
     if (!q->qkv || !q->out || !q->workspace || !q->sequence_length || !q->input_lengths || !q->kv_cache)
@@ -184,14 +165,9 @@ int32_t tllm_attention_decode(const tllm_attention_params_t* q, tllm_stream_t st
         if (!p.rope_table)
             return 1;
     }
-    // workspace: the merge tickets (zeroed per call, as the plugin does), then the partials
-    if (in_launch)
-    {
-        if (mmha_reset_workspace(q->workspace, p.batch, p.num_heads, st))
-            return 1;
-        p.tail_tickets = static_cast<uint32_t*>(q->workspace);
-    }
-    p.workspace = static_cast<char*>(q->workspace) + mmha_ticket_bytes(p.batch, p.num_heads);
+    // the merge tickets are zeroed per call, as the plugin does
+    if (mmha_bind_workspace(p, plan, q->workspace, true, st))
+        return 1;
     return launch_mmha(p, st) ? 1 : 0;
 }
 
@@ -217,8 +193,7 @@ int32_t tllm_attention_context(const tllm_attention_params_t* q, tllm_stream_t s
     p.rotary_dim = q->rotary_dim;
     p.neox = q->neox;
     p.inv_sqrt_dh = 1.f / (sqrtf((float) q->head_size) * (q->q_scaling != 0.f ? q->q_scaling : 1.f));
-    p.int8_kv = q->kv_cache_type == TLLM_INT8;
-    p.fp8_kv = q->kv_cache_type == TLLM_FP8;
+    p.kv_dtype = q->kv_cache_type ? q->kv_cache_type : DT_HALF; // (TLLM_* and DT_* share their values)
     p.max_seq_len = q->max_seq_len;
     p.qkv = q->qkv;
     p.kv_cache = q->kv_cache;

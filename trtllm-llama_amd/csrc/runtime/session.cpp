@@ -80,8 +80,8 @@ static int upload_prompt(tllm_session_t s, const int32_t* input_ids, const int32
         HIP_OK(hipMemsetAsync(s->cache_ind, 0, (size_t) B * Smax * 4, st)); // every slot -> hypothesis 0's rows
     }
     HIP_OK(hipMemcpyAsync(s->seq_len, seq.data(), B * 4, hipMemcpyHostToDevice, st));
-    if (s->attn_tickets) // re-arm the in-launch merge (it re-arms itself per launch; this covers a step that never finished)
-        HIP_OK(hipMemsetAsync(s->attn_tickets, 0, (size_t) B * s->Hr * 4, st));
+    if (s->attn_plan.in_launch_merge) // re-arm the in-launch merge (it re-arms itself per launch; this covers a step that never finished)
+        HIP_OK(hipMemsetAsync(s->mmha_ws, 0, (size_t) B * s->Hr * 4, st));
     HIP_OK(hipMemcpyAsync(s->finished, zeros.data(), B * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(s->masked, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(s->out_ids, out.data(), out.size() * 4, hipMemcpyHostToDevice, st));
@@ -192,7 +192,7 @@ int32_t tllm_session_fake_context(tllm_session_t s, int32_t length, uint32_t see
     // a padded prompt of `length` real tokens: slots [length, max_in) are masked
     RUN(upload_prompt(s, ids.data(), lens.data(), st));
     for (int i = 0; i < s->num_layers; ++i)
-        RUN(launch_fill_random(s->layers[i].kv, s->fp8_kv ? DT_FP8 : (s->int8_kv ? DT_INT8 : DT_HALF), s->kv_elems, seed + 7919u * i, 1.0f, st));
+        RUN(launch_fill_random(s->layers[i].kv, s->kv_dtype, s->kv_elems, seed + 7919u * i, 1.0f, st));
     RUN(s->run_sampler(0, st)); // prepares the RoPE row of the first generation step (the ids are overwritten next)
     RUN(launch_fill_i32(s->cur_ids, 3, B, st));
     RUN(launch_embedding(s->x, s->cur_ids, s->emb, B, s->hidden, s->vocab, st)); // what the sampler would have left in x

@@ -119,9 +119,9 @@ struct tllm_session
     // grouped-query attention (config key num_kv_heads, default num_heads): K/V heads of the model and of this rank (Hkv / tp), and
     // the extent of a fused QKV row of this rank, (Hr + 2 * Hkvr) * Dh
     int num_kv_heads = 0, Hkvr = 0, QKVr = 0;
-    bool sq = false, woq = false, int8_kv = false, per_token = false, per_channel = false;
-    bool fp8_kv = false; // OCP E4M3 cache (quant_mode bit 64): one-byte elements and the two scales of int8_kv, never both
-    size_t kv_esz() const { return (int8_kv || fp8_kv) ? 1 : 2; }
+    bool sq = false, woq = false, per_token = false, per_channel = false;
+    int kv_dtype = tllm::kernels::DT_HALF; // cache element: DT_INT8 (quant_mode bit 32) or DT_FP8 (OCP E4M3, bit 64), never both
+    size_t kv_esz() const { return kv_dtype == tllm::kernels::DT_HALF ? 2 : 1; }
     int wtype = tllm::kernels::W_FP16; // of every layer's five projections (lm_head stays fp16)
 
     std::map<std::string, TensorRec> tensors;
@@ -184,12 +184,9 @@ struct tllm_session
     int rope_len = 0;
     float* rope_row = nullptr; // [B, Dh/2, 2]: cos/sin row of the next generation step (written by the sampler)
     int32_t* rope_pos = nullptr; // [B]: the position that row belongs to (tllm_session_get_step_state)
-    int attn_nit = 4, attn_tchunk = 0, attn_ns = 0;
-    size_t attn_o_off = 0;
-    // the last split of a head to arrive merges inside the attention launch (mmha_decode.hip step 6); beyond 16 partials the finest
-    // split runs with its own combine launch
-    bool attn_tail = false;
-    uint32_t* attn_tickets = nullptr;
+    // the split-KV plan of the attention (kernels.h): in_launch_merge - the last split of a head to arrive merges inside the launch
+    // (mmha_decode.hip step 6), its tickets at the head of mmha_ws - or the finest split with its own combine launch
+    tllm::kernels::MmhaPlan attn_plan;
     // r05: batch-1 greedy decode of a SmoothQuant engine runs the QKV projection, RoPE, the cache append and the attention of a head
     // in ONE launch (kernels/qkv_attn_fused.hip); session key fuse_qkv_attention = 0 keeps the two launches (A/B, parity tests)
     int fuse_qkv_cfg = -1;          // -1 auto, 0 off

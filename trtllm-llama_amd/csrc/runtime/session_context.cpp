@@ -109,8 +109,7 @@ int tllm_session::context_attention(const Layer& L, bool q_in_attn, hipStream_t 
     c.rotary_dim = Dh;
     c.neox = neox;
     c.inv_sqrt_dh = 1.f / sqrtf((float) Dh);
-    c.int8_kv = int8_kv;
-    c.fp8_kv = fp8_kv;
+    c.kv_dtype = kv_dtype;
     c.max_seq_len = Smax;
     c.qkv = qkv;
     c.kv_cache = L.kv;

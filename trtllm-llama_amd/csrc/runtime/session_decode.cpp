@@ -293,7 +293,7 @@ tllm_session::DecodeStep tllm_session::plan_decode_step(hipStream_t st)
     ds.pro_norm = !sq ? PRO_RMSNORM : (per_token ? PRO_RMSNORM_QDYN : PRO_RMSNORM_QSTATIC);
     ds.pro_q = !sq ? PRO_NONE : (per_token ? PRO_QDYN : PRO_QSTATIC);
     ds.q_inter = sq && !per_token;
-    ds.tail_q8 = attn_tail && sq && !per_token;
+    ds.tail_q8 = attn_plan.in_launch_merge && sq && !per_token;
     // (kernel-timing id 1 measures the front's two-stage form, id 7 the launch exactly as the step runs it; with the stage clock
     //  on, the three-stage form is what id 1 looks at too - x is overwritten by every timed launch: the timer restores it)
     ds.front = qkv_attn_fused && (on(1) || ok == 7);
@@ -330,12 +330,10 @@ int tllm_session::stage_front(const DecodeStep& ds, int li)
     f.ldw = L.qkv.ldw;
     f.scale_col = L.qkv.scale_col;
     f.per_channel = L.qkv.per_channel;
-    f.woq8 = L.qkv.wtype == W_INT8_WOQ ? 1 : 0;
-    f.fp16_w = L.qkv.wtype == W_FP16 ? 1 : 0;
-    f.woq4 = L.qkv.wtype == W_INT4_WOQ ? 1 : 0;
+    f.wtype = L.qkv.wtype;
     f.act_quant_scale = (per_token || !sq) ? nullptr : L.ln1_scale;
     f.act_dequant_scale = (per_token || !sq) ? nullptr : L.qkv.act_scale;
-    f.int8_kv = int8_kv;
+    f.kv_dtype = kv_dtype;
     f.max_seq_len = Smax;
     f.inv_sqrt_dh = 1.f / sqrtf((float) Dh);
     f.kv_cache = L.kv;
@@ -394,7 +392,7 @@ int tllm_session::stage_qkv(const DecodeStep& ds, int li)
         ds.st, nullptr, ds.taps ? tap_ptr(0, li) : nullptr);
 }
 
-// K2 / K3: RoPE + KV append + split-KV attention, merged in the launch (attn_tail) or by its combine launch
+// K2 / K3: RoPE + KV append + split-KV attention, merged in the launch (attn_plan.in_launch_merge) or by its combine launch
 int tllm_session::stage_attention(const DecodeStep& ds, int li)
 {
     const Layer& L = layers[li];
@@ -407,8 +405,7 @@ int tllm_session::stage_attention(const DecodeStep& ds, int li)
     m.rotary_dim = Dh;
     m.neox = neox;
     m.inv_sqrt_dh = 1.f / sqrtf((float) Dh);
-    m.int8_kv = int8_kv;
-    m.fp8_kv = fp8_kv;
+    m.kv_dtype = kv_dtype;
     m.max_seq_len = Smax;
     m.max_input_len = max_in;
     m.qkv = qkv;
@@ -427,18 +424,13 @@ int tllm_session::stage_attention(const DecodeStep& ds, int li)
     m.block_pointers = L.kv_table;
     m.tokens_per_block = tokens_per_block;
     m.max_blocks_per_seq = max_blocks;
-    m.rows_per_group = attn_nit;
-    if (attn_tail)
+    if (ds.tail_q8)
     {
-        m.tail_tickets = attn_tickets;
-        if (ds.tail_q8)
-        {
-            m.tail_out_q8 = ctx_q8;
-            m.tail_quant_scale = L.attn_qscale;
-        }
+        m.tail_out_q8 = ctx_q8;
+        m.tail_quant_scale = L.attn_qscale;
     }
     m.out = ctx;
-    m.workspace = mmha_ws;
+    RUN(mmha_bind_workspace(m, attn_plan, mmha_ws, false, st)); // (the tickets: zero since setup / the prompt, re-armed by every launch)
     return timed(PC_ATTENTION, st, [&] { return launch_mmha(m, st); });
 }
 

@@ -94,8 +94,9 @@ int tllm_session::alloc_buffers()
     }
     RUN(dalloc(&cu_dev, (size_t) (Bc + 1) * 4));
     RUN(dalloc(&last_rows, (size_t) Bc * 4));
-    RUN(dalloc(&mmha_ws, mmha_workspace_size(B, Hr, Dh, Smax) + 256));
-    HIP_OK(hipMemset(mmha_ws, 0, mmha_workspace_size(B, Hr, Dh, Smax) + 256));
+    const size_t mmha_bytes = mmha_plan(Dh, Smax, B, Hr).workspace_bytes + 256;
+    RUN(dalloc(&mmha_ws, mmha_bytes));
+    HIP_OK(hipMemset(mmha_ws, 0, mmha_bytes)); // (the merge tickets at its head among them)
     RUN(dalloc(&ids_in, M * 4));
     RUN(dalloc(&cur_ids, (size_t) B * 4));
     RUN(dalloc(&out_ids, (size_t) B * Smax * 4));
@@ -128,36 +129,19 @@ int tllm_session::alloc_buffers()
 
 // ------------------------------------------------------------------------------------------ decode form
 // Which launches a generation step of this session consists of.  Decides, allocates nothing:
-//   attn_tail / attn_nit / attn_tchunk / attn_ns / attn_o_off   the split-KV layout of the attention
+//   attn_plan        the split-KV plan of the attention (kernels.h, mmha_plan)
 //   qkv_attn_fused   QKV projection + RoPE + cache append + attention in one launch (kernels/qkv_attn_fused.hip)
 //   o_fused          ... with the O-projection + residual as its third stage
 //   mlp_fused_dec    gate|up + down in one launch (kernels/mlp_fused.hip)
 int tllm_session::decide_decode_form()
 {
     const int D = hidden;
-    // The split-KV merge runs inside the attention launch, by the last split of a head to arrive (mmha_decode.hip step 6; up to
-    // 16 partials: 16-row splits cover 4096 cache slots at head size 128); 12 rows per lane group while that needs <= 8 partials
-    // (7 x 32 instead of 5 x 32 workgroups at the 1024-token bench context).  Beyond 16 partials: the finest split with its own
-    // combine launch.
-    int tc = 0, ns = 0;
-    size_t off = 0;
-    attn_tail = false;
-    attn_nit = 4;
-    if (mmha_split_layout(Dh, Smax, 16, B, Hr, &tc, &ns, &off) == 0 && ns <= 16)
-    {
-        attn_nit = 16;
-        if (mmha_split_layout(Dh, Smax, 12, B, Hr, &tc, &ns, &off) == 0 && ns <= 8)
-            attn_nit = 12;
-        attn_tail = true;
-    }
-    if (mmha_split_layout(Dh, Smax, attn_nit, B, Hr, &tc, &ns, &off))
+    attn_plan = mmha_plan(Dh, Smax, B, Hr);
+    if (attn_plan.rows_per_group == 0)
     {
         set_error("session: unsupported head size %d", Dh);
         return 1;
     }
-    attn_tchunk = tc;
-    attn_ns = ns;
-    attn_o_off = off;
 
     qkv_attn_fused = false;
     o_fused = false;
@@ -180,35 +164,31 @@ int tllm_session::decide_decode_form()
     // weight-only int8 (the same 4 KB weight rows against the normalised fp16 row), or - r06 - fp16 (rows of 8 KB, two tiles
     // per row pair; BASELINE.json configs[1]), or weight-only int4.  Every projection of a session has the session's weight type
     // (resolve_linear), so that type is the kind of all layers.
-    const bool fp16_w = wtype == W_FP16, woq4 = wtype == W_INT4_WOQ;
-    const int wkind = wtype == W_INT8_SQ ? 0 : (wtype == W_INT8_WOQ ? 1 : (fp16_w ? 2 : 3)); // qkv_attn_fused_serves' weight_kind
-    // an fp8 cache runs the separate launches (QKV GEMV, attention with its in-launch merge, O GEMV): the one-launch form has no
-    // E4M3 instance yet
-    if (fp8_kv)
-        return 0;
-    const int kv8 = int8_kv ? 1 : 0;
-    // grouped K/V heads (Hkvr != Hr) run the separate-launch step: the one-launch front is built for one K/V head per query head
-    if (fuse_qkv_cfg == 0 || Hkvr != Hr || !attn_tail || B != 1 || beam != 1 || paged_kv || tp != 1 || !neox
-        || !qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0, Hkvr))
+    const bool w16 = wtype == W_FP16, woq4 = wtype == W_INT4_WOQ;
+    // An fp8 cache (the one-launch form has no E4M3 instance yet, DESIGN.md section 4: qkv_attn_fused_serves refuses it) and grouped
+    // K/V heads (Hkvr != Hr: the front is built for one K/V head per query head) run the separate launches - QKV GEMV, attention
+    // with its in-launch merge, O GEMV
+    if (fuse_qkv_cfg == 0 || Hkvr != Hr || !attn_plan.in_launch_merge || B != 1 || beam != 1 || paged_kv || tp != 1 || !neox
+        || !qkv_attn_fused_serves(D, Hr, Dh, Smax, kv_dtype, wtype, 0, Hkvr))
         return 0;
     for (auto& L : layers)
-        if (!(L.qkv.wtype == wtype && L.qkv.K == D && L.qkv.ldw == (fp16_w ? 2 * D : (woq4 ? D / 2 : D)) && L.qkv.N == 3 * Dr
-                && (L.qkv.scale_col || fp16_w)))
+        if (!(L.qkv.wtype == wtype && L.qkv.K == D && L.qkv.ldw == (w16 ? 2 * D : (woq4 ? D / 2 : D)) && L.qkv.N == 3 * Dr
+                && (L.qkv.scale_col || w16)))
             return 0;
     qkv_attn_fused = true;
     // (tp == 1 here: no all-reduce behind the projection.  Weight-only int8: the context row travels as fp16)
     // (int4: the stage is built and bit-identical but measures at par with the GEMV launch it replaces - 724 vs 721 - 735 tokens/s -
     //  so it is on only when asked for: fuse_o_projection = 1)
-    o_fused = fuse_o_cfg != 0 && !fp16_w && (woq4 ? fuse_o_cfg > 0 : true) && (sq ? !per_token : true);
+    o_fused = fuse_o_cfg != 0 && !w16 && (woq4 ? fuse_o_cfg > 0 : true) && (sq ? !per_token : true);
     for (auto& L : layers)
         o_fused = o_fused && L.dense.N == D && L.dense.scale_col && L.dense.wtype == wtype
             && (sq ? (L.dense.act_scale && L.attn_qscale) : true)
-            && qkv_attn_fused_serves_o(Hr, Dh, L.dense.N, L.dense.K, L.dense.ldw, wkind, Hkvr);
+            && qkv_attn_fused_serves_o(Hr, Dh, L.dense.N, L.dense.K, L.dense.ldw, wtype, Hkvr);
     // ... and the instance that will run must be resident as a whole (occupancy query x CUs of this device >= its grid)
-    if (!qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, o_fused ? 1 : 0, Hkvr))
+    if (!qkv_attn_fused_serves(D, Hr, Dh, Smax, kv_dtype, wtype, o_fused ? 1 : 0, Hkvr))
     {
         o_fused = false;
-        qkv_attn_fused = qkv_attn_fused_serves(D, Hr, Dh, Smax, kv8, wkind, 0, Hkvr);
+        qkv_attn_fused = qkv_attn_fused_serves(D, Hr, Dh, Smax, kv_dtype, wtype, 0, Hkvr);
     }
     return 0;
 }
@@ -259,18 +239,13 @@ int tllm_session::alloc_decode_form_buffers()
         RUN(dalloc(&argmax_part, (size_t) kArgmaxPairs * 8));
         HIP_OK(hipMemset(argmax_part, 0, (size_t) kArgmaxPairs * 8));
     }
-    attn_tickets = nullptr;
     ctx_q8 = nullptr;
     fused_xchg = nullptr;
     fused_timing = nullptr;
     mlp_flags = nullptr;
     mlp_timing = nullptr;
-    if (attn_tail)
-    {
-        RUN(dalloc(reinterpret_cast<void**>(&attn_tickets), (size_t) B * Hr * 4));
-        HIP_OK(hipMemset(attn_tickets, 0, (size_t) B * Hr * 4));
+    if (attn_plan.in_launch_merge)
         RUN(dalloc(&ctx_q8, (size_t) B * Dr));
-    }
     if (mlp_fused_dec)
     {
         RUN(dalloc(&mlp_flags, mlp_fused_flag_bytes()));

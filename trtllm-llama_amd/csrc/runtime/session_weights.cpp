@@ -221,9 +221,8 @@ tllm_session_t tllm_session_create(const char* config_text)
     const int qm = s->quant_mode;
     s->sq = (qm & QM_ACTIVATIONS) && (qm & QM_INT8_WEIGHTS);
     s->woq = !s->sq && (qm & (QM_INT8_WEIGHTS | QM_INT4_WEIGHTS));
-    s->int8_kv = qm & QM_INT8_KV;
-    s->fp8_kv = qm & QM_FP8_KV;
-    if (s->int8_kv && s->fp8_kv)
+    s->kv_dtype = (qm & QM_INT8_KV) ? DT_INT8 : ((qm & QM_FP8_KV) ? DT_FP8 : DT_HALF);
+    if ((qm & QM_INT8_KV) && (qm & QM_FP8_KV))
     {
         set_error("tllm_session_create: quant_mode %d sets both INT8_KV_CACHE (32) and FP8_KV_CACHE (64); a cache has one element type", qm);
         return nullptr;
@@ -311,7 +310,7 @@ int32_t tllm_session_finalize(tllm_session_t s)
             RUN(s->scalar_f32(p + "attention.quantization_scaling_factor", &L.attn_qscale));
             RUN(s->scalar_f32(p + "mlp.quantization_scaling_factor", &L.mlp_qscale));
         }
-        if (s->int8_kv || s->fp8_kv)
+        if (s->kv_dtype != DT_HALF)
         {
             RUN(s->scalar_f32(p + "attention.kv_orig_quant_scale", &L.kv_oq));
             RUN(s->scalar_f32(p + "attention.kv_quant_orig_scale", &L.kv_qo));
@@ -409,8 +408,8 @@ int verify_engine_network(tllm_session_t s, const std::vector<EngineEntry>& ents
     d.per_token = s->per_token;
     d.woq = s->woq;
     d.int4 = s->wtype == W_INT4_WOQ;
-    d.int8_kv = s->int8_kv;
-    d.fp8_kv = s->fp8_kv;
+    d.int8_kv = s->kv_dtype == DT_INT8;
+    d.fp8_kv = s->kv_dtype == DT_FP8;
     d.paged = s->paged_kv;
     d.packed = s->packed;
     d.neox = s->neox != 0;
