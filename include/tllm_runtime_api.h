@@ -455,6 +455,12 @@ typedef struct
      * launched - never a substitute.  combine_launch: 1 = merge the splits in a second launch even where the in-launch merge
      * (at most 16 splits) would serve. */
     int32_t rows_per_group, q_heads_per_workgroup, combine_launch;
+    /* context launch shape.  context_kernel: the attention kernel, TLLM_CTX_ATTN_WAVE (one wave per query), _MFMA_NARROW (64
+     * queries per workgroup), _MFMA_WIDE (128) or _MFMA_PAIRED (two 64-query blocks per workgroup, three operand stages); 0 = the
+     * launcher's rule.  A forced value runs exactly that instance or the call returns non-zero with tllm_last_error() set and
+     * nothing launched - never a substitute: the MFMA kinds need head size 64 / 128, the workspace, seq >= 64 and a positive score
+     * scale. */
+    int32_t context_kernel;
     const float* tail_quant_scale; /* decode, in-launch merge: static int8 image of the context row to tail_out_q8 */
     void* tail_out_q8;
     int8_t* out_q8; /* context: static int8 image instead of (MFMA kernel) or next to `out` */
@@ -470,6 +476,16 @@ int32_t tllm_attention_context(const tllm_attention_params_t* p, tllm_stream_t s
  * query tile, and whether the splits are merged inside the launch (1) or by the combine launch (0).  Non-zero: p is refused. */
 int32_t tllm_attention_decode_layout(const tllm_attention_params_t* p, int32_t* tchunk, int32_t* nsplit, int32_t* q_tile,
     int32_t* in_launch_merge);
+/* the attention kernel tllm_attention_context would run for p (batch, seq, num_heads, head_size, q_scaling, context_kernel and
+ * whether workspace is NULL are read; no pointer is followed) on a device of `cus` compute units: its kind (TLLM_CTX_ATTN_*), the
+ * queries per workgroup, the operand stages in LDS (0 for the wave-per-query kernel) and the workgroups of the launch.  cus 0 = the
+ * current device; a non-zero cus needs no GPU.  Non-zero: p is refused (a forced context_kernel the launch cannot run). */
+#define TLLM_CTX_ATTN_WAVE 1
+#define TLLM_CTX_ATTN_MFMA_NARROW 2
+#define TLLM_CTX_ATTN_MFMA_WIDE 3
+#define TLLM_CTX_ATTN_MFMA_PAIRED 4
+int32_t tllm_attention_context_layout(const tllm_attention_params_t* p, int32_t cus, int32_t* kind, int32_t* query_block,
+    int32_t* stages, int32_t* workgroups);
 
 #ifdef __cplusplus
 }

@@ -302,6 +302,7 @@ def test_decode_with_the_paged_cache(lib, kind):
 
 
 # ------------------------------------------------------------------------------------------------------------ context
+# (every context attention instance forced at small shapes, against a float64 oracle: tests/test_gpu_ctx_attn_instances.py)
 def run_context(lib, kind, H, Hkv, Dh, S, in_len, qkv, smax, packed=False, pointers=None, T=0, M=0, pool=None):
     B = len(in_len)
     c = Call(lib, kind, B, H, Hkv, Dh, smax, seq=S, tokens_per_block=T, max_blocks_per_seq=M)

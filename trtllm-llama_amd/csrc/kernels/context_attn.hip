@@ -725,68 +725,124 @@ template <int DH>
 int launch_dh(const ContextAttnParams& p, hipStream_t stream)
 {
     constexpr int HG = 256 / (DH / 8);
-    bool mfma = false;
-    if constexpr (DH == 64 || DH == 128)
+    const ContextAttnPlan plan
+        = context_attention_plan(DH, p.seq, p.batch, p.num_heads, p.workspace != nullptr, p.inv_sqrt_dh > 0.f, 0, p.kernel);
+    if (plan.kernel == 0) // a forced kind this launch cannot run: nothing is enqueued
     {
-        if (p.workspace && p.seq >= 64 && p.inv_sqrt_dh > 0.f)
-        {
-            mfma = true;
-            const int spad = (p.seq + 63) / 64 * 64;
-            // RoPE + KV write (+ int8 quantisation) + the V^T image in one launch
-            hipLaunchKernelGGL((rope_kv_vt_kernel<DH>), dim3(spad / 64, p.num_heads, p.batch), dim3(256), 0, stream, p, spad);
-            {
-                // 64-query workgroups while 128-query ones would not fill the chip
-                bool narrow = (int64_t) ((p.seq + 127) / 128) * p.num_heads * p.batch < 256;
-                constexpr size_t stages = 2 * (size_t) (64 * DH * 2 + DH * 128), slab = (size_t) (2 + 16 * (DH / 32)) * 64 * 4;
-                // Paired 64-query blocks while the launch is at most ONE round of 128-query workgroups (32 heads, r02,
-                // profiles/r02_ctx_attn_pairing.txt: S = 1024, 256 workgroups on 256 CUs, 31.9 -> 26.8 us; S = 896 / 768 / 512 / 384 /
-                // 256, where the unpaired choice is the 64-query kernel, 28.0 -> 24.1, 24.5 -> 21.0, 18.5 -> 16.4, 15.8 -> 14.3,
-                // 12.5 -> 12.0): with more workgroups than CUs the dispatcher already back-fills the CUs of the short blocks and
-                // pairing only makes every workgroup long (S = 1536: 44 -> 58 us, S = 2048: 61.6 -> 72.4).
-                const int cus = launch_util::device_cus();
-                const int64_t wg128 = (int64_t) ((p.seq + 127) / 128) * p.num_heads * p.batch;
-                const bool pair = wg128 <= cus && 4 * wg128 >= cus;
-                if (pair)
-                    narrow = false;
-                // three operand stages only under the paired kernel (S = 1024: 28.1 -> 27.4 us; one block per workgroup loses with
-                // them: 30.4 -> 31.2 at S = 1024, 61.6 -> 63.0 at 2048 - the operand stream is bound by its rate, not by the latency
-                // of one block in flight; profiles/r02_ctx_attn_pairing.txt)
-                const bool ring = pair;
-                // (a FOURTH stage - three blocks in flight, 128 KB - measured 25.6 against 24.5 us at S = 1024 in r05: more bytes in
-                //  flight do not raise the rate of the operand stream)
-                const int nst = ring ? 3 : 2;
-                const size_t stg = stages / 2 * nst;
-                const size_t smem = stg > (narrow ? 2 : 4) * slab ? stg : 4 * slab;
-                auto kfn = narrow ? context_attn_mfma_ks_kernel<DH, 2>
-                                  : (pair ? context_attn_mfma_ks_kernel<DH, 4, true, 3> : context_attn_mfma_ks_kernel<DH, 4>);
-                if (stages > 64 * 1024 || 4 * slab > 64 * 1024)
-                    launch_util::ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), 96 * 1024);
-                const int qbw = narrow ? 64 : 128;
-                // paired: ceil(nblk64 / 2) workgroups per head - the same count as 128-query blocks
-                hipLaunchKernelGGL(kfn, dim3(p.num_heads, (p.seq + qbw - 1) / qbw, p.batch), dim3(narrow ? 256 : 512), smem, stream, p, spad);
-            }
-        }
+        set_error("context attention: kernel %d refused: %s", p.kernel, plan.refused ? plan.refused : "no plan");
+        return -1;
     }
-    if (!mfma)
+    const dim3 grid(plan.grid[0], plan.grid[1], plan.grid[2]);
+    if (plan.kernel == CTX_ATTN_WAVE)
     {
+        // the quantiser is a pass of its own behind this kernel, over the padded [B, S] rows
+        if (p.out_q8 && p.cu_seqlens)
+        {
+            set_error("context attention: the fused output quantiser needs padded inputs on this path");
+            return -1;
+        }
         hipLaunchKernelGGL((rope_kv_write_kernel<DH>), dim3(p.seq, (p.num_heads + HG - 1) / HG, p.batch), dim3(256), 0, stream, p);
-        hipLaunchKernelGGL((context_attn_kernel<DH>), dim3((p.seq + 3) / 4, p.num_heads, p.batch), dim3(256), 0, stream, p);
-        if (p.out_q8) // the quantiser as a pass of its own behind this kernel
-        {
-            const int64_t rows = p.cu_seqlens ? -1 : (int64_t) p.batch * p.seq;
-            if (rows < 0)
-            {
-                set_error("context attention: the fused output quantiser needs padded inputs on this path");
-                return -1;
-            }
-            if (launch_quantize_tensor(p.out_q8, p.out, DT_HALF, rows * p.num_heads * DH, p.out_q_scale, stream))
-                return -1;
-        }
+        hipLaunchKernelGGL((context_attn_kernel<DH>), grid, dim3(plan.threads), 0, stream, p);
+        if (p.out_q8
+            && launch_quantize_tensor(p.out_q8, p.out, DT_HALF, (int64_t) p.batch * p.seq * p.num_heads * DH, p.out_q_scale, stream))
+            return -1;
+        return launch_util::check_launch("context attention");
     }
-    return launch_util::check_launch("context attention");
+    if constexpr (DH == 64 || DH == 128) // (the plan gives no MFMA kind to another head size)
+    {
+        const int spad = (p.seq + 63) / 64 * 64;
+        // RoPE + KV write (+ int8 quantisation) + the V^T image in one launch
+        hipLaunchKernelGGL((rope_kv_vt_kernel<DH>), dim3(spad / 64, p.num_heads, p.batch), dim3(256), 0, stream, p, spad);
+        auto kfn = plan.kernel == CTX_ATTN_MFMA_NARROW
+            ? context_attn_mfma_ks_kernel<DH, 2>
+            : (plan.kernel == CTX_ATTN_MFMA_PAIRED ? context_attn_mfma_ks_kernel<DH, 4, true, 3> : context_attn_mfma_ks_kernel<DH, 4>);
+        constexpr size_t stages = 2 * (size_t) (64 * DH * 2 + DH * 128), slab = (size_t) (2 + 16 * (DH / 32)) * 64 * 4;
+        if (stages > 64 * 1024 || 4 * slab > 64 * 1024)
+            launch_util::ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), 96 * 1024);
+        hipLaunchKernelGGL(kfn, grid, dim3(plan.threads), plan.lds_bytes, stream, p, spad);
+        return launch_util::check_launch("context attention");
+    }
+    set_error("context attention: no MFMA kernel for head_size %d", DH);
+    return -1;
 }
 
 } // namespace
+
+ContextAttnPlan context_attention_plan(int32_t head_size, int32_t seq, int32_t batch, int32_t num_heads, bool has_workspace,
+    bool score_scale_positive, int32_t cus, int32_t forced_kernel)
+{
+    ContextAttnPlan plan;
+    if (seq < 1 || batch < 1 || num_heads < 1 || (head_size != 32 && head_size != 64 && head_size != 128 && head_size != 256))
+    {
+        plan.refused = "bad shape (seq, batch, num_heads >= 1, head_size 32 / 64 / 128 / 256)";
+        return plan;
+    }
+    const int DH = head_size;
+    int kind = forced_kernel;
+    if (kind < CTX_ATTN_RULE || kind > CTX_ATTN_MFMA_PAIRED)
+    {
+        plan.refused = "unknown kernel (1 wave-per-query, 2 MFMA narrow, 3 MFMA wide, 4 MFMA paired; 0 the rule)";
+        return plan;
+    }
+    if (kind >= CTX_ATTN_MFMA_NARROW)
+    {
+        if (DH != 64 && DH != 128)
+            plan.refused = "the MFMA kernels serve head sizes 64 and 128";
+        else if (!has_workspace)
+            plan.refused = "the MFMA kernels need the workspace (the V^T image)";
+        else if (seq < 64)
+            plan.refused = "the MFMA kernels need seq >= 64";
+        else if (!score_scale_positive)
+            plan.refused = "the MFMA kernels need a positive score scale";
+        if (plan.refused)
+            return plan;
+    }
+    if (kind == CTX_ATTN_RULE)
+    {
+        kind = CTX_ATTN_WAVE;
+        if ((DH == 64 || DH == 128) && has_workspace && seq >= 64 && score_scale_positive)
+        {
+            // 64-query workgroups while 128-query ones would not fill the chip
+            const int64_t wg128 = (int64_t) ((seq + 127) / 128) * num_heads * batch;
+            const bool narrow = wg128 < 256;
+            // Paired 64-query blocks while the launch is at most ONE round of 128-query workgroups (32 heads, r02,
+            // profiles/r02_ctx_attn_pairing.txt: S = 1024, 256 workgroups on 256 CUs, 31.9 -> 26.8 us; S = 896 / 768 / 512 / 384 /
+            // 256, where the unpaired choice is the 64-query kernel, 28.0 -> 24.1, 24.5 -> 21.0, 18.5 -> 16.4, 15.8 -> 14.3,
+            // 12.5 -> 12.0): with more workgroups than CUs the dispatcher already back-fills the CUs of the short blocks and
+            // pairing only makes every workgroup long (S = 1536: 44 -> 58 us, S = 2048: 61.6 -> 72.4).
+            if (cus <= 0)
+                cus = launch_util::device_cus();
+            const bool pair = wg128 <= cus && 4 * wg128 >= cus;
+            kind = pair ? CTX_ATTN_MFMA_PAIRED : (narrow ? CTX_ATTN_MFMA_NARROW : CTX_ATTN_MFMA_WIDE);
+        }
+    }
+    plan.kernel = kind;
+    plan.grid[2] = (uint32_t) batch;
+    if (kind == CTX_ATTN_WAVE)
+    {
+        plan.query_block = 4;
+        plan.threads = 256;
+        plan.grid[0] = (uint32_t) ((seq + 3) / 4);
+        plan.grid[1] = (uint32_t) num_heads;
+        return plan;
+    }
+    // three operand stages only under the paired kernel (S = 1024: 28.1 -> 27.4 us; one block per workgroup loses with them:
+    // 30.4 -> 31.2 at S = 1024, 61.6 -> 63.0 at 2048 - the operand stream is bound by its rate, not by the latency of one block in
+    // flight; profiles/r02_ctx_attn_pairing.txt)
+    // (a FOURTH stage - three blocks in flight, 128 KB - measured 25.6 against 24.5 us at S = 1024 in r05: more bytes in flight do
+    //  not raise the rate of the operand stream)
+    const bool narrow = kind == CTX_ATTN_MFMA_NARROW;
+    plan.stages = kind == CTX_ATTN_MFMA_PAIRED ? 3 : 2;
+    plan.query_block = narrow ? 64 : 128;
+    plan.threads = narrow ? 256 : 512;
+    const size_t stage = (size_t) (64 * DH * 2 + DH * 128), slab = (size_t) (2 + 16 * (DH / 32)) * 64 * 4; // (the kernel's STAGE, SLAB)
+    const size_t stg = stage * plan.stages;
+    plan.lds_bytes = stg > (narrow ? 2 : 4) * slab ? stg : 4 * slab; // the operand stages, reused by the merge records of the waves
+    // heads fastest; paired: ceil(nblk64 / 2) workgroups per head - the same count as 128-query blocks
+    plan.grid[0] = (uint32_t) num_heads;
+    plan.grid[1] = (uint32_t) ((seq + plan.query_block - 1) / plan.query_block);
+    return plan;
+}
 
 size_t context_attention_workspace_size(int batch, int num_heads, int head_size, int seq)
 {

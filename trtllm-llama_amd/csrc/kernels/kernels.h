@@ -362,8 +362,39 @@ struct ContextAttnParams
     // grouped-query attention, as MmhaParams::num_kv_heads (0 = num_heads): qkv rows are [q: H*Dh | k: Hkv*Dh | v: Hkv*Dh], RoPE
     // on k, the cache quantisation and the cache write run once per K/V head; `out` stays [B, S, H*Dh]
     int32_t num_kv_heads = 0;
+    // the attention kernel of the launch, a ContextAttnKernel: 0 = the launcher's rule (context_attention_plan); a forced kind runs
+    // exactly that instance, and one the launcher cannot run is an error with nothing enqueued, never a substitute
+    int32_t kernel = 0;
 };
 size_t context_attention_workspace_size(int batch, int num_heads, int head_size, int seq);
+// The launch plan of the context attention - which of the four attention kernels runs, and its geometry - stated once:
+//   wg128 = ceil(seq / 128) * num_heads * batch, the workgroups a launch of 128-query workgroups would have;
+//   the MFMA kernels serve head sizes 64 / 128 with a workspace (the V^T image), seq >= 64 and a positive score scale; everything
+//   else is the wave-per-query kernel (4 queries per workgroup, no dynamic LDS);
+//   among the MFMA kernels: PAIRED (two 64-query blocks per workgroup, three operand stages) while wg128 <= cus <= 4 * wg128,
+//   else NARROW (64 queries) while wg128 < 256, else WIDE (128 queries); both of the latter with two stages.
+// forced_kernel != 0: that kind or the empty plan (kernel 0, `refused` says why) - an MFMA kind outside what the MFMA kernels
+// serve, or an unknown value.  cus 0 = the CU count of the current device (asked only where the rule needs it).
+enum ContextAttnKernel
+{
+    CTX_ATTN_RULE = 0,
+    CTX_ATTN_WAVE = 1,
+    CTX_ATTN_MFMA_NARROW = 2,
+    CTX_ATTN_MFMA_WIDE = 3,
+    CTX_ATTN_MFMA_PAIRED = 4
+};
+struct ContextAttnPlan
+{
+    int32_t kernel = 0;                 // the kind that runs; 0 = refused
+    int32_t query_block = 0;            // queries per workgroup: 4, 64 or 128 (PAIRED: two blocks of 64)
+    int32_t stages = 0;                 // operand stages in LDS: 2 or 3 (WAVE: 0)
+    uint32_t grid[3] = {0, 0, 0};       // workgroups
+    int32_t threads = 0;
+    size_t lds_bytes = 0;               // dynamic LDS
+    const char* refused = nullptr;
+};
+ContextAttnPlan context_attention_plan(int32_t head_size, int32_t seq, int32_t batch, int32_t num_heads, bool has_workspace,
+    bool score_scale_positive, int32_t cus = 0, int32_t forced_kernel = 0);
 // cu[0] = 0, cu[b + 1] = cu[b] + lens[b]  (device, one tiny launch; packed-input bookkeeping)
 int launch_exclusive_scan_i32(int32_t* cu, const int32_t* lens, int32_t n, hipStream_t stream);
 // out[b, :] = hidden[rows[b], :]  (fp16 rows; the packed-input flavour of gather_last_token)

@@ -214,7 +214,39 @@ int32_t tllm_attention_context(const tllm_attention_params_t* q, tllm_stream_t s
     p.block_pointers = q->block_pointers;
     p.tokens_per_block = q->tokens_per_block;
     p.max_blocks_per_seq = q->max_blocks_per_seq;
+    p.kernel = q->context_kernel;
     return launch_context_attention(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_attention_context_layout(const tllm_attention_params_t* q, int32_t cus, int32_t* kind, int32_t* query_block,
+    int32_t* stages, int32_t* workgroups)
+{
+    static_assert(TLLM_CTX_ATTN_WAVE == CTX_ATTN_WAVE && TLLM_CTX_ATTN_MFMA_NARROW == CTX_ATTN_MFMA_NARROW
+            && TLLM_CTX_ATTN_MFMA_WIDE == CTX_ATTN_MFMA_WIDE && TLLM_CTX_ATTN_MFMA_PAIRED == CTX_ATTN_MFMA_PAIRED,
+        "the header's kinds are the launcher's");
+    if (!q || cus < 0)
+    {
+        set_error("tllm_attention_context_layout: bad arguments");
+        return 1;
+    }
+    // the score scale as tllm_attention_context computes it: the launcher's own plan, one statement of the rule
+    const float inv_sqrt_dh = 1.f / (sqrtf((float) q->head_size) * (q->q_scaling != 0.f ? q->q_scaling : 1.f));
+    const ContextAttnPlan plan = context_attention_plan(q->head_size, q->seq, q->batch, q->num_heads, q->workspace != nullptr,
+        inv_sqrt_dh > 0.f, cus, q->context_kernel);
+    if (plan.kernel == 0)
+    {
+        set_error("tllm_attention_context_layout: kernel %d refused: %s", q->context_kernel, plan.refused ? plan.refused : "no plan");
+        return 1;
+    }
+    if (kind)
+        *kind = plan.kernel;
+    if (query_block)
+        *query_block = plan.query_block;
+    if (stages)
+        *stages = plan.stages;
+    if (workgroups)
+        *workgroups = (int32_t) (plan.grid[0] * plan.grid[1] * plan.grid[2]);
+    return 0;
 }
 
 static GemvParams gemv_params(const tllm_gemv_params_t* q)

@@ -20,6 +20,8 @@ FLOAT, HALF, INT8, INT32, BOOL, UINT8, FP8 = 0, 1, 2, 3, 4, 5, 6
 PF_FLOAT16, PF_FLOAT32, PF_FLOAT64, PF_INT8, PF_INT16, PF_INT32, PF_CHAR, PF_DIMS, PF_UNKNOWN = range(9)
 
 MAX_DIMS = 8
+# TLLM_CTX_ATTN_* (tllm_attention_params_t::context_kernel; 0 = the launcher's rule)
+CTX_ATTN_WAVE, CTX_ATTN_MFMA_NARROW, CTX_ATTN_MFMA_WIDE, CTX_ATTN_MFMA_PAIRED = 1, 2, 3, 4
 
 
 class Dims(ctypes.Structure):
@@ -77,7 +79,8 @@ class AttentionParams(ctypes.Structure):
                 ('cache_indirection', ctypes.c_void_p), ('beam_width', ctypes.c_int32), ('cache_seq_stride', ctypes.c_int32),
                 ('block_pointers', ctypes.c_void_p), ('tokens_per_block', ctypes.c_int32), ('max_blocks_per_seq', ctypes.c_int32),
                 ('cu_seqlens', ctypes.c_void_p), ('rows_per_group', ctypes.c_int32), ('q_heads_per_workgroup', ctypes.c_int32),
-                ('combine_launch', ctypes.c_int32), ('tail_quant_scale', ctypes.c_void_p), ('tail_out_q8', ctypes.c_void_p),
+                ('combine_launch', ctypes.c_int32), ('context_kernel', ctypes.c_int32), ('tail_quant_scale', ctypes.c_void_p),
+                ('tail_out_q8', ctypes.c_void_p),
                 ('out_q8', ctypes.c_void_p), ('out_q_scale', ctypes.c_void_p), ('out', ctypes.c_void_p),
                 ('workspace', ctypes.c_void_p)]
 
@@ -151,6 +154,8 @@ def load_library():
     lib.tllm_attention_context.restype = c.c_int32
     lib.tllm_attention_decode_layout.argtypes = [c.POINTER(AttentionParams)] + [c.POINTER(c.c_int32)] * 4
     lib.tllm_attention_decode_layout.restype = c.c_int32
+    lib.tllm_attention_context_layout.argtypes = [c.POINTER(AttentionParams), c.c_int32] + [c.POINTER(c.c_int32)] * 4
+    lib.tllm_attention_context_layout.restype = c.c_int32
     lib.tllm_symmetric_quantize_last_axis.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int32, c.c_void_p,
                                                       c.c_void_p, c.c_void_p]
     lib.tllm_symmetric_quantize_last_axis.restype = c.c_int32
