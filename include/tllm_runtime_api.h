@@ -167,6 +167,36 @@ int32_t tllm_session_get_step_epoch(tllm_session_t s, uint32_t* epoch, tllm_stre
  * T/tests/model/test_llama.py:300-354).  Does not touch the KV cache or the step counters. */
 int32_t tllm_session_force_tokens(tllm_session_t s, const int32_t* ids, tllm_stream_t stream);
 
+/* Append n tokens per sequence to the live cache in ONE prefill pass (multi-turn chat, chunked prefill, verification of n known
+ * tokens): the parallel form of  for i < n: tllm_session_force_tokens(ids[:, i]); tllm_session_step(1).
+ *   ids  HOST int32 [B, n].
+ * With p_b = sequence_length[b]: appended token i replaces (i = 0) or extends from the pending token the last sampler chose - it
+ * occupies output slot and cache slot p_b + i at rotary position p_b + i - (max_input_len - input_lengths[b]) and sees every
+ * unmasked slot < p_b plus the appended tokens 0 .. i (kernels/append_attn.hip; DESIGN.md section 7c states the numeric rule).
+ * A caller who wants the model's own pending token kept passes it as ids[:, 0].  Afterwards: sequence_length += n, finished = 0,
+ * the fp32 logits of the last appended token are in the session (tllm_session_get_logits), and the sampler (greedy or the
+ * configured one) has chosen a new pending token and prepared the next step's RoPE row and input row exactly as after
+ * tllm_session_context; masked_tokens and input_lengths are unchanged; a captured step graph stays valid (it reads device state
+ * only).  The pass is the prefill schedule on B * n rows with the append attention in place of the context attention.
+ * Reads sequence_length back, so it synchronises the stream.  Refused, with nothing enqueued: before setup; before any context
+ * (every sequence_length must be >= max_input_len); n < 1, n > max_input_len (the activation buffers are sized for that) or
+ * sequence_length[b] + n > max_seq_len; beam_width > 1, the paged cache, tensor parallel > 1; a token id outside [0, vocab_size).
+ * Packed-input sessions are accepted (the appended rows are dense either way).  Not built: a different n per sequence, scoring
+ * of the appended tokens. */
+int32_t tllm_session_append(tllm_session_t s, const int32_t* ids, int32_t n, tllm_stream_t stream);
+/* tllm_session_append, then up to max_new_tokens generated tokens as tllm_session_generate produces them (the first by the
+ * append's sampler launch, the rest by generation steps from the graph, the finished flags polled every 32 steps).
+ *   output_ids  HOST int32 [B, max_seq_len]: the session's token record; from slot sequence_length[b] + n + (tokens produced) on,
+ *               and behind a sequence's first end_id among the new tokens, the row is filled with end_id (pad_id when end_id < 0).
+ * max_new_tokens >= 1 and sequence_length[b] + n + max_new_tokens <= max_seq_len.  When a bounded wait of the one-launch step
+ * expires, the call fails and the error says that the session's results are invalid: unlike tllm_session_generate it cannot
+ * repeat the request, because the append has consumed the state it started from. */
+int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32_t n, int32_t max_new_tokens, int32_t end_id,
+    int32_t pad_id, int32_t* output_ids, tllm_stream_t stream);
+/* Attention launches tllm_session_append has enqueued since setup, by kernel (one per layer and call): *wave, *mfma (either may
+ * be NULL).  For tests: which kernel served a chunk. */
+int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* mfma);
+
 /* Top-k / top-p sampling with temperature, repetition / presence penalty and minimum length, on the device inside the
  * generation step (the reference's dynamic decoder with beam_width 1: PY/runtime/generation.py:299-345, 949-961 ->
  * layers/baseSamplingLayer.cpp:171-248, layers/topKSamplingLayer.cu, K/samplingTopKKernels.cu, samplingTopPKernels.cu,
@@ -486,6 +516,49 @@ int32_t tllm_attention_decode_layout(const tllm_attention_params_t* p, int32_t* 
 #define TLLM_CTX_ATTN_MFMA_PAIRED 4
 int32_t tllm_attention_context_layout(const tllm_attention_params_t* p, int32_t cus, int32_t* kind, int32_t* query_block,
     int32_t* stages, int32_t* workgroups);
+
+/* Kernel-level entry of the append attention (kernels/append_attn.hip; the rule is DESIGN.md section 7c, restated in numpy float64
+ * in tensorrt_llm/runtime/append_ref.py): n new tokens per sequence onto a live cache, the parallel form of n decode steps.
+ * With p_b = sequence_length[b]: appended token i of sequence b gets RoPE at position p_b + i - (max_input_len -
+ * input_lengths[b]), its k and v go to cache slot p_b + i by the store rule of the cache type, and its query sees every slot
+ * t < p_b with masked_tokens[b][t] == 0 - read as the decode launch reads them - plus the appended tokens 0 .. i, whose k and v
+ * enter un-quantised.  sequence_length is NOT advanced (the session's advance launch does that).  Two launches: RoPE + cache
+ * write, then the attention.
+ *   qkv    fp16 [B, n, (H + 2 Hkv) * Dh], rows [ q | k | v ]; q and k are rewritten in place with RoPE applied;
+ *   cache  [B, 2, Hkv, Smax, Dh] fp16 / int8 / fp8 E4M3 (linear only);   out  fp16 [B, n, H * Dh].
+ * max_past is the caller's promise max_past >= every sequence_length[b]: max_past + n > max_seq_len is refused with nothing
+ * launched; on the device every cache store is guarded by slot < max_seq_len and every load index is clamped all the same.
+ * append_kernel: TLLM_APPEND_ATTN_WAVE (one wave per query: every n, head sizes 32 / 64 / 128 / 256) or TLLM_APPEND_ATTN_MFMA (64
+ * queries per workgroup, head sizes 64 / 128, n >= 16); 0 = the launcher's rule (MFMA where it serves).  A forced value runs exactly
+ * that kernel or the call returns non-zero with tllm_last_error() set and nothing launched - never a substitute.
+ * A struct of its own (tllm_attention_params_t keeps its layout); every field not needed is 0 / NULL (memset the struct). */
+#define TLLM_APPEND_ATTN_WAVE 1
+#define TLLM_APPEND_ATTN_MFMA 2
+typedef struct
+{
+    int32_t batch;
+    int32_t n;             /* tokens appended per sequence, the same for all */
+    int32_t num_heads, num_kv_heads, head_size; /* num_kv_heads 0 = num_heads */
+    int32_t rotary_dim, neox;
+    float q_scaling;       /* scores * 1 / (sqrt(Dh) * q_scaling); 0 = 1 */
+    int32_t kv_cache_type; /* TLLM_HALF (or 0), TLLM_INT8, TLLM_FP8 */
+    int32_t max_seq_len;   /* cache capacity Smax */
+    int32_t max_input_len; /* padded prompt length */
+    int32_t max_past;
+    int32_t append_kernel;
+    void* qkv;
+    void* kv_cache;
+    const int32_t* sequence_length; /* device int32 [B]: the past lengths p_b, may differ per sequence */
+    const int32_t* input_lengths;   /* device int32 [B] */
+    const int32_t* masked_tokens;   /* device int32 [B, Smax] or NULL */
+    const float* kv_scale_orig_quant; /* device f32 [1] (int8 / fp8 cache) */
+    const float* kv_scale_quant_orig; /* device f32 [1] (int8 / fp8 cache) */
+    void* out;
+} tllm_attention_append_params_t;
+int32_t tllm_attention_append(const tllm_attention_append_params_t* p, tllm_stream_t stream);
+/* the attention kernel tllm_attention_append would run for p (n, head_size and append_kernel are read; no pointer is followed; no
+ * GPU needed): TLLM_APPEND_ATTN_WAVE or _MFMA in *kind.  Non-zero: a forced append_kernel the launch cannot run. */
+int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* p, int32_t* kind);
 
 #ifdef __cplusplus
 }

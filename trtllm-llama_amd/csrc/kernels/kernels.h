@@ -402,6 +402,47 @@ int launch_gather_rows(void* out, const void* hidden, const int32_t* rows, int32
 int launch_context_attention(const ContextAttnParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
+// Append attention (kernels/append_attn.hip): n new tokens per sequence onto a live cache - RoPE + cache
+// write of the n rows, then their attention over the unmasked slots < sequence_length[b] (read as the decode kernel reads them)
+// and, causally, over the appended rows themselves (un-quantised, from the QKV buffer).  The parallel form of n decode steps.
+// ---------------------------------------------------------------------------------------------
+enum AppendAttnKernel
+{
+    APPEND_ATTN_RULE = 0, // the MFMA kernel where it serves (head size 64 / 128, n >= 16), else one wave per query
+    APPEND_ATTN_WAVE = 1, // one wave per query: every n, head sizes 32 / 64 / 128 / 256
+    APPEND_ATTN_MFMA = 2  // 64 queries per workgroup, online soft-max over 64-key blocks
+};
+struct AppendAttnParams
+{
+    int32_t batch = 0, n = 0; // n: tokens appended per sequence, the same for all
+    int32_t num_heads = 0, num_kv_heads = 0, head_size = 0; // num_kv_heads as MmhaParams (0 = num_heads)
+    int32_t rotary_dim = 0, neox = 1;
+    float inv_sqrt_dh = 1.f;
+    int32_t kv_dtype = DT_HALF; // DT_HALF, DT_INT8 or DT_FP8 (the one-byte types with both scales)
+    int32_t max_seq_len = 0;    // cache capacity Smax
+    int32_t max_input_len = 0;  // padded prompt length: rotary position of slot t = t - (max_input_len - input_lengths[b])
+    // >= every sequence_length[b], promised by the caller: max_past + n > max_seq_len is refused with nothing enqueued.  On the
+    // device every cache store is still guarded by slot < Smax and every load index clamped
+    int32_t max_past = 0;
+    void* qkv = nullptr;      // fp16 [B, n, (H + 2 Hkv) * Dh]; q and k rewritten in place with RoPE applied
+    void* kv_cache = nullptr; // [B, 2, Hkv, Smax, Dh]
+    const int32_t* sequence_length = nullptr; // [B] device: the past lengths p_b (may differ per sequence); not written
+    const int32_t* input_lengths = nullptr;   // [B] device
+    const int32_t* masked_tokens = nullptr;   // [B, Smax] device or null
+    const float* kv_scale_orig_quant = nullptr;
+    const float* kv_scale_quant_orig = nullptr;
+    const float* rope_table = nullptr; // f32 [rope_table_len, rotary_dim / 2, 2]
+    int32_t rope_table_len = 0;
+    void* out = nullptr; // fp16 [B, n, H * Dh]
+    int32_t kernel = 0;  // an AppendAttnKernel; a forced kind runs exactly that kernel or the launch is refused, never a substitute
+};
+// the attention kernel a launch runs (APPEND_ATTN_WAVE / _MFMA), 0 = refused (*refused says why)
+int append_attention_kernel(int32_t head_size, int32_t n, int32_t forced_kernel, const char** refused = nullptr);
+int launch_append_attention(const AppendAttnParams& p, hipStream_t stream);
+// sequence_length[b] += n; finished[b] = 0 (finished may be null): one workgroup, a launch of its own
+int launch_append_advance(int32_t* sequence_length, int32_t* finished, int32_t batch, int32_t n, hipStream_t stream);
+
+// ---------------------------------------------------------------------------------------------
 // MFMA GEMMs for M > 8 (prefill): C[m,n] = sum_k A[m,k] * B[n,k].
 // ---------------------------------------------------------------------------------------------
 struct GemmParams

@@ -249,6 +249,69 @@ int32_t tllm_attention_context_layout(const tllm_attention_params_t* q, int32_t 
     return 0;
 }
 
+int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* q, int32_t* kind)
+{
+    static_assert(TLLM_APPEND_ATTN_WAVE == APPEND_ATTN_WAVE && TLLM_APPEND_ATTN_MFMA == APPEND_ATTN_MFMA, "the header's kinds are the launcher's");
+    if (!q)
+    {
+        set_error("tllm_attention_append_layout: bad arguments");
+        return 1;
+    }
+    const char* why = nullptr;
+    const int k = append_attention_kernel(q->head_size, q->n, q->append_kernel, &why);
+    if (k == 0)
+    {
+        set_error("tllm_attention_append_layout: kernel %d refused: %s", q->append_kernel, why ? why : "no plan");
+        return 1;
+    }
+    if (kind)
+        *kind = k;
+    return 0;
+}
+
+int32_t tllm_attention_append(const tllm_attention_append_params_t* q, tllm_stream_t stream)
+{
+    if (!q || q->batch < 1 || q->n < 1 || q->num_heads < 1 || q->head_size < 1 || q->max_seq_len < 1)
+    {
+        set_error("tllm_attention_append: bad arguments (batch, n, num_heads, head_size, max_seq_len)");
+        return 1;
+    }
+    if (q->kv_cache_type != 0 && q->kv_cache_type != TLLM_HALF && q->kv_cache_type != TLLM_INT8 && q->kv_cache_type != TLLM_FP8)
+    {
+        set_error("tllm_attention_append: kv_cache_type %d is not TLLM_HALF, TLLM_INT8 or TLLM_FP8", q->kv_cache_type);
+        return 1;
+    }
+    AppendAttnParams p;
+    p.batch = q->batch;
+    p.n = q->n;
+    p.num_heads = q->num_heads;
+    p.num_kv_heads = q->num_kv_heads;
+    p.head_size = q->head_size;
+    p.rotary_dim = q->rotary_dim;
+    p.neox = q->neox;
+    p.inv_sqrt_dh = 1.f / (sqrtf((float) q->head_size) * (q->q_scaling != 0.f ? q->q_scaling : 1.f));
+    p.kv_dtype = q->kv_cache_type ? q->kv_cache_type : DT_HALF; // (TLLM_* and DT_* share their values)
+    p.max_seq_len = q->max_seq_len;
+    p.max_input_len = q->max_input_len;
+    p.max_past = q->max_past;
+    p.kernel = q->append_kernel;
+    p.qkv = q->qkv;
+    p.kv_cache = q->kv_cache;
+    p.sequence_length = q->sequence_length;
+    p.input_lengths = q->input_lengths;
+    p.masked_tokens = q->masked_tokens;
+    p.kv_scale_orig_quant = q->kv_scale_orig_quant;
+    p.kv_scale_quant_orig = q->kv_scale_quant_orig;
+    p.out = q->out;
+    if (p.rotary_dim > 0)
+    {
+        p.rope_table = tllm::plugins::rope_table(p.rotary_dim, p.max_seq_len, &p.rope_table_len);
+        if (!p.rope_table)
+            return 1;
+    }
+    return launch_append_attention(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
 static GemvParams gemv_params(const tllm_gemv_params_t* q)
 {
     GemvParams p;

@@ -86,6 +86,7 @@ static int upload_prompt(tllm_session_t s, const int32_t* input_ids, const int32
     HIP_OK(hipMemcpyAsync(s->masked, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(s->out_ids, out.data(), out.size() * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipStreamSynchronize(st)); // the host vectors above go out of scope
+    s->has_context = true;
     return 0;
 }
 
@@ -201,6 +202,9 @@ int32_t tllm_session_fake_context(tllm_session_t s, int32_t length, uint32_t see
 
 static int32_t generate_once(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths, int32_t max_new_tokens,
     int32_t end_id, int32_t pad_id, int32_t* output_ids, tllm_stream_t stream);
+static int32_t generate_steps(tllm_session_t s, int32_t max_new_tokens, int32_t end_id, int* produced_out, tllm_stream_t stream);
+static void fill_output_tail(tllm_session_t s, int32_t* output_ids, const std::vector<int>& first, int produced, int32_t end_id,
+    int32_t pad_id);
 
 int32_t tllm_session_generate(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
     int32_t max_new_tokens, int32_t end_id, int32_t pad_id, int32_t* output_ids, tllm_stream_t stream)
@@ -257,11 +261,24 @@ static int32_t generate_once(tllm_session_t s, const int32_t* input_ids, const i
         set_error("tllm_session_generate: max_new_tokens %d exceeds setup's %d", max_new_tokens, s->max_new);
         return 1;
     }
-    hipStream_t st = s->pick(stream);
     s->end_id = end_id;
     s->drop_graph(); // end_id is baked into the captured sampler node
     RUN(tllm_session_context(s, input_ids, input_lengths, stream));
-    int produced = max_new_tokens > 0 ? 1 : 0; // tokens generated per sequence (the prompt pass yields the first)
+    int produced = 0;
+    RUN(generate_steps(s, max_new_tokens, end_id, &produced, stream));
+    if (s->beam > 1)
+        return tllm_session_get_beam_output(s, output_ids, nullptr, stream);
+    RUN(tllm_session_get_output_ids(s, output_ids, stream));
+    fill_output_tail(s, output_ids, std::vector<int>(s->B, s->max_in), produced, end_id, pad_id);
+    return 0;
+}
+
+// The generation steps behind a sampler launch that has produced the first of max_new_tokens tokens (the prompt pass, or an
+// append): *produced = tokens generated per sequence, that first one included.
+static int32_t generate_steps(tllm_session_t s, int32_t max_new_tokens, int32_t end_id, int* produced_out, tllm_stream_t stream)
+{
+    hipStream_t st = s->pick(stream);
+    int produced = max_new_tokens > 0 ? 1 : 0; // tokens generated per sequence (the pass before yields the first)
     if (max_new_tokens > 1)
     {
         // first generation step eagerly (also warms lazily-initialised state), the rest from the graph
@@ -292,25 +309,154 @@ static int32_t generate_once(tllm_session_t s, const int32_t* input_ids, const i
             }
         }
     }
-    if (s->beam > 1)
-        return tllm_session_get_beam_output(s, output_ids, nullptr, stream);
-    RUN(tllm_session_get_output_ids(s, output_ids, stream));
-    // The reference runs gather_tree for beam_width 1 too (generation.py:990-994; K/decodingKernels.cu:130-156): everything
-    // after a sequence's first end token, and the tail no step wrote because every sequence had finished, is end_id - not the
-    // 0 (<unk>) the buffer was initialised with.  Without an end token (benchmarks) the unused tail is pad_id.
+    *produced_out = produced;
+    return 0;
+}
+
+// The reference runs gather_tree for beam_width 1 too (generation.py:990-994; K/decodingKernels.cu:130-156): everything
+// after a sequence's first end token, and the tail no step wrote because every sequence had finished, is end_id - not the
+// 0 (<unk>) the buffer was initialised with.  Without an end token (benchmarks) the unused tail is pad_id.
+// first[b]: the slot of sequence b's first generated token of this request (max_input_len behind a prompt).
+static void fill_output_tail(tllm_session_t s, int32_t* output_ids, const std::vector<int>& first, int produced, int32_t end_id,
+    int32_t pad_id)
+{
     const int32_t fill = end_id >= 0 ? end_id : pad_id;
     for (int b = 0; b < s->B; ++b)
     {
         int32_t* o = output_ids + (size_t) b * s->Smax;
         bool done = false;
-        for (int t = s->max_in; t < s->Smax; ++t)
+        for (int t = first[b]; t < s->Smax; ++t)
         {
-            if (done || t >= s->max_in + produced)
+            if (done || t >= first[b] + produced)
                 o[t] = fill;
             else if (end_id >= 0 && o[t] == end_id)
                 done = true;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------ append
+// The checks of tllm_session_append (nothing is enqueued before every one has passed), then: the ids to the device and into the
+// token record, the append pass, the advance launch, the sampler.  past[b] = sequence_length[b] before the call.
+static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, int32_t reserve_new,
+    std::vector<int32_t>& past, tllm_stream_t stream)
+{
+    if (!s || !s->B)
+    {
+        set_error("%s: call tllm_session_setup first", who);
+        return 1;
+    }
+    if (s->beam > 1 || s->paged_kv || s->tp > 1)
+    {
+        set_error("%s: not built for beam search, the paged cache or tensor parallelism (beam_width %d, paged %d, tp %d)", who, s->beam,
+            s->paged_kv ? 1 : 0, s->tp);
+        return 1;
+    }
+    if (!ids)
+    {
+        set_error("%s: null argument", who);
+        return 1;
+    }
+    if (n < 1 || n > s->max_in)
+    {
+        set_error("%s: n %d out of range [1, max_input_len %d] (the activation buffers are sized for the prompt)", who, n, s->max_in);
+        return 1;
+    }
+    if (!s->has_context)
+    {
+        set_error("%s: no context yet - the cache is not live (call tllm_session_context first)", who);
+        return 1;
+    }
+    const int B = s->B, Smax = s->Smax;
+    for (size_t k = 0; k < (size_t) B * n; ++k)
+        if (ids[k] < 0 || ids[k] >= s->vocab)
+        {
+            set_error("%s: token id %d (sequence %d, token %d) outside [0, %d)", who, ids[k], (int) (k / n), (int) (k % n), s->vocab);
+            return 1;
+        }
+    hipStream_t st = s->pick(stream);
+    past.assign(B, 0);
+    HIP_OK(hipMemcpyAsync(past.data(), s->seq_len, (size_t) B * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    RUN(s->check_comm());
+    int max_past = 0;
+    for (int b = 0; b < B; ++b)
+    {
+        if (past[b] < s->max_in)
+        {
+            set_error("%s: sequence_length[%d] = %d is below max_input_len %d - no context has run", who, b, past[b], s->max_in);
+            return 1;
+        }
+        if ((int64_t) past[b] + n + reserve_new > Smax)
+        {
+            set_error("%s: sequence %d: %d slots in use + %d appended + %d new exceed the cache capacity %d", who, b, past[b], n,
+                reserve_new, Smax);
+            return 1;
+        }
+        max_past = std::max(max_past, past[b]);
+    }
+    HIP_OK(hipMemcpyAsync(s->ids_in, ids, (size_t) B * n * 4, hipMemcpyHostToDevice, st));
+    for (int b = 0; b < B; ++b)
+        HIP_OK(hipMemcpyAsync(s->out_ids + (size_t) b * Smax + past[b], ids + (size_t) b * n, (size_t) n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st)); // the caller's buffer may go out of scope
+    RUN(s->run_append(n, max_past, st));
+    RUN(launch_append_advance(s->seq_len, s->finished, B, n, st) ? 1 : 0);
+    RUN(s->run_sampler(0, st));
+    return 0;
+}
+
+int32_t tllm_session_append(tllm_session_t s, const int32_t* ids, int32_t n, tllm_stream_t stream)
+{
+    std::vector<int32_t> past;
+    return append_enqueue(s, "tllm_session_append", ids, n, 0, past, stream) ? 1 : 0;
+}
+
+int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32_t n, int32_t max_new_tokens, int32_t end_id,
+    int32_t pad_id, int32_t* output_ids, tllm_stream_t stream)
+{
+    const char* who = "tllm_session_append_generate";
+    if (!s || !s->B || !output_ids || max_new_tokens < 1)
+    {
+        set_error("%s: bad arguments (max_new_tokens >= 1, output_ids set) / setup not called", who);
+        return 1;
+    }
+    if (end_id != s->end_id)
+    {
+        s->end_id = end_id;
+        s->drop_graph(); // end_id is baked into the captured sampler node
+    }
+    std::vector<int32_t> past;
+    // the last of the max_new_tokens tokens is chosen by a sampler that writes slot past + n + max_new_tokens - 1
+    int rc = append_enqueue(s, who, ids, n, max_new_tokens, past, stream);
+    int produced = 0;
+    if (!rc)
+        rc = generate_steps(s, max_new_tokens, end_id, &produced, stream);
+    if (!rc)
+        rc = tllm_session_get_output_ids(s, output_ids, stream);
+    if (rc == kFusedTimedOut)
+        set_error("%s: a bounded in-launch wait of the generation step expired: the session's tokens and cache behind it are invalid, "
+                  "and the append has consumed the state the call started from - run the conversation again from tllm_session_context",
+            who);
+    if (rc)
+        return 1;
+    std::vector<int> first(s->B);
+    for (int b = 0; b < s->B; ++b)
+        first[b] = past[b] + n;
+    fill_output_tail(s, output_ids, first, produced, end_id, pad_id);
+    return 0;
+}
+
+int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* mfma)
+{
+    if (!s || !s->B)
+    {
+        set_error("tllm_session_append_launches: setup not called");
+        return 1;
+    }
+    if (wave)
+        *wave = s->append_wave_launches;
+    if (mfma)
+        *mfma = s->append_mfma_launches;
     return 0;
 }
 

@@ -180,6 +180,9 @@ struct tllm_session
     void* ctx_ws = nullptr; // V^T scratch of the MFMA context attention
     int32_t *ids_in = nullptr, *cur_ids = nullptr, *out_ids = nullptr, *seq_len = nullptr, *in_len = nullptr,
             *masked = nullptr, *finished = nullptr, *last_tok = nullptr;
+    bool has_context = false;       // a prompt has been uploaded since setup (tllm_session_append needs a live cache)
+    int32_t* append_last = nullptr; // [B]: n for every sequence (the gather of the appended rows' last one)
+    int64_t append_wave_launches = 0, append_mfma_launches = 0; // attention launches of tllm_session_append since setup, by kernel
     const float* rope = nullptr;
     int rope_len = 0;
     float* rope_row = nullptr; // [B, Dh/2, 2]: cos/sin row of the next generation step (written by the sampler)
@@ -316,7 +319,12 @@ struct tllm_session
     int context_attention(const Layer& L, bool q_in_attn, hipStream_t st);
     int context_gate_up(const Layer& L, int M, const void* a_in, const void** p_in, hipStream_t st);
     int context_proj_residual(const Linear& L, int M, const void* in, bool fuse_res, hipStream_t st);
+    // one decoder layer of the prefill schedule on M rows; append_n > 0: with the append attention (n rows per sequence)
+    int context_layer(Layer& L, int M, int append_n, int max_past, hipStream_t st);
     int run_context(hipStream_t st);
+    // tllm_session_append: the prefill schedule on B * n appended rows (ids in ids_in) onto the live cache, head on row n - 1
+    int append_attention(const Layer& L, int n, int max_past, hipStream_t st);
+    int run_append(int n, int max_past, hipStream_t st);
     // score: enqueue ln_f -> lm_head in row chunks -> partial records (-> all-gather) -> merge on the rows of x that have a next
     // token (between run_context and the sampler, which reuses x); collect: after the stream is synchronised, scatter to the host
     int score_enqueue(const int32_t* input_ids, const int32_t* input_lengths, hipStream_t st);

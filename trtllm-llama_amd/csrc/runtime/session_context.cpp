@@ -196,46 +196,105 @@ int tllm_session::context_proj_residual(const Linear& L, int M, const void* in, 
     return launch_add(x, x, tmp, (int64_t) M * hidden, st);
 }
 
+// ------------------------------------------------------------------------------------------ one layer
+// One decoder layer of the prefill schedule on the M rows of x.  append_n == 0: the prompt's layer (context attention);
+// append_n > 0: the layer of an append pass on B * append_n rows (append attention onto the live cache, max_past as
+// AppendAttnParams) - everything but the attention launch is the same code.
+int tllm_session::context_layer(Layer& L, int M, int append_n, int max_past, hipStream_t st)
+{
+    const int D = hidden;
+    const void* a_in = sq ? (const void*) q8 : tmp; // what context_norm leaves
+    // (weight-only: gemm_woq.hip adds the residual in its epilogue too - same two roundings; its own serve conditions)
+    const bool woq_w = L.dense.wtype == W_INT8_WOQ || L.dense.wtype == W_INT4_WOQ;
+    const bool fuse_res = tp == 1 && !force_comm && M >= 32 && D % 8 == 0
+        && (woq_w ? (L.dense.K % 64 == 0 && L.proj.K % 64 == 0)
+                  : ((L.dense.wtype == W_INT8_SQ || L.dense.wtype == W_FP16)
+                      && (L.dense.K * (L.dense.wtype == W_FP16 ? 2 : 1)) % 128 == 0
+                      && (L.proj.K * (L.proj.wtype == W_FP16 ? 2 : 1)) % 128 == 0));
+    // --- attention block
+    RUN(context_norm(M, L.ln1, L.ln1_scale, st));
+    RUN(gemm(L.qkv, M, a_in, qkv, DT_HALF, st));
+    // SmoothQuant static: the O-projection's input quantiser rides in the context attention's epilogue (padded inputs; with
+    // packed inputs M counts real tokens only and the pass below covers exactly those).  The append attention has no such
+    // epilogue: the quantiser pass follows it
+    const bool q_in_attn = sq && !per_token && !packed && append_n == 0;
+    if (append_n > 0)
+        RUN(append_attention(L, append_n, max_past, st));
+    else
+        RUN(context_attention(L, q_in_attn, st));
+    if (sq && per_token)
+        RUN(launch_quantize_per_token(q8, ctx, DT_HALF, M, Dr, qscale, st));
+    else if (sq && !q_in_attn)
+        RUN(launch_quantize_tensor(q8, ctx, DT_HALF, (int64_t) M * Dr, L.attn_qscale, st));
+    RUN(context_proj_residual(L.dense, M, sq ? (const void*) q8 : ctx, fuse_res, st));
+    // --- MLP block
+    RUN(context_norm(M, L.ln2, L.ln2_scale, st));
+    const void* p_in = nullptr; // inter_buf or q8, as the path through gate|up leaves it
+    RUN(context_gate_up(L, M, a_in, &p_in, st));
+    RUN(context_proj_residual(L.proj, M, p_in, fuse_res, st));
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ context step
 int tllm_session::run_context(hipStream_t st)
 {
     const int S = max_in, M = packed ? ctx_tokens : Bc * S, D = hidden;
-    const void* a_in = sq ? (const void*) q8 : tmp; // what context_norm leaves
     RUN(launch_embedding(x, ids_in, emb, M, D, vocab, st));
     for (int li = 0; li < num_layers; ++li)
-    {
-        Layer& L = layers[li];
-        // (weight-only: gemm_woq.hip adds the residual in its epilogue too - same two roundings; its own serve conditions)
-        const bool woq_w = L.dense.wtype == W_INT8_WOQ || L.dense.wtype == W_INT4_WOQ;
-        const bool fuse_res = tp == 1 && !force_comm && M >= 32 && D % 8 == 0
-            && (woq_w ? (L.dense.K % 64 == 0 && L.proj.K % 64 == 0)
-                      : ((L.dense.wtype == W_INT8_SQ || L.dense.wtype == W_FP16)
-                          && (L.dense.K * (L.dense.wtype == W_FP16 ? 2 : 1)) % 128 == 0
-                          && (L.proj.K * (L.proj.wtype == W_FP16 ? 2 : 1)) % 128 == 0));
-        // --- attention block
-        RUN(context_norm(M, L.ln1, L.ln1_scale, st));
-        RUN(gemm(L.qkv, M, a_in, qkv, DT_HALF, st));
-        // SmoothQuant static: the O-projection's input quantiser rides in the attention's epilogue (padded inputs; with
-        // packed inputs M counts real tokens only and the pass below covers exactly those)
-        const bool q_in_attn = sq && !per_token && !packed;
-        RUN(context_attention(L, q_in_attn, st));
-        if (sq && per_token)
-            RUN(launch_quantize_per_token(q8, ctx, DT_HALF, M, Dr, qscale, st));
-        else if (sq && !q_in_attn)
-            RUN(launch_quantize_tensor(q8, ctx, DT_HALF, (int64_t) M * Dr, L.attn_qscale, st));
-        RUN(context_proj_residual(L.dense, M, sq ? (const void*) q8 : ctx, fuse_res, st));
-        // --- MLP block
-        RUN(context_norm(M, L.ln2, L.ln2_scale, st));
-        const void* p_in = nullptr; // inter_buf or q8, as the path through gate|up leaves it
-        RUN(context_gate_up(L, M, a_in, &p_in, st));
-        RUN(context_proj_residual(L.proj, M, p_in, fuse_res, st));
-    }
+        RUN(context_layer(layers[li], M, 0, 0, st));
     // head: last real token of every sequence -> ln_f -> lm_head -> fp32 logits  (Q/llama_model.py:272-279)
     if (packed)
         RUN(launch_gather_rows(last_hidden, x, last_rows, Bc, D, st));
     else
         RUN(launch_gather_last_token(last_hidden, x, last_tok, Bc, S, D, st));
     RUN(run_head(last_hidden, Bc, st));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ append
+int tllm_session::append_attention(const Layer& L, int n, int max_past, hipStream_t st)
+{
+    AppendAttnParams a;
+    a.batch = B;
+    a.n = n;
+    a.num_heads = Hr;
+    a.num_kv_heads = Hkvr;
+    a.head_size = Dh;
+    a.rotary_dim = Dh;
+    a.neox = neox;
+    a.inv_sqrt_dh = 1.f / sqrtf((float) Dh);
+    a.kv_dtype = kv_dtype;
+    a.max_seq_len = Smax;
+    a.max_input_len = max_in;
+    a.max_past = max_past;
+    a.qkv = qkv;
+    a.kv_cache = L.kv;
+    a.sequence_length = seq_len;
+    a.input_lengths = in_len;
+    a.masked_tokens = masked;
+    a.kv_scale_orig_quant = L.kv_oq;
+    a.kv_scale_quant_orig = L.kv_qo;
+    a.rope_table = rope;
+    a.rope_table_len = rope_len;
+    a.out = ctx;
+    const int kind = append_attention_kernel(Dh, n, APPEND_ATTN_RULE);
+    RUN(launch_append_attention(a, st) ? 1 : 0);
+    ++(kind == APPEND_ATTN_MFMA ? append_mfma_launches : append_wave_launches);
+    return 0;
+}
+
+// n appended tokens per sequence (their ids in ids_in, [B, n]) through every layer on M = B * n rows, the head on row n - 1 of
+// every sequence.  sequence_length is read by every layer's attention and advanced by the caller afterwards.
+int tllm_session::run_append(int n, int max_past, hipStream_t st)
+{
+    const int M = B * n, D = hidden;
+    RUN(launch_embedding(x, ids_in, emb, M, D, vocab, st));
+    for (int li = 0; li < num_layers; ++li)
+        RUN(context_layer(layers[li], M, n, max_past, st));
+    // row n - 1 of every sequence (append_last holds n for every sequence: the padded-layout gather takes row last - 1)
+    RUN(launch_fill_i32(append_last, n, B, st));
+    RUN(launch_gather_last_token(last_hidden, x, append_last, B, n, D, st));
+    RUN(run_head(last_hidden, B, st));
     return 0;
 }
 

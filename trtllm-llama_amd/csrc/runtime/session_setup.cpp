@@ -104,6 +104,9 @@ int tllm_session::alloc_buffers()
     RUN(dalloc(&in_len, (size_t) B * 4));
     RUN(dalloc(&last_tok, (size_t) Bc * 4));
     RUN(dalloc(&in_len_ctx, (size_t) Bc * 4));
+    RUN(dalloc(&append_last, (size_t) B * 4));
+    append_wave_launches = append_mfma_launches = 0;
+    has_context = false;
     cum_log_probs = nullptr;
     parent_ids = cache_ind = nullptr;
     if (beam > 1)

@@ -10,6 +10,7 @@ The per-step bookkeeping of the reference's Python loop (sequence_length = max_i
 [0,1] then [max_in + step, 0], masked_tokens[b, len_b:max_in] = 1, ping-pong contexts, a device->host sync per step:
 generation.py:490-699, :812-821, :963) lives on the device inside tllm_session_generate."""
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 
@@ -100,8 +101,9 @@ class GenerationSession(object):
         self.runtime.setup(batch_size, max_input_length, max_new_tokens, beam_width)
 
     def decode(self, input_ids, input_lengths, sampling_config: SamplingConfig, prompt_embedding_table=None,
-               tasks=None, prompt_vocab_size=None):
+               tasks=None, prompt_vocab_size=None, max_new_tokens: Optional[int] = None):
         """input_ids: int32 [batch, max_input_length] (torch tensor or ndarray), padded with pad_id.
+        max_new_tokens: fewer than setup()'s (None: all of them) - a first turn that leaves cache room for decode_append().
         Returns int32 [batch, num_beams, max_input_length + max_new_tokens] like the reference (generation.py:991-997):
         num_beams == 1: top-k / top-p sampling with temperature, penalties and min_length on the device (arg-max with the
         default fields), reproducible for a fixed sampling_config.random_seed; beam search (hypotheses best first, back-tracked
@@ -116,7 +118,10 @@ class GenerationSession(object):
         assert ids.shape == (self.batch_size, self.max_input_length), 'call setup() with matching sizes first'
         if sampling_config.num_beams == 1:
             self.runtime.set_sampling(self._native_sampling(sampling_config))
-        out = self.runtime.generate(ids.astype(np.int32), lens.astype(np.int32), self.max_new_tokens,
+        new = self.max_new_tokens if max_new_tokens is None else int(max_new_tokens)
+        if not 0 <= new <= self.max_new_tokens:
+            raise ValueError(f'max_new_tokens {new} outside [0, {self.max_new_tokens}] (setup)')
+        out = self.runtime.generate(ids.astype(np.int32), lens.astype(np.int32), new,
                                     end_id=sampling_config.end_id, pad_id=sampling_config.pad_id)
         out = out.reshape(self.batch_size, sampling_config.num_beams, -1)
         if is_torch:
@@ -158,6 +163,64 @@ class GenerationSession(object):
         if is_torch:
             import torch
             out = {k: torch.from_numpy(v).to(input_ids.device) for k, v in out.items()}
+        return out
+
+    @staticmethod
+    def _check_append_args(ids, batch_size: int, max_input_length: int, vocab_size: int, beam_width: int = 1):
+        """What append() / decode_append() refuse before anything reaches the device."""
+        if beam_width != 1:
+            raise ValueError(f'append() needs beam_width 1 (the session is set up with {beam_width})')
+        if ids.ndim != 2 or ids.shape[0] != batch_size:
+            raise ValueError(f'input_ids {ids.shape}: [batch {batch_size}, n] - the same number of tokens for every sequence')
+        if not np.issubdtype(ids.dtype, np.integer):
+            raise TypeError('input_ids must be integers')
+        if not 1 <= ids.shape[1] <= max_input_length:
+            raise ValueError(f'n = {ids.shape[1]} must lie in [1, max_input_length {max_input_length}] '
+                             '(longer input: append it in chunks)')
+        if ids.size and (ids.min() < 0 or ids.max() >= vocab_size):
+            raise ValueError(f'token ids must lie in [0, {vocab_size})')
+
+    def _append_ids(self, input_ids) -> np.ndarray:
+        ids = input_ids.cpu().numpy() if hasattr(input_ids, 'cpu') else np.asarray(input_ids)
+        if self.mapping.tp_size > 1 or self._model_config.paged_kv_cache:
+            raise NotImplementedError('append() is not built for tensor parallelism or the paged KV cache')
+        self._check_append_args(ids, self.batch_size, self.max_input_length, self.vocab_size, getattr(self, 'beam_width', 1))
+        return ids.astype(np.int32)
+
+    def append(self, input_ids):
+        """Append input_ids int32 [batch, n] (torch tensor or ndarray; the same n for every sequence, n <= max_input_length) to
+        the live KV cache in one prefill pass (tllm_session_append) - the next user turn of a chat, the next chunk of a long
+        prompt, n tokens to verify.  Token 0 takes the place of the pending token the last decode() / append() chose (pass that
+        token first to keep it).  Returns the fp32 logits [batch, vocab] of the last appended token; the session has chosen
+        the next pending token and generation can continue (decode_append, or another append).  Needs a decode() / score()
+        before it and room in the cache: setup()'s max_new_tokens bounds everything behind the prompt."""
+        self.runtime.append(self._append_ids(input_ids))
+        logits = self.runtime.logits()
+        if hasattr(input_ids, 'cpu'):
+            import torch
+            return torch.from_numpy(logits).to(input_ids.device)
+        return logits
+
+    def decode_append(self, input_ids, sampling_config: SamplingConfig, max_new_tokens: Optional[int] = None):
+        """append(input_ids), then generation as decode() runs it (tllm_session_append_generate), under sampling_config
+        (num_beams 1).  max_new_tokens None: as many as the cache still has room for.  Returns int32 [batch, 1, max_input_length
+        + max_new_tokens(setup)]: the whole token record - prompt, earlier turns, the appended ids, the new tokens - its unused
+        tail filled with end_id (pad_id when end_id < 0)."""
+        self._check_sampling_config(sampling_config)
+        if sampling_config.num_beams != 1:
+            raise ValueError('decode_append() needs num_beams 1')
+        ids = self._append_ids(input_ids)
+        if max_new_tokens is None:
+            used = int(self.runtime.step_state()['sequence_length'].max())
+            max_new_tokens = self.max_input_length + self.max_new_tokens - used - ids.shape[1]
+        if max_new_tokens < 1:
+            raise ValueError('no room left in the KV cache for a new token: set up with a larger max_new_tokens')
+        self.runtime.set_sampling(self._native_sampling(sampling_config))
+        out = self.runtime.append_generate(ids, max_new_tokens, end_id=sampling_config.end_id, pad_id=sampling_config.pad_id)
+        out = out.reshape(self.batch_size, 1, -1)
+        if hasattr(input_ids, 'cpu'):
+            import torch
+            return torch.from_numpy(out).to(input_ids.device)
         return out
 
     @staticmethod

@@ -94,6 +94,17 @@ def _lib():
     lib.tllm_token_logprobs.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p,
                                         c.c_void_p, c.c_void_p, c.c_void_p]
     lib.tllm_token_logprobs.restype = c.c_int32
+    lib.tllm_session_append.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
+    lib.tllm_session_append.restype = c.c_int32
+    lib.tllm_session_append_generate.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_void_p,
+                                                 c.c_void_p]
+    lib.tllm_session_append_generate.restype = c.c_int32
+    lib.tllm_session_append_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64), c.POINTER(c.c_int64)]
+    lib.tllm_session_append_launches.restype = c.c_int32
+    lib.tllm_attention_append.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p]
+    lib.tllm_attention_append.restype = c.c_int32
+    lib.tllm_attention_append_layout.argtypes = [c.POINTER(AttentionAppendParamsC), c.POINTER(c.c_int32)]
+    lib.tllm_attention_append_layout.restype = c.c_int32
     _bound = True
     return lib
 
@@ -103,6 +114,49 @@ class SamplingConfigC(ctypes.Structure):
     _fields_ = [('top_k', ctypes.c_int32), ('top_p', ctypes.c_float), ('temperature', ctypes.c_float),
                 ('repetition_penalty', ctypes.c_float), ('presence_penalty', ctypes.c_float), ('min_length', ctypes.c_int32),
                 ('random_seed', ctypes.c_uint64)]
+
+
+class AttentionAppendParamsC(ctypes.Structure):
+    """tllm_attention_append_params_t"""
+    _fields_ = [('batch', ctypes.c_int32), ('n', ctypes.c_int32), ('num_heads', ctypes.c_int32), ('num_kv_heads', ctypes.c_int32),
+                ('head_size', ctypes.c_int32), ('rotary_dim', ctypes.c_int32), ('neox', ctypes.c_int32), ('q_scaling', ctypes.c_float),
+                ('kv_cache_type', ctypes.c_int32), ('max_seq_len', ctypes.c_int32), ('max_input_len', ctypes.c_int32),
+                ('max_past', ctypes.c_int32), ('append_kernel', ctypes.c_int32), ('qkv', ctypes.c_void_p),
+                ('kv_cache', ctypes.c_void_p), ('sequence_length', ctypes.c_void_p), ('input_lengths', ctypes.c_void_p),
+                ('masked_tokens', ctypes.c_void_p), ('kv_scale_orig_quant', ctypes.c_void_p),
+                ('kv_scale_quant_orig', ctypes.c_void_p), ('out', ctypes.c_void_p)]
+
+
+APPEND_ATTN_WAVE, APPEND_ATTN_MFMA = 1, 2
+
+
+def attention_append_kernel(n: int, head_size: int, append_kernel: int = 0) -> int:
+    """the attention kernel tllm_attention_append would run (APPEND_ATTN_WAVE / APPEND_ATTN_MFMA); raises where a forced kind
+    cannot run.  Needs no GPU."""
+    p = AttentionAppendParamsC(n=int(n), head_size=int(head_size), append_kernel=int(append_kernel))
+    kind = ctypes.c_int32()
+    _check(_lib().tllm_attention_append_layout(ctypes.byref(p), ctypes.byref(kind)), 'attention_append_layout')
+    return int(kind.value)
+
+
+def attention_append(qkv, kv_cache, out, sequence_length, input_lengths, *, num_heads, num_kv_heads=0, head_size, max_input_len,
+                     max_past, masked_tokens=None, kv_cache_type=0, kv_scale_orig_quant=None, kv_scale_quant_orig=None,
+                     rotary_dim=None, neox=1, q_scaling=1.0, append_kernel=0, stream: int = 0):
+    """tllm_attention_append on torch cuda tensors: qkv fp16 [B, n, (H + 2 Hkv) * Dh] (q and k rewritten in place), kv_cache
+    [B, 2, Hkv, Smax, Dh] fp16 / int8 / uint8, out fp16 [B, n, H * Dh], sequence_length / input_lengths int32 [B], masked_tokens
+    int32 [B, Smax] or None, the two scales f32 [1] (one-byte caches; kv_cache_type capi.INT8 / capi.FP8).  Asynchronous."""
+    B, n = qkv.shape[0], qkv.shape[1]
+    for t in (qkv, kv_cache, out, sequence_length, input_lengths, masked_tokens, kv_scale_orig_quant, kv_scale_quant_orig):
+        assert t is None or (t.is_cuda and t.is_contiguous())
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    p = AttentionAppendParamsC(batch=B, n=n, num_heads=num_heads, num_kv_heads=num_kv_heads, head_size=head_size,
+                               rotary_dim=head_size if rotary_dim is None else rotary_dim, neox=neox, q_scaling=q_scaling,
+                               kv_cache_type=kv_cache_type, max_seq_len=kv_cache.shape[3], max_input_len=max_input_len,
+                               max_past=max_past, append_kernel=append_kernel, qkv=ptr(qkv), kv_cache=ptr(kv_cache),
+                               sequence_length=ptr(sequence_length), input_lengths=ptr(input_lengths),
+                               masked_tokens=ptr(masked_tokens), kv_scale_orig_quant=ptr(kv_scale_orig_quant),
+                               kv_scale_quant_orig=ptr(kv_scale_quant_orig), out=ptr(out))
+    _check(_lib().tllm_attention_append(ctypes.byref(p), stream), 'attention_append')
 
 
 def _sampling_config(top_k=1, top_p=0.0, temperature=1.0, repetition_penalty=1.0, presence_penalty=0.0, min_length=1,
@@ -342,6 +396,32 @@ class NativeSession:
         ids = self._i32(ids)
         assert ids.shape == (self.batch, )
         _check(_lib().tllm_session_force_tokens(self._h, ids.ctypes.data, stream), 'force_tokens')
+
+    def append(self, ids, stream: int = 0):
+        """Append ids [batch, n] to the live cache in one prefill pass (tllm_session_append): the parallel form of n times
+        force_tokens(ids[:, i]); step(1).  Token 0 replaces the pending token (pass it as ids[:, 0] to keep it).  Afterwards
+        logits() holds the last appended token's logits and a new pending token is chosen.  beam_width 1, linear cache, tp 1."""
+        ids = self._i32(ids)
+        assert ids.ndim == 2 and (not self.batch or ids.shape[0] == self.batch), 'ids must be [batch, n]'
+        _check(_lib().tllm_session_append(self._h, ids.ctypes.data, ids.shape[1], stream), 'append')
+
+    def append_generate(self, ids, max_new_tokens: int, end_id: int = -1, pad_id: int = 0, stream: int = 0) -> np.ndarray:
+        """append(ids), then up to max_new_tokens generated tokens (tllm_session_append_generate): the token record
+        [batch, max_seq_len], its unused tail filled as generate() fills it."""
+        ids = self._i32(ids)
+        assert ids.ndim == 2 and (not self.batch or ids.shape[0] == self.batch), 'ids must be [batch, n]'
+        out = np.empty((self.batch, self.max_in + self.max_new), np.int32)
+        _check(_lib().tllm_session_append_generate(self._h, ids.ctypes.data, ids.shape[1], max_new_tokens, end_id, pad_id,
+                                                   out.ctypes.data, stream), 'append_generate')
+        return out
+
+    def append_launches(self):
+        """(wave, mfma): attention launches append() has enqueued since setup, by kernel (one per layer and call)"""
+        w, m = ctypes.c_int64(), ctypes.c_int64()
+        _check(_lib().tllm_session_append_launches(self._h, ctypes.byref(w), ctypes.byref(m)), 'append_launches')
+        return int(w.value), int(m.value)
+
+    attention_append = staticmethod(attention_append)
 
     def attention_tap(self, layer: int, heads_x_dh: int, quantised: bool, stream: int = 0) -> np.ndarray:
         """O-projection input of the last generation step (debug_taps=1): [batch * beam, H/tp * Dh] fp16, int8 for SmoothQuant."""
