@@ -215,6 +215,7 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
     float* hpart = wpart + kWavesF * (kDH + 8);                            // [8][136]: the head's partials (member 0)
     float* misc = hpart + kMembers * (kDH + 8);                            // [0] score of the current token, [1] give-up flag
     uint32_t* qflag = reinterpret_cast<uint32_t*>(misc + 2);               // set by wave 0 once q' is in `rot`
+    uint32_t* pflag = reinterpret_cast<uint32_t*>(misc + 3);               // waves 0 - 2 that have issued the partial's granule stores
 
     const int H = hot_num_heads;
     const int h = blockIdx.x % H, mem = blockIdx.x / H;
@@ -308,12 +309,13 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
     const float4 cs = reinterpret_cast<const float4*>(p.rope_row)[lane & 31]; // RoPE coefficients of elements 2 l', 2 l' + 1
     // O-projection stage: members 1 .. 7 of every head are the row workers - worker j takes rows [j n / W, (j + 1) n / W) of the dense
     // projection, wave `wid` rows r0 + wid, + 8, + 16.  Their per-channel scales and residual elements are launch constants too
+    // (j n < 224 workers x 5376 rows, the most the launcher admits: 32-bit divisions, not the two 64-bit ones that stood here)
     extern __shared__ __attribute__((aligned(16))) char wo_lds[]; // [rows of this worker][K bytes], filled by LDS-DMA
     const bool o_stage = p.o_w != nullptr; // uniform
-    const int o_workers = (kMembers - 1) * H;
-    const int o_j = (mem - 1) * H + h;
-    const int o_r0 = o_stage && mem ? (int) ((int64_t) o_j * p.o_n / o_workers) : 0;
-    const int o_r1 = o_stage && mem ? (int) ((int64_t) (o_j + 1) * p.o_n / o_workers) : 0;
+    const uint32_t o_workers = (uint32_t) ((kMembers - 1) * H);
+    const uint32_t o_j = (uint32_t) ((mem - 1) * H + h);
+    const int o_r0 = o_stage && mem ? (int) (o_j * (uint32_t) p.o_n / o_workers) : 0;
+    const int o_r1 = o_stage && mem ? (int) ((o_j + 1) * (uint32_t) p.o_n / o_workers) : 0;
     // the residual elements (and the weight-only scales) are 16-bit: vector loads.  Unconditional, from a clamped row, and kept as
     // raw bits until the O-projection's epilogue - a conversion here would wait for them behind the q rows
     float o_cs[3];
@@ -355,6 +357,7 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
         {
             misc[1] = 0.f;
             *qflag = 0u;
+            *pflag = 0u;
         }
         __syncthreads();
         ss = red[0] + red[1] + red[2] + red[3];
@@ -448,10 +451,15 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
     int mk[NIT];
     const bool has_mask = p.masked_tokens != nullptr;
     const int32_t* mask_ptr = has_mask ? p.masked_tokens : p.sequence_length;
+    // the last LIVE slot (tl arrived under the prologue: the scalar word of the entry, no wait in front of a weight load).  Slots
+    // [tl, Smax) were fetched for the validity mask to drop them: 140 - 190 rows of K and of V per head at the bench's live length
+    const int t_last = max(min(tl, Smax) - 1, 0);
 #pragma unroll
     for (int i = 0; i < NIT; ++i)
     {
-        const int t = min(t0 + i * NGRP + gid, Smax - 1); // clamped, dropped by the validity mask: no branch around a load
+        // clamped to the live length, dropped by the validity mask: no branch around a load, and every dead slot is the one line
+        // the last live slot's lanes have in flight anyway
+        const int t = min(t0 + i * NGRP + gid, t_last);
         const int64_t off = ((int64_t) t * kDH + li * EPL) * ESZ;
         // read once per step and never handed off inside the launch: `nt`, like the weights, so that the cache rows of 32 layers
         // (268 MB at the bench context) do not push the resident lm_head rows out of the Infinity Cache
@@ -736,7 +744,10 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
         }
         else
         {
-            const uint32_t vw[4] = {vreg[i].x, vreg[i].y, vreg[i].z, vreg[i].w};
+            // a dropped slot's bits never enter the sums (0 x NaN is NaN; with an empty cache the clamped row is slot 0, not yet
+            // written): zero bits, which is what p16 = 0 makes of every finite value
+            const bool dead = s[i] == -INFINITY;
+            const uint32_t vw[4] = {dead ? 0u : vreg[i].x, dead ? 0u : vreg[i].y, dead ? 0u : vreg[i].z, dead ? 0u : vreg[i].w};
 #pragma unroll
             for (int w = 0; w < 4; ++w)
             {
@@ -788,17 +799,22 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
             atomicOr(hot_error, 1u);
         return;
     }
-    // O-projection stage, row workers: waves 3 - 7 (no part in the publication below) request the worker's rows of the dense
-    // projection by LDS-DMA NOW - the CU's load queue is empty, and the 3 - 4 us until the context rows arrive are what the
-    // 16 MB of weights take (row slot s of the worker -> wave 3 + s % 5)
+    // O-projection stage, row workers: waves 3 - 7 (no part in the publication below) request the worker's rows of the
+    // dense projection by LDS-DMA - the CU's load queue is empty, and the 3 - 4 us until the context rows arrive are what the
+    // 16 MB of weights take.  Not before waves 0 - 2 have ISSUED the partial's granule stores (pflag): the stores pass through the
+    // same in-order queue, and behind 60 DMA instructions the partials were in the merger's LDS 2.0 - 2.2 us after the last member's
+    // barrier D (median; 1.5 - 1.7 us now, profiles/front_queue_levelling.txt)
     if (o_stage && mem != 0 && wid >= 3)
     {
+        while (__hip_atomic_load(pflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 3u)
+            __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_sched_barrier(0);
         const uint32_t wo_base = (uint32_t) (uintptr_t) (__attribute__((address_space(3))) void*) wo_lds;
         const char* owb = reinterpret_cast<const char*>(p.o_w);
 #pragma unroll
         for (int i = 0; i < (kORowsMax + 4) / 5; ++i)
         {
-            const int slot = (wid - 3) + 5 * i;
+            const int slot = (wid - 3) + 5 * i; // row slot s of the worker -> wave 3 + s % 5
             if (o_r0 + slot < o_r1) // wave-uniform
             {
 #pragma unroll
@@ -825,6 +841,11 @@ __global__ __launch_bounds__(512) void qkv_attn_fused_kernel(const void* const h
         }
         const float val = tid < kDH ? O : (tid == kDH ? M : L);
         st_granule(gp + mem * kPartStride + tid, tag, __float_as_uint(val));
+        // issued, not completed: the queue is in order from here on (no fence - a release would wait for the write-through)
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::: "memory");
+        if (lane == 0)
+            __hip_atomic_fetch_add(pflag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (mem != 0)
     {
