@@ -181,8 +181,8 @@ int32_t tllm_session_force_tokens(tllm_session_t s, const int32_t* ids, tllm_str
  * Reads sequence_length back, so it synchronises the stream.  Refused, with nothing enqueued: before setup; before any context
  * (every sequence_length must be >= max_input_len); n < 1, n > max_input_len (the activation buffers are sized for that) or
  * sequence_length[b] + n > max_seq_len; beam_width > 1, the paged cache, tensor parallel > 1; a token id outside [0, vocab_size).
- * Packed-input sessions are accepted (the appended rows are dense either way).  Not built: a different n per sequence, scoring
- * of the appended tokens. */
+ * Packed-input sessions are accepted (the appended rows are dense either way).  Not built: a different n per sequence.  The
+ * scoring of the appended tokens is tllm_session_verify's. */
 int32_t tllm_session_append(tllm_session_t s, const int32_t* ids, int32_t n, tllm_stream_t stream);
 /* tllm_session_append, then up to max_new_tokens generated tokens as tllm_session_generate produces them (the first by the
  * append's sampler launch, the rest by generation steps from the graph, the finished flags polled every 32 steps).
@@ -196,6 +196,61 @@ int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32
 /* Attention launches tllm_session_append has enqueued since setup, by kernel (one per layer and call): *wave, *mfma (either may
  * be NULL).  For tests: which kernel served a chunk. */
 int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* mfma);
+
+/* Speculative greedy decoding (the rules are stated in csrc/kernels/kernels.h, SpecAcceptParams and
+ * PromptLookupParams, and restated in numpy in tensorrt_llm/runtime/spec_ref.py).  Opt-in: tllm_session_generate, the step graph
+ * and the append are what they were.
+ *
+ * Verify n ids per sequence in ONE append pass and keep the longest prefix plain greedy decoding would have produced.
+ *   ids        HOST int32 [B, n]: ids[b][0] takes the pending token's place (pass the pending token itself to keep it), ids[b][1..]
+ *              are drafts of the tokens behind it;
+ *   accepted   HOST int32 [B]: m_b, the number of drafts kept; -1 for a frozen sequence (finished: nothing of it changes);
+ *   log_probs  HOST float [B, n] or NULL: log_probs[b][i] = log softmax(logits row i - 1)[ids[b][i]] for 1 <= i < n, 0 at i = 0 - the
+ *              scoring of the appended tokens, whether they were kept or not.
+ * The pass is tllm_session_append's with the head on all B * n rows (fp32, on the device); row i of a sequence is the distribution
+ * behind ids[b][0..i], a_i its arg-max (ties: lowest id).  With p = sequence_length[b]:
+ *   m = 0; while (m + 1 < n && a[m] != end_id && ids[b][m + 1] == a[m]) ++m;
+ *   output slots p .. p + m = ids[b][0..m], slot p + m + 1 = a[m] (the new pending token), sequence_length[b] = p + m + 1,
+ *   finished[b] |= a[m] == end_id; the next step's RoPE row and input row as every sampler launch leaves them.
+ * Afterwards tllm_session_get_logits returns row m_b of every sequence and generation continues by step, append or another verify.
+ * The cache rows of the rejected drafts stay behind the sequence length, where no launch reads them, and are overwritten by the
+ * next tokens.  end_id is the session's (the last tllm_session_generate* call's; -1 after setup).  Synchronises the stream.
+ * Refused, with nothing enqueued: everything tllm_session_append refuses; n > TLLM_VERIFY_MAX_TOKENS;
+ * sequence_length[b] + n + 1 > max_seq_len; a sampling configuration that is not plain arg-max (speculative sampling is not built).
+ * Not built: speculative sampling, a draft model, a different n per sequence, beam / paged / tensor-parallel sessions, a verify
+ * pass in the one-launch form of the generation step. */
+#define TLLM_VERIFY_MAX_TOKENS 32
+int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
+    tllm_stream_t stream);
+/* For tests: the arg-max ids a[b][i] of the n logits rows per sequence of the last verify pass, HOST int32 [B, n] (n as that
+ * pass's; refused before any verify pass).  Synchronises the stream. */
+int32_t tllm_session_verify_top1(tllm_session_t s, int32_t* top1, int32_t n, tllm_stream_t stream);
+
+/* tllm_session_generate with prompt-lookup drafts: the same tokens (greedy), fewer passes where the text repeats itself.
+ * After tllm_session_context every round enqueues (1) the prompt lookup - per sequence the up to num_draft_tokens - 1 tokens that
+ * followed the most recent earlier occurrence of its last max_ngram .. 1 tokens, in its own record (prompt without the padding +
+ * generated tokens) - straight into the pass's input ids, (2) ONE readback of {sequence_length, finished, draft length} per
+ * sequence, the round's only host synchronisation, (3) one pass: a generation step (from the graph) when no sequence has a draft
+ * and none is frozen - a step advances every sequence, so it is taken only while all are live - else a verify pass of
+ * num_draft_tokens ids.  A sequence is frozen once it is finished or holds max_new_tokens tokens; the loop ends when all are.
+ *   cfg    num_draft_tokens in [2, TLLM_VERIFY_MAX_TOKENS] (ids per verify pass, the pending token included), max_ngram in [1, 8];
+ *   stats  (may be NULL) rounds = passes, verify_rounds + step_rounds = rounds, drafted = draft tokens offered, accepted = drafts kept;
+ *   output_ids as tllm_session_generate fills it.
+ * Refused: what tllm_session_verify refuses; max_new_tokens < 1 or max_new_tokens + num_draft_tokens > setup's max_new_tokens (the
+ * last verify pass still writes num_draft_tokens cache rows from the current length).  When a bounded wait of the one-launch
+ * generation step expires the call fails as tllm_session_append_generate does: the session's results are invalid. */
+typedef struct
+{
+    int32_t num_draft_tokens;
+    int32_t max_ngram;
+} tllm_lookup_config_t;
+typedef struct
+{
+    int64_t rounds, verify_rounds, step_rounds, drafted, accepted;
+} tllm_lookup_stats_t;
+int32_t tllm_session_generate_lookup(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg, int32_t* output_ids,
+    tllm_lookup_stats_t* stats, tllm_stream_t stream);
 
 /* Top-k / top-p sampling with temperature, repetition / presence penalty and minimum length, on the device inside the
  * generation step (the reference's dynamic decoder with beam_width 1: PY/runtime/generation.py:299-345, 949-961 ->
@@ -363,6 +418,27 @@ typedef struct
     const void* argmax_part;
 } tllm_greedy_params_t;
 int32_t tllm_greedy_step(const tllm_greedy_params_t* p, tllm_stream_t stream);
+/* Kernel-level entries of speculative greedy decoding (kernels/spec_decode.hip; kernels.h SpecAcceptParams / PromptLookupParams),
+ * for parity tests.  All pointers DEVICE.
+ * tllm_spec_accept: the accept step on the caller's buffers.  g as tllm_greedy_step takes it, except g.logits = the verify rows f32
+ *   [batch * n, vocab_part] (nparts 1), g.advance / g.argmax_part ignored.  ids, top1 int32 [batch, n]; limit int32 [batch] or
+ *   NULL; accepted int32 [batch] or NULL; logits_out f32 [batch, vocab_part] or NULL (receives row accepted[b] of sequence b).
+ * tllm_prompt_lookup: ids int32 [batch, n] = [pending, draft..., pending...], draft_len int32 [batch] from out_ids int32
+ *   [batch, out_stride] / seq_len / input_lengths (NULL = max_input_len) / finished (or NULL) / limit (or NULL), all int32 [batch]. */
+typedef struct
+{
+    tllm_greedy_params_t g;
+    int32_t n;
+    const int32_t* ids;
+    const int32_t* top1;
+    const int32_t* limit;
+    int32_t* accepted;
+    float* logits_out;
+} tllm_spec_accept_params_t;
+int32_t tllm_spec_accept(const tllm_spec_accept_params_t* p, tllm_stream_t stream);
+int32_t tllm_prompt_lookup(const int32_t* out_ids, int32_t batch, int32_t out_stride, const int32_t* seq_len,
+    const int32_t* input_lengths, int32_t max_input_len, const int32_t* finished, const int32_t* limit, int32_t vocab, int32_t n,
+    int32_t max_ngram, int32_t* ids, int32_t* draft_len, tllm_stream_t stream);
 /* Test/bench knob: persistent workgroups per CU (0 = occupancy query). */
 void tllm_gemv_set_blocks_per_cu(int32_t n);
 /* Test/bench knob: number of rows (sequences) from which the SmoothQuant decode GEMM runs on the matrix pipe

@@ -625,6 +625,66 @@ int launch_token_logprob_partial(const TokenLogprobParams& p, hipStream_t stream
 int launch_token_logprob_merge(const float* partials, int32_t nparts, int32_t rows, int32_t vocab, const int32_t* targets,
     float* log_probs, float* lse, int32_t* top1_ids, hipStream_t stream);
 
+// ---------------------------------------------------------------------------------------------
+// Speculative greedy decoding (kernels/spec_decode.hip; the numpy restatement is
+// tensorrt_llm/runtime/spec_ref.py).  A verify pass runs n ids per sequence - t[0] the pending token, t[1..] drafts - onto the
+// live cache in one append pass and scores all n rows; a[i] is the arg-max id of row i, the distribution behind t[0..i].
+//
+// The accept step takes the sampler's place behind that pass.  One workgroup per sequence b; p = seq_len[b],
+// lim = limit ? limit[b] : INT32_MAX (the largest sequence length the call may leave):
+//   frozen (finished[b] != 0 or p >= lim): accepted[b] = -1 and no state of the sequence is written (its input row in x_out, which
+//     the pass has used as an activation buffer, is put back from cur_ids[b]);
+//   otherwise  m = 0; while (m + 1 < n && p + m + 1 < lim && a[m] != end_id && t[m + 1] == a[m]) ++m;  bonus = a[m];
+//     out_ids[b][p + i] = t[i] for i <= m, out_ids[b][p + m + 1] = bonus (slots above are not written), seq_len[b] = p + m + 1,
+//     cur_ids[b] = bonus, finished[b] |= bonus == end_id, accepted[b] = m; the RoPE row (and rope_pos_out) of position
+//     p + m + 1 - (max_input_len - input_lengths[b]), clamped into the table; the embedding row of bonus into x_out; row m of the
+//     sequence's logits rows into row b of logits_out;
+//   once per launch: step_epoch += 1, as every sampler launch does.
+// The tokens are those plain greedy decoding defines whatever the drafts were: a draft is kept only where it is the arg-max.
+// Fields of g as launch_greedy_step reads them, except: g.logits = the verify rows f32 [batch * n, vocab_part] (one part, read
+// only for the row copy), g.advance and g.argmax_part are ignored.  Guards: cache slot < out_stride, id < vocab (else a zero row).
+// ---------------------------------------------------------------------------------------------
+constexpr int kVerifyMaxTokens = 32; // ids per sequence of one verify pass (TLLM_VERIFY_MAX_TOKENS)
+constexpr int kLookupMaxNgram = 8;   // longest suffix the prompt lookup matches
+struct SpecAcceptParams
+{
+    GreedyParams g;
+    int32_t n = 0;                 // ids per sequence, 1 .. kVerifyMaxTokens
+    const int32_t* ids = nullptr;  // int32 [batch, n]: t
+    const int32_t* top1 = nullptr; // int32 [batch, n]: a
+    const int32_t* limit = nullptr; // int32 [batch] or null
+    int32_t* accepted = nullptr;   // int32 [batch] or null
+    float* logits_out = nullptr;   // f32 [batch, vocab_part] or null
+};
+int launch_spec_accept(const SpecAcceptParams& p, hipStream_t stream);
+
+// Prompt lookup: drafts from the sequence's own token record.  One workgroup per sequence b.  The logical sequence is
+// out_ids[b][0 .. input_lengths[b]) followed by out_ids[b][max_input_len .. seq_len[b]] - the padding slots between are not part
+// of it - and its last element is the pending token.  With k = n - 1 draft slots: for g = max_ngram down to 1 the last g tokens
+// are the suffix; among the starts s with s + g < len whose g tokens equal it the most recent wins, at the first g that has one.
+// The draft is the up to k tokens behind the match that exist inside the logical sequence; draft_len[b] is their number, 0
+// without a match and for a frozen sequence (finished, or seq_len >= limit).  ids[b] = [pending, draft..., pending...]: any valid
+// id serves behind the draft, the accept rule rejects or rightly accepts whatever it is given.  state_out (optional, int32
+// [batch, 4]) = {seq_len, finished, draft_len, frozen}: what the host loop reads back in one copy.
+struct PromptLookupParams
+{
+    int32_t batch = 0, n = 0, max_ngram = 0; // n 1 .. kVerifyMaxTokens, max_ngram 1 .. kLookupMaxNgram
+    const int32_t* out_ids = nullptr;        // int32 [batch, out_stride]
+    int32_t out_stride = 0;
+    const int32_t* seq_len = nullptr;        // int32 [batch]
+    const int32_t* input_lengths = nullptr;  // int32 [batch] or null (= max_input_len)
+    int32_t max_input_len = 0;
+    const int32_t* finished = nullptr;       // int32 [batch] or null
+    const int32_t* limit = nullptr;          // int32 [batch] or null
+    int32_t vocab = 0;                       // an id outside [0, vocab) in the record is passed on as 0
+    int32_t* ids = nullptr;                  // int32 [batch, n]
+    int32_t* draft_len = nullptr;            // int32 [batch] or null
+    int32_t* state_out = nullptr;            // int32 [batch, 4] or null
+};
+int launch_prompt_lookup(const PromptLookupParams& p, hipStream_t stream);
+// targets[b][i] = ids[b][i + 1], -1 at i = n - 1: the next-token targets of a verify pass's n rows (token_logprob)
+int launch_spec_targets(int32_t* targets, const int32_t* ids, int32_t batch, int32_t n, hipStream_t stream);
+
 // teacher forcing for parity tests: overwrite the sampler's last choice (output slot seq_len[b], step input id, next input row)
 int launch_force_token(const int32_t* ids_dev, int32_t* cur_ids, int32_t* out_ids, int32_t out_stride, const int32_t* seq_len,
     const void* emb, void* x, int32_t batch, int32_t hidden, int32_t vocab, hipStream_t stream);

@@ -363,15 +363,15 @@ int32_t tllm_gemv_head(const tllm_gemv_params_t* q, int32_t resident_rows, void*
     return launch_gemv(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
-int32_t tllm_greedy_step(const tllm_greedy_params_t* q, tllm_stream_t stream)
+static bool greedy_args_ok(const tllm_greedy_params_t* q)
 {
-    if (!q || !q->logits || !q->cur_ids || !q->out_ids || !q->seq_len || q->batch < 1 || q->nparts < 1 || q->vocab_part < 1
-        || q->vocab < 1 || (int64_t) q->nparts * q->vocab_part < q->vocab
-        || (q->rope_row_out && (q->rope_half < 1 || q->rope_half > 960 || q->rope_table_len < 1))) // (the launcher checks the rest)
-    {
-        set_error("tllm_greedy_step: bad arguments");
-        return 1;
-    }
+    return q && q->logits && q->cur_ids && q->out_ids && q->seq_len && q->batch >= 1 && q->nparts >= 1 && q->vocab_part >= 1
+        && q->vocab >= 1 && (int64_t) q->nparts * q->vocab_part >= q->vocab
+        && !(q->rope_row_out && (q->rope_half < 1 || q->rope_half > 960 || q->rope_table_len < 1)); // (the launchers check the rest)
+}
+
+static GreedyParams greedy_params(const tllm_greedy_params_t* q)
+{
     GreedyParams g;
     g.logits = q->logits;
     g.batch = q->batch;
@@ -397,7 +397,63 @@ int32_t tllm_greedy_step(const tllm_greedy_params_t* q, tllm_stream_t stream)
     g.hidden = q->hidden;
     g.step_epoch = q->step_epoch;
     g.argmax_part = q->argmax_part;
-    return launch_greedy_step(g, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+    return g;
+}
+
+int32_t tllm_greedy_step(const tllm_greedy_params_t* q, tllm_stream_t stream)
+{
+    if (!greedy_args_ok(q))
+    {
+        set_error("tllm_greedy_step: bad arguments");
+        return 1;
+    }
+    return launch_greedy_step(greedy_params(q), reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_spec_accept(const tllm_spec_accept_params_t* q, tllm_stream_t stream)
+{
+    static_assert(TLLM_VERIFY_MAX_TOKENS == kVerifyMaxTokens, "the header's constant is the kernels'");
+    if (!q || !greedy_args_ok(&q->g) || q->g.nparts != 1 || q->g.out_stride < 1)
+    {
+        set_error("tllm_spec_accept: bad arguments (the greedy step's, with one vocabulary part)");
+        return 1;
+    }
+    SpecAcceptParams p;
+    p.g = greedy_params(&q->g);
+    p.g.argmax_part = nullptr;
+    p.n = q->n;
+    p.ids = q->ids;
+    p.top1 = q->top1;
+    p.limit = q->limit;
+    p.accepted = q->accepted;
+    p.logits_out = q->logits_out;
+    return launch_spec_accept(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_prompt_lookup(const int32_t* out_ids, int32_t batch, int32_t out_stride, const int32_t* seq_len,
+    const int32_t* input_lengths, int32_t max_input_len, const int32_t* finished, const int32_t* limit, int32_t vocab, int32_t n,
+    int32_t max_ngram, int32_t* ids, int32_t* draft_len, tllm_stream_t stream)
+{
+    if (batch < 1)
+    {
+        set_error("tllm_prompt_lookup: bad arguments");
+        return 1;
+    }
+    PromptLookupParams p;
+    p.batch = batch;
+    p.n = n;
+    p.max_ngram = max_ngram;
+    p.out_ids = out_ids;
+    p.out_stride = out_stride;
+    p.seq_len = seq_len;
+    p.input_lengths = input_lengths;
+    p.max_input_len = max_input_len;
+    p.finished = finished;
+    p.limit = limit;
+    p.vocab = vocab;
+    p.ids = ids;
+    p.draft_len = draft_len;
+    return launch_prompt_lookup(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
 int32_t tllm_gemm(const tllm_gemm_params_t* q, tllm_stream_t stream)

@@ -336,10 +336,8 @@ static void fill_output_tail(tllm_session_t s, int32_t* output_ids, const std::v
 }
 
 // ------------------------------------------------------------------------------------------ append
-// The checks of tllm_session_append (nothing is enqueued before every one has passed), then: the ids to the device and into the
-// token record, the append pass, the advance launch, the sampler.  past[b] = sequence_length[b] before the call.
-static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, int32_t reserve_new,
-    std::vector<int32_t>& past, tllm_stream_t stream)
+// What a session must be for an append pass (tllm_session_append, _verify, _generate_lookup)
+static int32_t append_session_ok(tllm_session_t s, const char* who)
 {
     if (!s || !s->B)
     {
@@ -352,6 +350,15 @@ static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* 
             s->paged_kv ? 1 : 0, s->tp);
         return 1;
     }
+    return 0;
+}
+
+// The checks of tllm_session_append; they enqueue nothing but the read of sequence_length.  past[b] = sequence_length[b] before
+// the call, *max_past_out their maximum.
+static int32_t append_checks(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, int32_t reserve_new,
+    std::vector<int32_t>& past, int* max_past_out, tllm_stream_t stream)
+{
+    RUN(append_session_ok(s, who));
     if (!ids)
     {
         set_error("%s: null argument", who);
@@ -395,6 +402,19 @@ static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* 
         }
         max_past = std::max(max_past, past[b]);
     }
+    *max_past_out = max_past;
+    return 0;
+}
+
+// append_checks (nothing is enqueued before every one has passed), then: the ids to the device and into the token record, the
+// append pass, the advance launch, the sampler.
+static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, int32_t reserve_new,
+    std::vector<int32_t>& past, tllm_stream_t stream)
+{
+    int max_past = 0;
+    RUN(append_checks(s, who, ids, n, reserve_new, past, &max_past, stream));
+    hipStream_t st = s->pick(stream);
+    const int B = s->B, Smax = s->Smax;
     HIP_OK(hipMemcpyAsync(s->ids_in, ids, (size_t) B * n * 4, hipMemcpyHostToDevice, st));
     for (int b = 0; b < B; ++b)
         HIP_OK(hipMemcpyAsync(s->out_ids + (size_t) b * Smax + past[b], ids + (size_t) b * n, (size_t) n * 4, hipMemcpyHostToDevice, st));
@@ -457,6 +477,183 @@ int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* m
         *wave = s->append_wave_launches;
     if (mfma)
         *mfma = s->append_mfma_launches;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ speculative greedy decoding
+static int32_t verify_session_ok(tllm_session_t s, const char* who)
+{
+    RUN(append_session_ok(s, who));
+    if (s->sampling_on && !sampling_is_greedy(s->sampling))
+    {
+        set_error("%s: the session samples (top-k / top-p / penalties): the accept rule is greedy - speculative sampling is not built", who);
+        return 1;
+    }
+    return 0;
+}
+
+int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
+    tllm_stream_t stream)
+{
+    const char* who = "tllm_session_verify";
+    RUN(verify_session_ok(s, who) ? 1 : 0);
+    if (!accepted)
+    {
+        set_error("%s: null argument", who);
+        return 1;
+    }
+    if (n > TLLM_VERIFY_MAX_TOKENS)
+    {
+        set_error("%s: n %d exceeds TLLM_VERIFY_MAX_TOKENS %d", who, n, TLLM_VERIFY_MAX_TOKENS);
+        return 1;
+    }
+    std::vector<int32_t> past;
+    int max_past = 0;
+    // (one slot behind the n rows: the accept step writes the new pending token to slot p + m + 1 <= p + n)
+    RUN(append_checks(s, who, ids, n, 1, past, &max_past, stream) ? 1 : 0);
+    hipStream_t st = s->pick(stream);
+    const int B = s->B;
+    HIP_OK(hipMemcpyAsync(s->ids_in, ids, (size_t) B * n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st)); // the caller's buffer may go out of scope
+    RUN(s->run_verify(n, max_past, nullptr, st) ? 1 : 0);
+    HIP_OK(hipMemcpyAsync(accepted, s->verify.accepted, (size_t) B * 4, hipMemcpyDeviceToHost, st));
+    if (log_probs) // row (b, i - 1) scored ids[b][i]; its last row had no target and scored 0
+    {
+        for (int b = 0; b < B; ++b)
+            log_probs[(size_t) b * n] = 0.f;
+        if (n > 1)
+            HIP_OK(hipMemcpy2DAsync(log_probs + 1, (size_t) n * 4, s->verify.log_probs, (size_t) n * 4, (size_t) (n - 1) * 4, B,
+                hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    return s->check_comm() ? 1 : 0;
+}
+
+int32_t tllm_session_verify_top1(tllm_session_t s, int32_t* top1, int32_t n, tllm_stream_t stream)
+{
+    if (!s || !s->B || !top1 || !s->verify.top1 || n != s->verify_n)
+    {
+        set_error("tllm_session_verify_top1: bad arguments, or no verify pass of n = %d ids has run since setup", n);
+        return 1;
+    }
+    hipStream_t st = s->pick(stream);
+    HIP_OK(hipMemcpyAsync(top1, s->verify.top1, (size_t) s->B * n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int32_t tllm_session_generate_lookup(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg, int32_t* output_ids,
+    tllm_lookup_stats_t* stats, tllm_stream_t stream)
+{
+    const char* who = "tllm_session_generate_lookup";
+    RUN(verify_session_ok(s, who) ? 1 : 0);
+    if (!input_ids || !input_lengths || !output_ids || !cfg)
+    {
+        set_error("%s: null argument", who);
+        return 1;
+    }
+    const int n = cfg->num_draft_tokens;
+    if (n < 2 || n > TLLM_VERIFY_MAX_TOKENS || cfg->max_ngram < 1 || cfg->max_ngram > kLookupMaxNgram)
+    {
+        set_error("%s: num_draft_tokens %d outside [2, %d] or max_ngram %d outside [1, %d]", who, n, TLLM_VERIFY_MAX_TOKENS,
+            cfg->max_ngram, kLookupMaxNgram);
+        return 1;
+    }
+    if (n > s->max_in)
+    {
+        set_error("%s: num_draft_tokens %d exceeds max_input_len %d (the activation buffers are sized for the prompt)", who, n, s->max_in);
+        return 1;
+    }
+    if (max_new_tokens < 1 || (int64_t) max_new_tokens + n > s->max_new)
+    {
+        set_error("%s: max_new_tokens %d + num_draft_tokens %d exceed setup's max_new_tokens %d (the last verify pass still writes "
+                  "num_draft_tokens cache rows from the current length)", who, max_new_tokens, n, s->max_new);
+        return 1;
+    }
+    hipStream_t st = s->pick(stream);
+    const int B = s->B, S = s->max_in;
+    if (end_id != s->end_id)
+    {
+        s->end_id = end_id;
+        s->drop_graph(); // end_id is baked into the captured sampler node
+    }
+    RUN(tllm_session_context(s, input_ids, input_lengths, stream) ? 1 : 0);
+    const int lim = S + max_new_tokens - 1; // sequence length with max_new_tokens tokens in the record
+    tllm_lookup_stats_t acc = {0, 0, 0, 0, 0};
+    std::vector<int32_t> state((size_t) B * 4), before(B, 0);
+    bool verify_pending = false, stepped = false;
+    RUN(s->verify_buffers() ? 1 : 0); // the lookup's state record and the limits are among them
+    RUN(launch_fill_i32(s->verify.limit, lim, B, st) ? 1 : 0);
+    for (;;)
+    {
+        PromptLookupParams lp;
+        lp.batch = B;
+        lp.n = n;
+        lp.max_ngram = cfg->max_ngram;
+        lp.out_ids = s->out_ids;
+        lp.out_stride = s->Smax;
+        lp.seq_len = s->seq_len;
+        lp.input_lengths = s->in_len;
+        lp.max_input_len = S;
+        lp.finished = s->finished;
+        lp.limit = s->verify.limit;
+        lp.vocab = s->vocab;
+        lp.ids = s->ids_in;
+        lp.state_out = s->verify.state;
+        RUN(launch_prompt_lookup(lp, st) ? 1 : 0);
+        HIP_OK(hipMemcpyAsync(state.data(), s->verify.state, state.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st)); // the round's only host synchronisation
+        const int crc = s->check_comm();
+        if (crc == kFusedTimedOut)
+            set_error("%s: a bounded in-launch wait of the generation step expired: the session's tokens and cache behind it are invalid "
+                      "- run the request again from tllm_session_context", who);
+        if (crc)
+            return 1;
+        bool all_frozen = true, any_frozen = false, any_draft = false;
+        int max_past = 0;
+        for (int b = 0; b < B; ++b)
+        {
+            const int32_t* r = &state[(size_t) b * 4];
+            if (verify_pending && before[b] >= 0) // drafts the last verify pass kept: what the length moved by, less the bonus token
+                acc.accepted += r[0] - before[b] - 1;
+            const bool frozen = r[3] != 0;
+            all_frozen = all_frozen && frozen;
+            any_frozen = any_frozen || frozen;
+            any_draft = any_draft || r[2] > 0;
+            before[b] = frozen ? -1 : r[0];
+            max_past = std::max(max_past, r[0]);
+        }
+        if (all_frozen)
+            break;
+        if (!any_draft && !any_frozen)
+        {
+            // a plain step: the first of a call eagerly (it also warms lazily-initialised state), the others from the graph
+            RUN(tllm_session_step(s, 1, stepped ? 1 : 0, stream) ? 1 : 0);
+            stepped = true;
+            verify_pending = false;
+            acc.step_rounds += 1;
+        }
+        else
+        {
+            if (max_past + n + 1 > s->Smax) // (cannot happen behind the room check above: the lengths come from the device)
+            {
+                set_error("%s: sequence length %d + %d ids do not fit the cache capacity %d", who, max_past, n, s->Smax);
+                return 1;
+            }
+            for (int b = 0; b < B; ++b)
+                acc.drafted += state[(size_t) b * 4 + 2];
+            RUN(s->run_verify(n, max_past, s->verify.limit, st) ? 1 : 0);
+            verify_pending = true;
+            acc.verify_rounds += 1;
+        }
+        acc.rounds += 1;
+    }
+    RUN(tllm_session_get_output_ids(s, output_ids, stream) ? 1 : 0);
+    // every sequence is finished (the row is end_id behind its first end_id) or holds max_new_tokens tokens
+    fill_output_tail(s, output_ids, std::vector<int>(B, S), max_new_tokens, end_id, pad_id);
+    if (stats)
+        *stats = acc;
     return 0;
 }
 

@@ -249,6 +249,19 @@ struct tllm_session
         float* log_probs = nullptr;  // [max_rows]
         int32_t* top1 = nullptr;     // [max_rows]
     } score;
+    // tllm_session_verify / tllm_session_generate_lookup (run_verify): the buffers exist from the first verify pass after a setup on
+    struct VerifyBuffers
+    {
+        float* logits = nullptr;    // f32 [B * kVerifyMaxTokens, Vr]: the logits rows of one pass
+        int32_t* targets = nullptr; // [B * kVerifyMaxTokens] ids[b][i + 1], -1 on a sequence's last row
+        float* rec = nullptr;       // [B * kVerifyMaxTokens, 8] token_logprob records
+        float* log_probs = nullptr; // [B * kVerifyMaxTokens]
+        int32_t* top1 = nullptr;    // [B * kVerifyMaxTokens]
+        int32_t* accepted = nullptr; // [B]
+        int32_t* limit = nullptr;    // [B] largest sequence length the lookup loop may leave
+        int32_t* state = nullptr;    // [B, 4] the prompt lookup's {seq_len, finished, draft_len, frozen}
+    } verify;
+    int verify_n = 0; // ids per sequence of the last verify pass (0: none since setup)
     std::vector<int32_t> score_pos;  // host: output slot b * max_in + t + 1 of every scored row of the current call
     std::vector<float> score_lp_host;
     std::vector<int32_t> score_top_host;
@@ -325,6 +338,15 @@ struct tllm_session
     // tllm_session_append: the prefill schedule on B * n appended rows (ids in ids_in) onto the live cache, head on row n - 1
     int append_attention(const Layer& L, int n, int max_past, hipStream_t st);
     int run_append(int n, int max_past, hipStream_t st);
+    int append_layers(int n, int max_past, hipStream_t st); // embedding + every layer on the B * n rows (ids in ids_in)
+    // tllm_session_verify: append_layers, then the head on ALL B * n rows (fp32, verify.logits), their scoring (verify.top1 /
+    // .log_probs against the next id of the row) and the accept step in the sampler's place; limit: device int32 [B] or null
+    int run_verify(int n, int max_past, const int32_t* limit, hipStream_t st);
+    int verify_buffers(); // allocates `verify` on first use after a setup
+    // ln_f of R hidden rows into tmp (fp16), and lm_head as a prefill GEMM on `rows` of them with fp32 output [rows, Vr]: the
+    // head of scoring and of a verify pass (run_head's fused GEMV leaves at most B rows, in the session's logits)
+    int head_norm(const void* h, int R, hipStream_t st);
+    int head_gemm_f32(const void* a, int rows, float* out, hipStream_t st);
     // score: enqueue ln_f -> lm_head in row chunks -> partial records (-> all-gather) -> merge on the rows of x that have a next
     // token (between run_context and the sampler, which reuses x); collect: after the stream is synchronised, scatter to the host
     int score_enqueue(const int32_t* input_ids, const int32_t* input_lengths, hipStream_t st);
@@ -339,6 +361,7 @@ struct tllm_session
         const float* row_scales = nullptr, void* tap = nullptr);
     int allreduce(void* buf, int64_t n, hipStream_t st);
     int run_head(const void* h, int rows, hipStream_t st, bool normalised = false);
+    tllm::kernels::GreedyParams greedy_params();
     int run_sampler(int advance, hipStream_t st);
     struct DecodeStep; // what is fixed for one generation step (session_decode.cpp)
     DecodeStep plan_decode_step(hipStream_t st);

@@ -283,19 +283,115 @@ int tllm_session::append_attention(const Layer& L, int n, int max_past, hipStrea
     return 0;
 }
 
-// n appended tokens per sequence (their ids in ids_in, [B, n]) through every layer on M = B * n rows, the head on row n - 1 of
-// every sequence.  sequence_length is read by every layer's attention and advanced by the caller afterwards.
-int tllm_session::run_append(int n, int max_past, hipStream_t st)
+// n appended tokens per sequence (their ids in ids_in, [B, n]) through every layer on M = B * n rows: the body of an append pass
+// and of a verify pass.  sequence_length is read by every layer's attention and not written.
+int tllm_session::append_layers(int n, int max_past, hipStream_t st)
 {
-    const int M = B * n, D = hidden;
-    RUN(launch_embedding(x, ids_in, emb, M, D, vocab, st));
+    const int M = B * n;
+    RUN(launch_embedding(x, ids_in, emb, M, hidden, vocab, st));
     for (int li = 0; li < num_layers; ++li)
         RUN(context_layer(layers[li], M, n, max_past, st));
+    return 0;
+}
+
+// ... and the head on row n - 1 of every sequence.  The caller advances sequence_length afterwards.
+int tllm_session::run_append(int n, int max_past, hipStream_t st)
+{
+    RUN(append_layers(n, max_past, st));
     // row n - 1 of every sequence (append_last holds n for every sequence: the padded-layout gather takes row last - 1)
     RUN(launch_fill_i32(append_last, n, B, st));
-    RUN(launch_gather_last_token(last_hidden, x, append_last, B, n, D, st));
+    RUN(launch_gather_last_token(last_hidden, x, append_last, B, n, hidden, st));
     RUN(run_head(last_hidden, B, st));
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------ verify
+// The buffers of a verify pass, sized for kVerifyMaxTokens ids per sequence; allocated by the first one after a setup.
+int tllm_session::verify_buffers()
+{
+    if (verify.logits)
+        return 0;
+    VerifyBuffers vb;
+    const size_t rows = (size_t) B * kVerifyMaxTokens;
+    RUN(dalloc(&vb.logits, rows * Vr * 4));
+    RUN(dalloc(&vb.targets, rows * 4));
+    RUN(dalloc(&vb.rec, rows * 8 * 4));
+    RUN(dalloc(&vb.log_probs, rows * 4));
+    RUN(dalloc(&vb.top1, rows * 4));
+    RUN(dalloc(&vb.accepted, (size_t) B * 4));
+    RUN(dalloc(&vb.limit, (size_t) B * 4));
+    RUN(dalloc(&vb.state, (size_t) B * 4 * 4));
+    verify = vb;
+    return 0;
+}
+
+// run_append's layers, then every one of the B * n final hidden rows through the head: row (b, i) is the distribution behind
+// ids[b][0..i].  The rows are scored against the next id of their sequence (top1 = the arg-max the accept rule compares the
+// drafts with, log_probs for the caller) and the accept step commits the longest right prefix in the sampler's place
+// (kernels.h SpecAcceptParams).  sequence_length is read by every layer's attention and written by the accept step alone.
+int tllm_session::run_verify(int n, int max_past, const int32_t* limit, hipStream_t st)
+{
+    const int R = B * n;
+    RUN(verify_buffers());
+    verify_n = n;
+    RUN(append_layers(n, max_past, st));
+    RUN(head_norm(x, R, st));
+    RUN(head_gemm_f32(tmp, R, verify.logits, st));
+    RUN(launch_spec_targets(verify.targets, ids_in, B, n, st) ? 1 : 0);
+    TokenLogprobParams p;
+    p.logits = verify.logits;
+    p.ld = Vr;
+    p.rows = R;
+    p.vocab_part = Vr;
+    p.vocab = vocab;
+    p.targets = verify.targets;
+    p.partials = verify.rec;
+    RUN(launch_token_logprob_partial(p, st) ? 1 : 0);
+    RUN(launch_token_logprob_merge(verify.rec, 1, R, vocab, verify.targets, verify.log_probs, nullptr, verify.top1, st) ? 1 : 0);
+    head_partials_live = false; // the session's logits are a copied row from here on, no head launch's partials belong to them
+    logit_rows = B;
+    SpecAcceptParams a;
+    a.g = greedy_params();
+    a.g.logits = verify.logits;
+    a.n = n;
+    a.ids = ids_in;
+    a.top1 = verify.top1;
+    a.limit = limit;
+    a.accepted = verify.accepted;
+    a.logits_out = logits_local;
+    return launch_spec_accept(a, st) ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------ the head on many rows
+int tllm_session::head_norm(const void* h, int R, hipStream_t st)
+{
+    RmsnormParams r;
+    r.M = R;
+    r.N = hidden;
+    r.x = h;
+    r.gamma = lnf;
+    r.eps = eps;
+    r.y = tmp; // [Bc * S, D] fp16, free between the last layer and the next call
+    return launch_rmsnorm(r, st);
+}
+
+int tllm_session::head_gemm_f32(const void* a, int rows, float* out, hipStream_t st)
+{
+    GemmParams g;
+    g.wtype = head.wtype;
+    g.out_dtype = DT_FLOAT;
+    g.M = rows;
+    g.N = head.N;
+    g.K = head.K;
+    g.a = a;
+    g.lda = hidden;
+    g.w = head.w;
+    g.ldw = head.ldw;
+    g.scale_col = head.scale_col;
+    g.per_channel = head.per_channel;
+    g.c = out;
+    g.ldc = Vr;
+    return launch_gemm(g, st) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------ scoring
@@ -348,33 +444,11 @@ int tllm_session::score_enqueue(const int32_t* input_ids, const int32_t* input_l
     HIP_OK(hipMemcpyAsync(score.targets, tgt.data(), (size_t) R * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipStreamSynchronize(st)); // src / tgt go out of scope
     RUN(launch_gather_rows(score.hidden, x, score.src_rows, R, D, st));
-    RmsnormParams r;
-    r.M = R;
-    r.N = D;
-    r.x = score.hidden;
-    r.gamma = lnf;
-    r.eps = eps;
-    r.y = tmp; // [Bc * S, D] fp16, free between the last layer and the next call
-    RUN(launch_rmsnorm(r, st));
+    RUN(head_norm(score.hidden, R, st));
     for (int r0 = 0; r0 < R; r0 += score.chunk)
     {
         const int rows = std::min(score.chunk, R - r0);
-        GemmParams g;
-        g.wtype = head.wtype;
-        g.out_dtype = DT_FLOAT;
-        g.M = rows;
-        g.N = head.N;
-        g.K = head.K;
-        g.a = static_cast<const char*>(tmp) + (size_t) r0 * D * 2;
-        g.lda = D;
-        g.w = head.w;
-        g.ldw = head.ldw;
-        g.scale_col = head.scale_col;
-        g.per_channel = head.per_channel;
-        g.c = score.logits;
-        g.ldc = Vr;
-        if (launch_gemm(g, st))
-            return 1;
+        RUN(head_gemm_f32(static_cast<const char*>(tmp) + (size_t) r0 * D * 2, rows, score.logits, st));
         TokenLogprobParams p;
         p.logits = score.logits;
         p.ld = Vr;

@@ -166,6 +166,38 @@ int tllm_session::run_head(const void* h, int rows, hipStream_t st, bool normali
     return 0;
 }
 
+// the session's logits, step words and next-step buffers as a sampler launch takes them (greedy, top-k / top-p or accept step)
+GreedyParams tllm_session::greedy_params()
+{
+    GreedyParams gp;
+    gp.logits = (tp > 1 || force_comm) ? logits : logits_local;
+    gp.batch = B;
+    gp.vocab_part = Vr;
+    gp.nparts = tp;
+    gp.vocab = vocab;
+    gp.cur_ids = cur_ids;
+    gp.out_ids = out_ids;
+    gp.out_stride = Smax;
+    gp.seq_len = seq_len;
+    gp.finished = finished;
+    gp.end_id = end_id;
+    gp.rope_row_out = rope_row;
+    gp.rope_pos_out = rope_pos;
+    gp.step_epoch = step_epoch;
+    gp.rope_table = rope;
+    gp.rope_half = Dh / 2;
+    gp.rope_table_len = rope_len;
+    gp.input_lengths = in_len;
+    gp.max_input_len = max_in;
+    if (hidden % 8 == 0)
+    {
+        gp.emb_table = emb; // the sampler leaves the next step's input row in x (run_decode_step skips its embedding launch)
+        gp.x_out = x;
+        gp.hidden = hidden;
+    }
+    return gp;
+}
+
 int tllm_session::run_sampler(int advance, hipStream_t st)
 {
     // the partials belong to the logits of the head launch just before this sampler, and to no later one
@@ -200,33 +232,8 @@ int tllm_session::run_sampler(int advance, hipStream_t st)
         bp.max_input_len = max_in;
         return timed(PC_OTHER, st, [&] { return launch_beam_step(bp, st) ? 1 : 0; });
     }
-    GreedyParams gp;
-    gp.logits = (tp > 1 || force_comm) ? logits : logits_local;
-    gp.batch = B;
-    gp.vocab_part = Vr;
-    gp.nparts = tp;
-    gp.vocab = vocab;
-    gp.cur_ids = cur_ids;
-    gp.out_ids = out_ids;
-    gp.out_stride = Smax;
-    gp.seq_len = seq_len;
-    gp.finished = finished;
-    gp.end_id = end_id;
+    GreedyParams gp = greedy_params();
     gp.advance = advance;
-    gp.rope_row_out = rope_row;
-    gp.rope_pos_out = rope_pos;
-    gp.step_epoch = step_epoch;
-    gp.rope_table = rope;
-    gp.rope_half = Dh / 2;
-    gp.rope_table_len = rope_len;
-    gp.input_lengths = in_len;
-    gp.max_input_len = max_in;
-    if (hidden % 8 == 0)
-    {
-        gp.emb_table = emb; // the sampler leaves the next step's input row in x (run_decode_step skips its embedding launch)
-        gp.x_out = x;
-        gp.hidden = hidden;
-    }
     if (sampling_on && !sampling_is_greedy(sampling))
     {
         // same logits (gathered shards included), same bookkeeping; every tensor-parallel rank draws the same token

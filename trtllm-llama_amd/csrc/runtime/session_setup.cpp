@@ -24,6 +24,8 @@ void tllm_session::free_runtime()
         (void) hipFree(p);
     allocs.clear();
     score = ScoreBuffers();
+    verify = VerifyBuffers();
+    verify_n = 0;
 }
 
 // ------------------------------------------------------------------------------------------ buffers

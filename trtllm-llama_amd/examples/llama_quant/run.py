@@ -42,6 +42,10 @@ def parse_arguments(args=None):
     p.add_argument('--repetition_penalty', type=float, default=1.0)
     p.add_argument('--random_seed', type=int, default=None)
     p.add_argument('--num_runs', type=int, default=55)
+    # greedy decoding with prompt-lookup speculation (GenerationSession.decode_lookup): the same tokens, N ids verified per pass
+    p.add_argument('--prompt_lookup_tokens', type=int, default=0,
+                   help='N in [2, 32]: draft from earlier n-gram matches of the text and verify N ids per pass; 0 = off.')
+    p.add_argument('--prompt_lookup_ngram', type=int, default=3, help='longest n-gram the lookup matches, 1 to 8')
     return p.parse_args(args)
 
 
@@ -74,7 +78,7 @@ def load_session(engine_dir):
 
 def generate(max_output_len, log_level='error', engine_dir='llama_outputs', input_text=None, input_file=None,
              output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55, top_k=1, top_p=0.0,
-             temperature=1.0, repetition_penalty=1.0, random_seed=None):
+             temperature=1.0, repetition_penalty=1.0, random_seed=None, prompt_lookup_tokens=0, prompt_lookup_ngram=3):
     tensorrt_llm.logger.set_level(log_level)
     decoder, runtime_rank = load_session(engine_dir)
     sampling_config = SamplingConfig(end_id=EOS_TOKEN, pad_id=PAD_TOKEN, num_beams=num_beams, top_k=top_k, top_p=top_p,
@@ -97,8 +101,15 @@ def generate(max_output_len, log_level='error', engine_dir='llama_outputs', inpu
         else:
             ids = np.load(input_file).astype(np.int32).reshape(1, -1)
         input_lengths = np.array([ids.shape[1]], dtype=np.int32)
-        decoder.setup(ids.shape[0], int(input_lengths.max()), max_output_len)
-        output_ids = decoder.decode(ids, input_lengths, sampling_config)
+        if prompt_lookup_tokens:
+            # the last verify pass writes prompt_lookup_tokens cache rows from the current length: that much room behind the output
+            decoder.setup(ids.shape[0], int(input_lengths.max()), max_output_len + prompt_lookup_tokens)
+            output_ids = decoder.decode_lookup(ids, input_lengths, sampling_config, num_draft_tokens=prompt_lookup_tokens,
+                                               max_ngram=prompt_lookup_ngram, max_new_tokens=max_output_len)
+            output_ids = output_ids[:, :, :ids.shape[1] + max_output_len]
+        else:
+            decoder.setup(ids.shape[0], int(input_lengths.max()), max_output_len)
+            output_ids = decoder.decode(ids, input_lengths, sampling_config)
         if tokenizer is not None and runtime_rank == 0:
             outputs = output_ids[0, 0, ids.shape[1]:].tolist()
             tokenizer.decode(outputs)
@@ -116,6 +127,8 @@ def generate(max_output_len, log_level='error', engine_dir='llama_outputs', inpu
         if output_npy is not None:
             np.save(output_npy, out.astype(np.int32))
         print(total)
+        if prompt_lookup_tokens:
+            print(f'prompt lookup: {decoder.lookup_stats}')
         warm = total[5:] if len(total) > 5 else total
         print(f'llama-run (mean latency: {np.mean(warm)} sec)')
     return output_ids

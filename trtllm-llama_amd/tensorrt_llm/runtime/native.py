@@ -105,8 +105,92 @@ def _lib():
     lib.tllm_attention_append.restype = c.c_int32
     lib.tllm_attention_append_layout.argtypes = [c.POINTER(AttentionAppendParamsC), c.POINTER(c.c_int32)]
     lib.tllm_attention_append_layout.restype = c.c_int32
+    lib.tllm_session_verify.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.tllm_session_verify.restype = c.c_int32
+    lib.tllm_session_verify_top1.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
+    lib.tllm_session_verify_top1.restype = c.c_int32
+    lib.tllm_session_generate_lookup.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.c_int32,
+                                                 c.POINTER(LookupConfigC), c.c_void_p, c.POINTER(LookupStatsC), c.c_void_p]
+    lib.tllm_session_generate_lookup.restype = c.c_int32
+    lib.tllm_spec_accept.argtypes = [c.POINTER(SpecAcceptParamsC), c.c_void_p]
+    lib.tllm_spec_accept.restype = c.c_int32
+    lib.tllm_prompt_lookup.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
+                                       c.c_int32, c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.tllm_prompt_lookup.restype = c.c_int32
     _bound = True
     return lib
+
+
+VERIFY_MAX_TOKENS = 32  # TLLM_VERIFY_MAX_TOKENS
+
+
+class LookupConfigC(ctypes.Structure):
+    """tllm_lookup_config_t"""
+    _fields_ = [('num_draft_tokens', ctypes.c_int32), ('max_ngram', ctypes.c_int32)]
+
+
+class LookupStatsC(ctypes.Structure):
+    """tllm_lookup_stats_t"""
+    _fields_ = [(k, ctypes.c_int64) for k in ('rounds', 'verify_rounds', 'step_rounds', 'drafted', 'accepted')]
+
+
+class GreedyParamsC(ctypes.Structure):
+    """tllm_greedy_params_t"""
+    _fields_ = [('logits', ctypes.c_void_p), ('batch', ctypes.c_int32), ('vocab_part', ctypes.c_int32), ('nparts', ctypes.c_int32),
+                ('vocab', ctypes.c_int32), ('cur_ids', ctypes.c_void_p), ('out_ids', ctypes.c_void_p), ('out_stride', ctypes.c_int32),
+                ('seq_len', ctypes.c_void_p), ('finished', ctypes.c_void_p), ('end_id', ctypes.c_int32), ('advance', ctypes.c_int32),
+                ('rope_row_out', ctypes.c_void_p), ('rope_pos_out', ctypes.c_void_p), ('rope_table', ctypes.c_void_p),
+                ('rope_half', ctypes.c_int32), ('rope_table_len', ctypes.c_int32), ('input_lengths', ctypes.c_void_p),
+                ('max_input_len', ctypes.c_int32), ('emb_table', ctypes.c_void_p), ('x_out', ctypes.c_void_p),
+                ('hidden', ctypes.c_int32), ('step_epoch', ctypes.c_void_p), ('argmax_part', ctypes.c_void_p)]
+
+
+class SpecAcceptParamsC(ctypes.Structure):
+    """tllm_spec_accept_params_t"""
+    _fields_ = [('g', GreedyParamsC), ('n', ctypes.c_int32), ('ids', ctypes.c_void_p), ('top1', ctypes.c_void_p),
+                ('limit', ctypes.c_void_p), ('accepted', ctypes.c_void_p), ('logits_out', ctypes.c_void_p)]
+
+
+def spec_accept(ids, top1, *, logits, seq_len, finished, cur_ids, out_ids, end_id=-1, limit=None, accepted=None, logits_out=None,
+                rope_row_out=None, rope_pos_out=None, rope_table=None, input_lengths=None, max_input_len=0, emb_table=None,
+                x_out=None, step_epoch=None, vocab=None, stream: int = 0):
+    """tllm_spec_accept on torch cuda tensors (the rule: csrc/kernels/kernels.h SpecAcceptParams, spec_ref.accept): ids, top1 int32
+    [B, n]; logits f32 [B * n, vocab_part]; seq_len / finished / cur_ids / limit / accepted / input_lengths / rope_pos_out int32 [B];
+    out_ids int32 [B, Smax]; logits_out f32 [B, vocab_part]; rope_table f32 [len, half, 2], rope_row_out f32 [B, half, 2]; emb_table
+    fp16 [vocab, hidden], x_out fp16 [B, hidden]; step_epoch int32 / uint32 [>= 1].  The state tensors are updated in place."""
+    B, n = ids.shape
+    for t in (ids, top1, logits, seq_len, finished, cur_ids, out_ids, limit, accepted, logits_out, rope_row_out, rope_pos_out,
+              rope_table, input_lengths, emb_table, x_out, step_epoch):
+        assert t is None or (t.is_cuda and t.is_contiguous())
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    g = GreedyParamsC(logits=ptr(logits), batch=B, vocab_part=logits.shape[-1], nparts=1, vocab=vocab or logits.shape[-1],
+                      cur_ids=ptr(cur_ids), out_ids=ptr(out_ids), out_stride=out_ids.shape[1], seq_len=ptr(seq_len),
+                      finished=ptr(finished), end_id=end_id, advance=0, rope_row_out=ptr(rope_row_out),
+                      rope_pos_out=ptr(rope_pos_out), rope_table=ptr(rope_table),
+                      rope_half=rope_table.shape[1] if rope_table is not None else 0,
+                      rope_table_len=rope_table.shape[0] if rope_table is not None else 0, input_lengths=ptr(input_lengths),
+                      max_input_len=max_input_len, emb_table=ptr(emb_table), x_out=ptr(x_out),
+                      hidden=emb_table.shape[1] if emb_table is not None else 0, step_epoch=ptr(step_epoch), argmax_part=None)
+    p = SpecAcceptParamsC(g=g, n=n, ids=ptr(ids), top1=ptr(top1), limit=ptr(limit), accepted=ptr(accepted),
+                          logits_out=ptr(logits_out))
+    _check(_lib().tllm_spec_accept(ctypes.byref(p), stream), 'spec_accept')
+
+
+def prompt_lookup(out_ids, seq_len, n: int, max_ngram: int, *, max_input_len: int, vocab: int, input_lengths=None, finished=None,
+                  limit=None, stream: int = 0):
+    """tllm_prompt_lookup on torch cuda tensors (the rule: kernels.h PromptLookupParams, spec_ref.prompt_lookup): out_ids int32
+    [B, Smax], seq_len / input_lengths / finished / limit int32 [B] -> (ids int32 [B, n], draft_len int32 [B])."""
+    import torch
+    B, smax = out_ids.shape
+    for t in (out_ids, seq_len, input_lengths, finished, limit):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ids = torch.empty((B, n), dtype=torch.int32, device=out_ids.device)
+    dl = torch.empty(B, dtype=torch.int32, device=out_ids.device)
+    _check(_lib().tllm_prompt_lookup(out_ids.data_ptr(), B, smax, seq_len.data_ptr(), ptr(input_lengths), max_input_len,
+                                     ptr(finished), ptr(limit), vocab, n, max_ngram, ids.data_ptr(), dl.data_ptr(), stream),
+           'prompt_lookup')
+    return ids, dl
 
 
 class SamplingConfigC(ctypes.Structure):
@@ -422,6 +506,38 @@ class NativeSession:
         return int(w.value), int(m.value)
 
     attention_append = staticmethod(attention_append)
+    spec_accept = staticmethod(spec_accept)
+    prompt_lookup = staticmethod(prompt_lookup)
+
+    def verify(self, ids, stream: int = 0):
+        """Verify ids [batch, n] in one append pass (tllm_session_verify): ids[:, 0] takes the pending token's place, ids[:, 1:] are
+        drafts; the longest prefix greedy decoding would have produced is kept.  Returns (accepted int32 [batch]: drafts kept, -1 for
+        a finished sequence; log_probs f32 [batch, n]: log p(ids[b][i] | everything before it), 0 at i = 0).  logits() then holds
+        the row behind the last kept token and the arg-max of that row is the new pending token."""
+        ids = self._i32(ids)
+        assert ids.ndim == 2 and (not self.batch or ids.shape[0] == self.batch), 'ids must be [batch, n]'
+        acc = np.empty(ids.shape[0], np.int32)
+        lp = np.empty(ids.shape, np.float32)
+        _check(_lib().tllm_session_verify(self._h, ids.ctypes.data, ids.shape[1], acc.ctypes.data, lp.ctypes.data, stream), 'verify')
+        return acc, lp
+
+    def verify_top1(self, n: int, stream: int = 0) -> np.ndarray:
+        """the arg-max ids [batch, n] of the logits rows of the last verify() of n ids (tests)"""
+        top = np.empty((self.batch, n), np.int32)
+        _check(_lib().tllm_session_verify_top1(self._h, top.ctypes.data, n, stream), 'verify_top1')
+        return top
+
+    def generate_lookup(self, input_ids, input_lengths, max_new_tokens: int, end_id: int = -1, pad_id: int = 0,
+                        num_draft_tokens: int = 8, max_ngram: int = 3, stream: int = 0):
+        """generate() with prompt-lookup drafts verified num_draft_tokens ids at a time (tllm_session_generate_lookup): the same
+        tokens.  max_new_tokens + num_draft_tokens <= setup's max_new_tokens.  Returns (output_ids [batch, max_seq_len], stats:
+        dict(rounds, verify_rounds, step_rounds, drafted, accepted))."""
+        ids, lens = self._i32(input_ids), self._i32(input_lengths)
+        out = np.empty((self.batch, self.max_in + self.max_new), np.int32)
+        cfg, st = LookupConfigC(int(num_draft_tokens), int(max_ngram)), LookupStatsC()
+        _check(_lib().tllm_session_generate_lookup(self._h, ids.ctypes.data, lens.ctypes.data, max_new_tokens, end_id, pad_id,
+                                                   ctypes.byref(cfg), out.ctypes.data, ctypes.byref(st), stream), 'generate_lookup')
+        return out, {k: int(getattr(st, k)) for k, _ in LookupStatsC._fields_}
 
     def attention_tap(self, layer: int, heads_x_dh: int, quantised: bool, stream: int = 0) -> np.ndarray:
         """O-projection input of the last generation step (debug_taps=1): [batch * beam, H/tp * Dh] fp16, int8 for SmoothQuant."""
