@@ -216,15 +216,42 @@ int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* m
  * The cache rows of the rejected drafts stay behind the sequence length, where no launch reads them, and are overwritten by the
  * next tokens.  end_id is the session's (the last tllm_session_generate* call's; -1 after setup).  Synchronises the stream.
  * Refused, with nothing enqueued: everything tllm_session_append refuses; n > TLLM_VERIFY_MAX_TOKENS;
- * sequence_length[b] + n + 1 > max_seq_len; a sampling configuration that is not plain arg-max (speculative sampling is not built).
- * Not built: speculative sampling, a draft model, a different n per sequence, beam / paged / tensor-parallel sessions, a verify
- * pass in the one-launch form of the generation step. */
+ * sequence_length[b] + n + 1 > max_seq_len; a sampling configuration that is not plain arg-max (speculative sampling is not built
+ * into this entry: tllm_session_verify_sampled below takes it).
+ * Not built: a draft model with a soft distribution q and the rejection rule's residual distribution (speculative sampling is
+ * by exact match with the draw, below), a different n per sequence, beam / paged / tensor-parallel sessions, a verify pass in
+ * the one-launch form of the generation step. */
 #define TLLM_VERIFY_MAX_TOKENS 32
 int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
     tllm_stream_t stream);
 /* For tests: the arg-max ids a[b][i] of the n logits rows per sequence of the last verify pass, HOST int32 [B, n] (n as that
  * pass's; refused before any verify pass).  Synchronises the stream. */
 int32_t tllm_session_verify_top1(tllm_session_t s, int32_t* top1, int32_t n, tllm_stream_t stream);
+
+/* Speculative SAMPLING by exact match (the rule of the draws: csrc/kernels/kernels.h SpecSampleParams,
+ * restated in numpy in spec_ref.sample_rows).  tllm_session_verify under the session's sampling configuration
+ * (tllm_session_set_sampling): same arguments, same append pass, same head on all B * n rows, same log_probs (the raw model's
+ * log p, whatever the configuration), and the accept rule with the sampler's draws in the arg-maxes' place:
+ *   d[i] = the id the sampler selects from row i for generated-token number g = sequence_length[b] + i + 2 - max_input_len, with
+ *          the step's own uniform variate Philox(random_seed; b, g) and, for the penalties, the history prompt + record +
+ *          ids[b][0..i] - the token a plain sampled step would put behind ids[b][0..i];
+ *   m = 0; while (m + 1 < n && d[m] != end_id && ids[b][m + 1] == d[m]) ++m;   the new pending token is d[m].
+ * Draft i + 1 survives only where it EQUALS the draw of row i; the draw behind the last kept draft is the new pending token.  For
+ * one-hot drafts the acceptance probability is p(draft), the rejection rule's min(1, p / q) at q = 1 - and beyond equality in
+ * distribution the tokens are the very tokens tllm_session_generate yields for that configuration and seed, whatever the drafts
+ * and whatever n (up to the arithmetic of the logits: a verify row comes from the append's GEMMs, a step's from the GEMVs).
+ * With a configuration that is plain arg-max, or none, no sampler launch is made: the call is tllm_session_verify bit for bit.
+ * Refused: everything tllm_session_verify refuses except the sampling configuration.
+ * Not built: a draft model with a soft q and the residual-distribution rule. */
+int32_t tllm_session_verify_sampled(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
+    tllm_stream_t stream);
+/* For tests: the ids the last verify pass compared the drafts with, HOST int32 [B, n]: the draws d[b][i] after a sampled pass, the
+ * arg-maxes after a greedy one (rows of frozen sequences of a sampled pass hold end_id).  n as that pass's; refused before any
+ * verify pass.  Synchronises the stream. */
+int32_t tllm_session_verify_draws(tllm_session_t s, int32_t* draws, int32_t n, tllm_stream_t stream);
+/* For tests: the B * n logits rows of the last verify pass, HOST f32 [B, n, vocab].  n as that pass's; refused before any verify
+ * pass.  Synchronises the stream. */
+int32_t tllm_session_verify_logits(tllm_session_t s, float* logits, int32_t n, tllm_stream_t stream);
 
 /* tllm_session_generate with prompt-lookup drafts: the same tokens (greedy), fewer passes where the text repeats itself.
  * After tllm_session_context every round enqueues (1) the prompt lookup - per sequence the up to num_draft_tokens - 1 tokens that
@@ -249,6 +276,13 @@ typedef struct
     int64_t rounds, verify_rounds, step_rounds, drafted, accepted;
 } tllm_lookup_stats_t;
 int32_t tllm_session_generate_lookup(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg, int32_t* output_ids,
+    tllm_lookup_stats_t* stats, tllm_stream_t stream);
+/* tllm_session_generate_lookup under the session's sampling configuration: same signature, rounds and statistics.  A plain round
+ * is the graph's sampler step, a verify round is tllm_session_verify_sampled's pass.  The tokens are tllm_session_generate's for
+ * the same configuration and seed (see there for the one reservation, the arithmetic of the logits).  Refused: what
+ * tllm_session_generate_lookup refuses except the sampling configuration. */
+int32_t tllm_session_generate_lookup_sampled(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
     int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg, int32_t* output_ids,
     tllm_lookup_stats_t* stats, tllm_stream_t stream);
 
@@ -439,6 +473,17 @@ int32_t tllm_spec_accept(const tllm_spec_accept_params_t* p, tllm_stream_t strea
 int32_t tllm_prompt_lookup(const int32_t* out_ids, int32_t batch, int32_t out_stride, const int32_t* seq_len,
     const int32_t* input_lengths, int32_t max_input_len, const int32_t* finished, const int32_t* limit, int32_t vocab, int32_t n,
     int32_t max_ngram, int32_t* ids, int32_t* draft_len, tllm_stream_t stream);
+/* tllm_spec_sample_rows: the sampler on all n rows per sequence of a verify pass, on the caller's buffers (kernels.h
+ *   SpecSampleParams; the launcher tllm_session_verify_sampled uses).  All pointers DEVICE.  logits f32 [batch * n, vocab_part]
+ *   (nparts must be 1, vocab <= vocab_part; never written); ids int32 [batch, n]; out_ids int32 [batch, out_stride] the token
+ *   record (prompt slots [0, max_input_len), committed tokens behind; NULL when cfg sets no penalty); seq_len int32 [batch];
+ *   input_lengths / finished / limit int32 [batch] or NULL; draws int32 [batch, n]: the id drawn for generated-token number
+ *   seq_len[b] + i + 2 - max_input_len, end_id in the rows of a frozen sequence (finished, or seq_len >= limit); u_out optional
+ *   f32 [batch, n].  Refused: n outside [1, TLLM_VERIFY_MAX_TOKENS], nparts != 1, what tllm_sample_tokens refuses of cfg. */
+int32_t tllm_spec_sample_rows(const float* logits, int32_t nparts, int32_t batch, int32_t n, int32_t vocab_part, int32_t vocab,
+    const tllm_sampling_config_t* cfg, int32_t end_id, const int32_t* ids, const int32_t* out_ids, int32_t out_stride,
+    const int32_t* seq_len, const int32_t* input_lengths, int32_t max_input_len, const int32_t* finished, const int32_t* limit,
+    int32_t* draws, float* u_out, tllm_stream_t stream);
 /* Test/bench knob: persistent workgroups per CU (0 = occupancy query). */
 void tllm_gemv_set_blocks_per_cu(int32_t n);
 /* Test/bench knob: number of rows (sequences) from which the SmoothQuant decode GEMM runs on the matrix pipe

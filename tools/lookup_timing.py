@@ -6,7 +6,16 @@ and from the two the break-even acceptance  t_verify(n) / t_step - 1: the drafts
 plain steps (a round that keeps m drafts yields m + 1 tokens for t_verify; m + 1 steps cost (m + 1) t_step).
 The verify pass is timed as the caller sees it: the copy of the ids, the read of sequence_length ahead of the pass, the pass, the
 accept step and the read-back of its result.
-GPU only.    python tools/lookup_timing.py [--out profiles/prompt_lookup.txt]"""
+GPU only.    python tools/lookup_timing.py [--out profiles/prompt_lookup.txt]
+
+--sampled: speculative sampling by exact match instead -> profiles/spec_sampling.txt:
+  * the sample-rows launch at n = 2 / 8 / 32, vocab 32000, batch 1, beside the token_logprob and accept launches it joins;
+  * a sampled verify pass against a greedy one on the 7B configuration above (n = 8);
+  * the path difference on the deterministic trained parent (fp16): the largest distance, as a share of S, between the prefix sums
+    from the verify rows (the append pass's GEMMs) and from the step logits (the GEMVs) on the same forced tokens - what the margin of
+    the seed of tests/test_gpu_session_verify_sampled.py is held against - and the same on the tiny fixture of its front-end test;
+  * drafts offered and kept by generate_lookup(sampled=True) on the parent's evaluation prompts at temperature 0.7 and 1.0.
+             python tools/lookup_timing.py --sampled [--seed N] [--out profiles/spec_sampling.txt]"""
 import argparse, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'trtllm-llama_amd'))
@@ -14,8 +23,12 @@ import torch, numpy as np
 import bench
 from tensorrt_llm.runtime.native import NativeSession
 ap = argparse.ArgumentParser()
-ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'prompt_lookup.txt'))
+ap.add_argument('--out', default=None)
+ap.add_argument('--sampled', action='store_true')
+ap.add_argument('--seed', type=int, default=125, help='--sampled: the seed whose sampled continuation is one of the forced paths')
+ap.add_argument('--tiny_seed', type=int, default=112, help='--sampled: the same for the tiny fixture')
 args = ap.parse_args()
+args.out = args.out or os.path.join(ROOT, 'profiles', 'spec_sampling.txt' if args.sampled else 'prompt_lookup.txt')
 assert torch.cuda.is_available(), 'lookup_timing.py needs a GPU'
 cfg = dict(bench.LLAMA_7B, num_layers=32)
 V = cfg['vocab_size']
@@ -49,6 +62,13 @@ for k, t in w.items():
 s.finalize()
 s.setup(1, PAST, 512)
 r = np.random.default_rng(1)
+if args.sampled:
+    import lookup_timing_sampled
+    lookup_timing_sampled.run(s, cfg, stream, say, event_ms, args.seed, args.tiny_seed)
+    s.close()
+    with open(args.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
 say(f'7B SmoothQuant int8 + int8 KV, batch 1, synthetic weights, {PAST}-token cache (tllm_session_fake_context); ms, median (min) of '
     f'{RUNS} runs between device events, verify pass and graph steps alternating, one warm-up run of each dropped')
 say(f'decode form {s.decode_form()} (bit 0: projection + attention in one launch, bit 1: + the O-projection); the verify pass runs the '

@@ -651,7 +651,7 @@ struct SpecAcceptParams
     GreedyParams g;
     int32_t n = 0;                 // ids per sequence, 1 .. kVerifyMaxTokens
     const int32_t* ids = nullptr;  // int32 [batch, n]: t
-    const int32_t* top1 = nullptr; // int32 [batch, n]: a
+    const int32_t* top1 = nullptr; // int32 [batch, n]: a - the arg-maxes, or the draws of launch_spec_sample_rows (a sampled pass)
     const int32_t* limit = nullptr; // int32 [batch] or null
     int32_t* accepted = nullptr;   // int32 [batch] or null
     float* logits_out = nullptr;   // f32 [batch, vocab_part] or null
@@ -684,6 +684,36 @@ struct PromptLookupParams
 int launch_prompt_lookup(const PromptLookupParams& p, hipStream_t stream);
 // targets[b][i] = ids[b][i + 1], -1 at i = n - 1: the next-token targets of a verify pass's n rows (token_logprob)
 int launch_spec_targets(int32_t* targets, const int32_t* ids, int32_t batch, int32_t n, hipStream_t stream);
+
+// Speculative sampling by exact match (kernels/sampling.hip, beside the step kernel whose row draw it shares; DESIGN.md section
+// 7e; the numpy restatement is spec_ref.sample_rows): the sampler on ALL n rows of a verify pass, so that the accept step above
+// can compare the drafts with the DRAWS plain sampled decoding would have made instead of with the arg-maxes.  One workgroup per
+// (sequence b, row i < n); p = seq_len[b], t = ids[b], S = g_base = max_input_len.  Row (b, i) is row b * n + i of the logits:
+//   draws[b][i] = the id steps 1 - 5 of SamplingParams select from that row for generated-token number g = p + i + 2 - S - the
+//     token that would land in slot p + i + 1 - with u = Philox(random_seed; b, g), the step's own variate for that token;
+//   the row's history for the penalty: the real prompt tokens record[b][0 .. input_lengths[b]), the record [S .. p), then
+//     t[0..i] in the places of slots p .. p + i - from ids, not from the record: t[0] stands in the pending token's place and the
+//     drafts are not in the record yet.  Padding slots [input_lengths[b], S) are skipped, an id outside [0, vocab) is skipped;
+//   min_length masks end_id per row by the row's own g (it may hold for the first rows of a pass and not for the later ones);
+//   frozen (finished[b] != 0, p >= limit[b], or p < 0): the rows are not drawn, draws[b][i] = end_id (the accept step does not
+//     read them); u_out is written all the same.
+// A draw is a pure function of (logits row, history, seed, b, g): the same integer weight sums as the step, so draws[b][i] is
+// bit-identical to what launch_sampling_step selects for the same row, history and g, whatever n and whatever the other rows
+// hold.  The logits are never written.  Both forms of the step kernel are kept: y staged in LDS beside the history bitmap when
+// it fits, recomputed otherwise.
+// Fields read of s: the configuration (top_k .. random_seed), g_base, history = the token record int32 [batch, history_stride]
+// (NULL without a penalty), u_out (optional f32 [batch, n]); of s.g: logits f32 [batch * n, vocab_part] (nparts 1: anything else
+// is refused), batch, vocab_part, vocab, seq_len, finished (or NULL), end_id, input_lengths (or NULL = max_input_len),
+// max_input_len.  Nothing else of s.g is read and none of the step words is written.
+struct SpecSampleParams
+{
+    SamplingParams s;
+    int32_t n = 0;                  // rows per sequence, 1 .. kVerifyMaxTokens
+    const int32_t* ids = nullptr;   // int32 [batch, n]: t
+    const int32_t* limit = nullptr; // int32 [batch] or null
+    int32_t* draws = nullptr;       // int32 [batch, n]
+};
+int launch_spec_sample_rows(const SpecSampleParams& p, hipStream_t stream);
 
 // teacher forcing for parity tests: overwrite the sampler's last choice (output slot seq_len[b], step input id, next input row)
 int launch_force_token(const int32_t* ids_dev, int32_t* cur_ids, int32_t* out_ids, int32_t out_stride, const int32_t* seq_len,

@@ -1,5 +1,7 @@
 // Top-k / top-p sampling step with temperature, repetition / presence penalty and minimum length (SamplingParams in
 // kernels.h states the rule).  One workgroup of 1024 threads per row, plain launch, no waits on other workgroups.
+// Two kernels share the row draw (draw_row): sampling_step_kernel, one row per sequence with the step's bookkeeping, and
+// spec_sample_rows_kernel, all n rows per sequence of a verify pass and nothing else (SpecSampleParams in kernels.h).
 //
 // How the row is processed:
 //   * the row's history (real prompt tokens + generated tokens) becomes a membership bitmap in LDS (vocab / 8 bytes), the
@@ -136,21 +138,249 @@ __device__ __forceinline__ void scan_pick(const T* hist, NeedFn need_of_total, i
     }
 }
 
-__global__ __launch_bounds__(kThreads) void sampling_step_kernel(const SampleArgs a)
+// Steps 1 - 5 of the rule (SamplingParams in kernels.h) for ONE row, by the whole workgroup of kThreads threads: the body the step
+// kernel and the verify-rows kernel share, so that the two select the same id bit for bit.  The row is given by what the rule
+// reads: raw_logit(v) the fp32 logit of id v < V, for_history(mark) calls mark(id) for every id of the row's history (the
+// workgroup's threads share them out; called only with a penalty), gnum the generated-token number (min_length), u the variate.
+// dyn is the kernel's dynamic LDS (a.bm_words bitmap words, then V floats when a.staged).  Every thread returns the chosen id.
+template <typename LogitFn, typename HistoryFn>
+__device__ __forceinline__ int draw_row(const SampleArgs& a, const int V, const int end_id, const int gnum, const float u,
+    uint32_t* dyn, LogitFn raw_logit, HistoryFn for_history)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
     __shared__ uint64_t s_w[kBuckets];
     __shared__ uint32_t s_cnt[kBuckets];
     __shared__ uint32_t s_min[kBuckets];
     __shared__ uint64_t s_red[kThreads / 64];
     __shared__ uint64_t s_before, s_need;
-    __shared__ int s_d, s_id;
-
-    const GreedyParams& g = a.p.g;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int V = g.vocab;
+    __shared__ int s_d;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     uint32_t* bm = dyn;
     float* sy = reinterpret_cast<float*>(dyn + a.bm_words);
+    int chosen;
+
+    // ---- history bitmap
+    if (a.pen_mode)
+    {
+        for (int i = tid; i < a.bm_words; i += kThreads)
+            bm[i] = 0;
+        __syncthreads();
+        for_history([&](int id) {
+            if (id >= 0 && id < V)
+                atomicOr(&bm[id >> 5], 1u << (id & 31));
+        });
+        __syncthreads();
+    }
+    const bool mask_end = gnum < a.p.min_length && end_id >= 0 && end_id < V;
+    auto compute_y = [&](int v) -> float {
+        float y = raw_logit(v);
+        // separately rounded operations (no fused multiply-add across them): every pass and the host restatement get the same y
+        if (a.use_temp)
+            y = __fmul_rn(y, a.inv_temp);
+        if (a.pen_mode && ((bm[v >> 5] >> (v & 31)) & 1u))
+            y = a.pen_mode == 1 ? (y < 0.f ? __fmul_rn(y, a.pen) : __fdiv_rn(y, a.pen)) : __fsub_rn(y, a.pen);
+        if (mask_end && v == end_id)
+            y = -FLT_MAX;
+        if (!(y == y))
+            y = -INFINITY;
+        if (y == 0.f)
+            y = 0.f; // -0 -> +0: one key per value
+        return y;
+    };
+    auto get_y = [&](int v) -> float { return a.staged ? sy[v] : compute_y(v); };
+
+    // ---- pass 1: stage y, largest key of the row (= y_max and the arg-max with ties to the lowest id)
+    uint64_t best = 0;
+    constexpr int kBatch = 8; // loads of a thread in flight together (latency-bound otherwise, as the greedy step)
+    for (int v0 = tid; v0 < V; v0 += kThreads * kBatch)
+    {
+        float yy[kBatch];
+#pragma unroll
+        for (int e = 0; e < kBatch; ++e)
+        {
+            const int v = v0 + e * kThreads;
+            yy[e] = v < V ? compute_y(v) : -INFINITY;
+        }
+#pragma unroll
+        for (int e = 0; e < kBatch; ++e)
+        {
+            const int v = v0 + e * kThreads;
+            if (v < V)
+            {
+                if (a.staged)
+                    sy[v] = yy[e];
+                const uint64_t key = sort_key(yy[e], v);
+                best = key > best ? key : best;
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1)
+    {
+        const uint64_t o = shfl_xor_u64(best, m);
+        best = o > best ? o : best;
+    }
+    if (lane == 0)
+        s_red[wid] = best;
+    __syncthreads();
+    for (int w = 0; w < kThreads / 64; ++w)
+        best = s_red[w] > best ? s_red[w] : best;
+    const float ymax = key_value(best);
+    chosen = (int) ~(uint32_t) best;
+
+    if (a.kprime > 1 && ymax != -INFINITY)
+    {
+        // levels: the 4 bytes of the value image, then the bytes of ~id that can differ (the higher ones are 0xff for all)
+        int nid = 1;
+        while (nid < 4 && ((uint32_t) (V - 1) >> (8 * nid)))
+            ++nid;
+        const uint64_t fixed = nid == 4 ? 0ull : (uint64_t) (0xffffffffu << (8 * nid));
+        const int nlev = 4 + nid;
+        auto shift_of = [&](int l) { return l < 4 ? 56 - 8 * l : 8 * (nid - 1 - (l - 4)); };
+
+        // ---- the key of the k'-th candidate: everything >= kth is a candidate
+        uint64_t kth = 0;
+        if (a.kprime < V)
+        {
+            uint64_t prefix = fixed, mask = fixed, need = (uint64_t) a.kprime;
+            for (int l = 0; l < nlev; ++l)
+            {
+                const int sh = shift_of(l);
+                if (tid < kBuckets)
+                    s_cnt[tid] = 0;
+                __syncthreads();
+                int cur = -1;
+                uint32_t run = 0;
+                for (int v = tid; v < V; v += kThreads)
+                {
+                    const uint64_t key = sort_key(get_y(v), v);
+                    if ((key & mask) != prefix)
+                        continue;
+                    const int d = (int) (key >> sh) & 255;
+                    if (d != cur)
+                    {
+                        if (run)
+                            atomicAdd(&s_cnt[cur], run);
+                        cur = d;
+                        run = 0;
+                    }
+                    ++run;
+                }
+                if (run)
+                    atomicAdd(&s_cnt[cur], run);
+                __syncthreads();
+                if (wid == 0)
+                    scan_pick(s_cnt, [&](uint64_t) { return need; }, &s_d, &s_before, &s_need);
+                __syncthreads();
+                const int d = s_d & (kBuckets - 1);
+                need -= s_before;
+                prefix |= (uint64_t) d << sh;
+                mask |= 255ull << sh;
+                if ((uint64_t) s_cnt[d] == need) // the whole bucket belongs to the candidates
+                    break;
+                __syncthreads(); // s_cnt is cleared next
+            }
+            kth = prefix;
+            __syncthreads();
+        }
+
+        // ---- the crossing point of the prefix sum of the candidates' weights
+        auto weight = [&](float y) -> uint64_t {
+            if (y == ymax)
+                return (uint64_t) kFixedOne;
+            if (y == -INFINITY)
+                return 0ull;
+            return (uint64_t) (expf(y - ymax) * kFixedOne);
+        };
+        uint64_t prefix = fixed, mask = fixed, target = 0;
+        for (int l = 0; l < nlev; ++l)
+        {
+            const int sh = shift_of(l);
+            if (tid < kBuckets)
+            {
+                s_cnt[tid] = 0;
+                s_w[tid] = 0;
+                s_min[tid] = 0xffffffffu;
+            }
+            __syncthreads();
+            int cur = -1;
+            uint32_t run = 0, run_min = 0xffffffffu;
+            uint64_t run_w = 0;
+            auto flush = [&]() {
+                if (run)
+                {
+                    atomicAdd(&s_cnt[cur], run);
+                    atomicAdd(reinterpret_cast<unsigned long long*>(&s_w[cur]), (unsigned long long) run_w);
+                    atomicMin(&s_min[cur], run_min);
+                }
+            };
+            for (int v = tid; v < V; v += kThreads)
+            {
+                const float y = get_y(v);
+                const uint64_t key = sort_key(y, v);
+                if (key < kth || (key & mask) != prefix)
+                    continue;
+                const int d = (int) (key >> sh) & 255;
+                if (d != cur)
+                {
+                    flush();
+                    cur = d;
+                    run = 0;
+                    run_w = 0;
+                    run_min = 0xffffffffu;
+                }
+                ++run;
+                run_w += weight(y);
+                run_min = min(run_min, (uint32_t) v);
+            }
+            flush();
+            __syncthreads();
+            if (wid == 0)
+            {
+                if (l == 0)
+                    scan_pick(
+                        s_w,
+                        [&](uint64_t total) {
+                            // target = u * p' * S, as the smallest integer the integer prefix sums can reach
+                            const double t = ceil((double) u * (double) a.pprime * (double) total);
+                            uint64_t T = t >= 18446744073709551615.0 ? total : (uint64_t) t;
+                            T = T > total ? total : T;
+                            return T < 1 ? (uint64_t) 1 : T;
+                        },
+                        &s_d, &s_before, &s_need);
+                else
+                    scan_pick(s_w, [&](uint64_t) { return target; }, &s_d, &s_before, &s_need);
+            }
+            __syncthreads();
+            const int d = s_d & (kBuckets - 1);
+            target = s_need - s_before;
+            prefix |= (uint64_t) d << sh;
+            mask |= 255ull << sh;
+            if (s_cnt[d] == 1u)
+            {
+                chosen = (int) s_min[d];
+                break;
+            }
+            __syncthreads(); // the histograms are cleared next
+        }
+    }
+    return chosen;
+}
+
+// u in (0, 1] of row b's generated token number gnum: a function of (seed, b, gnum) and nothing else
+__device__ __forceinline__ float draw_uniform(uint64_t seed, int b, int gnum)
+{
+    const uint32_t r0 = philox4x32_10_word0((uint32_t) b, (uint32_t) gnum, 0u, 0u, (uint32_t) seed, (uint32_t) (seed >> 32));
+    return (float) ((r0 >> 8) + 1u) * 5.9604644775390625e-8f; // 2^-24
+}
+
+__global__ __launch_bounds__(kThreads) void sampling_step_kernel(const SampleArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+    __shared__ int s_id;
+
+    const GreedyParams& g = a.p.g;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int V = g.vocab;
 
     // read before thread 0 advances them (several barriers further down)
     const int slot = g.seq_len[b] + (g.advance ? 1 : 0); // where this token goes = slots of the row in use before it
@@ -169,231 +399,31 @@ __global__ __launch_bounds__(kThreads) void sampling_step_kernel(const SampleArg
             g.rope_pos_out[b] = pos;
     }
 
-    const uint32_t r0 = philox4x32_10_word0((uint32_t) b, (uint32_t) gnum, 0u, 0u, (uint32_t) a.p.random_seed,
-        (uint32_t) (a.p.random_seed >> 32));
-    const float u = (float) ((r0 >> 8) + 1u) * 5.9604644775390625e-8f; // 2^-24: (0, 1]
+    const float u = draw_uniform(a.p.random_seed, b, gnum);
     if (a.p.u_out && tid == 0)
         a.p.u_out[b] = u;
 
     int chosen = g.end_id;
     if (!was_finished) // uniform over the workgroup
-    {
-        // ---- history bitmap
-        if (a.pen_mode)
-        {
-            for (int i = tid; i < a.bm_words; i += kThreads)
-                bm[i] = 0;
-            __syncthreads();
-            const int32_t* h = a.p.history + (int64_t) b * a.p.history_stride;
-            const int n_prompt = g.input_lengths ? min(g.input_lengths[b], g.max_input_len) : g.max_input_len;
-            // generated tokens behind the prompt slots; clamped BEFORE the sum (g is the caller's through tllm_sample_tokens)
-            const int room = max(a.p.history_stride - g.max_input_len, 0);
-            const int hist_end = min(g.max_input_len, a.p.history_stride) + min(max(gnum - 1, 0), room);
-            for (int t = tid; t < hist_end; t += kThreads)
-            {
-                if (t >= n_prompt && t < g.max_input_len) // padding slots
-                    continue;
-                const int id = h[t];
-                if (id >= 0 && id < V)
-                    atomicOr(&bm[id >> 5], 1u << (id & 31));
-            }
-            __syncthreads();
-        }
-        const bool mask_end = gnum < a.p.min_length && g.end_id >= 0 && g.end_id < V;
-        auto compute_y = [&](int v) -> float {
-            const int part = v / g.vocab_part, vi = v - part * g.vocab_part;
-            float y = g.logits[((int64_t) part * g.batch + b) * g.vocab_part + vi];
-            // separately rounded operations (no fused multiply-add across them): every pass and the host restatement get the same y
-            if (a.use_temp)
-                y = __fmul_rn(y, a.inv_temp);
-            if (a.pen_mode && ((bm[v >> 5] >> (v & 31)) & 1u))
-                y = a.pen_mode == 1 ? (y < 0.f ? __fmul_rn(y, a.pen) : __fdiv_rn(y, a.pen)) : __fsub_rn(y, a.pen);
-            if (mask_end && v == g.end_id)
-                y = -FLT_MAX;
-            if (!(y == y))
-                y = -INFINITY;
-            if (y == 0.f)
-                y = 0.f; // -0 -> +0: one key per value
-            return y;
-        };
-        auto get_y = [&](int v) -> float { return a.staged ? sy[v] : compute_y(v); };
-
-        // ---- pass 1: stage y, largest key of the row (= y_max and the arg-max with ties to the lowest id)
-        uint64_t best = 0;
-        constexpr int kBatch = 8; // loads of a thread in flight together (latency-bound otherwise, as the greedy step)
-        for (int v0 = tid; v0 < V; v0 += kThreads * kBatch)
-        {
-            float yy[kBatch];
-#pragma unroll
-            for (int e = 0; e < kBatch; ++e)
-            {
-                const int v = v0 + e * kThreads;
-                yy[e] = v < V ? compute_y(v) : -INFINITY;
-            }
-#pragma unroll
-            for (int e = 0; e < kBatch; ++e)
-            {
-                const int v = v0 + e * kThreads;
-                if (v < V)
+        chosen = draw_row(
+            a, V, g.end_id, gnum, u, dyn,
+            [&](int v) -> float {
+                const int part = v / g.vocab_part, vi = v - part * g.vocab_part;
+                return g.logits[((int64_t) part * g.batch + b) * g.vocab_part + vi];
+            },
+            [&](auto mark) {
+                const int32_t* h = a.p.history + (int64_t) b * a.p.history_stride;
+                const int n_prompt = g.input_lengths ? min(g.input_lengths[b], g.max_input_len) : g.max_input_len;
+                // generated tokens behind the prompt slots; clamped BEFORE the sum (g is the caller's through tllm_sample_tokens)
+                const int room = max(a.p.history_stride - g.max_input_len, 0);
+                const int hist_end = min(g.max_input_len, a.p.history_stride) + min(max(gnum - 1, 0), room);
+                for (int t = tid; t < hist_end; t += kThreads)
                 {
-                    if (a.staged)
-                        sy[v] = yy[e];
-                    const uint64_t key = sort_key(yy[e], v);
-                    best = key > best ? key : best;
-                }
-            }
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1)
-        {
-            const uint64_t o = shfl_xor_u64(best, m);
-            best = o > best ? o : best;
-        }
-        if (lane == 0)
-            s_red[wid] = best;
-        __syncthreads();
-        for (int w = 0; w < kThreads / 64; ++w)
-            best = s_red[w] > best ? s_red[w] : best;
-        const float ymax = key_value(best);
-        chosen = (int) ~(uint32_t) best;
-
-        if (a.kprime > 1 && ymax != -INFINITY)
-        {
-            // levels: the 4 bytes of the value image, then the bytes of ~id that can differ (the higher ones are 0xff for all)
-            int nid = 1;
-            while (nid < 4 && ((uint32_t) (V - 1) >> (8 * nid)))
-                ++nid;
-            const uint64_t fixed = nid == 4 ? 0ull : (uint64_t) (0xffffffffu << (8 * nid));
-            const int nlev = 4 + nid;
-            auto shift_of = [&](int l) { return l < 4 ? 56 - 8 * l : 8 * (nid - 1 - (l - 4)); };
-
-            // ---- the key of the k'-th candidate: everything >= kth is a candidate
-            uint64_t kth = 0;
-            if (a.kprime < V)
-            {
-                uint64_t prefix = fixed, mask = fixed, need = (uint64_t) a.kprime;
-                for (int l = 0; l < nlev; ++l)
-                {
-                    const int sh = shift_of(l);
-                    if (tid < kBuckets)
-                        s_cnt[tid] = 0;
-                    __syncthreads();
-                    int cur = -1;
-                    uint32_t run = 0;
-                    for (int v = tid; v < V; v += kThreads)
-                    {
-                        const uint64_t key = sort_key(get_y(v), v);
-                        if ((key & mask) != prefix)
-                            continue;
-                        const int d = (int) (key >> sh) & 255;
-                        if (d != cur)
-                        {
-                            if (run)
-                                atomicAdd(&s_cnt[cur], run);
-                            cur = d;
-                            run = 0;
-                        }
-                        ++run;
-                    }
-                    if (run)
-                        atomicAdd(&s_cnt[cur], run);
-                    __syncthreads();
-                    if (wid == 0)
-                        scan_pick(s_cnt, [&](uint64_t) { return need; }, &s_d, &s_before, &s_need);
-                    __syncthreads();
-                    const int d = s_d & (kBuckets - 1);
-                    need -= s_before;
-                    prefix |= (uint64_t) d << sh;
-                    mask |= 255ull << sh;
-                    if ((uint64_t) s_cnt[d] == need) // the whole bucket belongs to the candidates
-                        break;
-                    __syncthreads(); // s_cnt is cleared next
-                }
-                kth = prefix;
-                __syncthreads();
-            }
-
-            // ---- the crossing point of the prefix sum of the candidates' weights
-            auto weight = [&](float y) -> uint64_t {
-                if (y == ymax)
-                    return (uint64_t) kFixedOne;
-                if (y == -INFINITY)
-                    return 0ull;
-                return (uint64_t) (expf(y - ymax) * kFixedOne);
-            };
-            uint64_t prefix = fixed, mask = fixed, target = 0;
-            for (int l = 0; l < nlev; ++l)
-            {
-                const int sh = shift_of(l);
-                if (tid < kBuckets)
-                {
-                    s_cnt[tid] = 0;
-                    s_w[tid] = 0;
-                    s_min[tid] = 0xffffffffu;
-                }
-                __syncthreads();
-                int cur = -1;
-                uint32_t run = 0, run_min = 0xffffffffu;
-                uint64_t run_w = 0;
-                auto flush = [&]() {
-                    if (run)
-                    {
-                        atomicAdd(&s_cnt[cur], run);
-                        atomicAdd(reinterpret_cast<unsigned long long*>(&s_w[cur]), (unsigned long long) run_w);
-                        atomicMin(&s_min[cur], run_min);
-                    }
-                };
-                for (int v = tid; v < V; v += kThreads)
-                {
-                    const float y = get_y(v);
-                    const uint64_t key = sort_key(y, v);
-                    if (key < kth || (key & mask) != prefix)
+                    if (t >= n_prompt && t < g.max_input_len) // padding slots
                         continue;
-                    const int d = (int) (key >> sh) & 255;
-                    if (d != cur)
-                    {
-                        flush();
-                        cur = d;
-                        run = 0;
-                        run_w = 0;
-                        run_min = 0xffffffffu;
-                    }
-                    ++run;
-                    run_w += weight(y);
-                    run_min = min(run_min, (uint32_t) v);
+                    mark(h[t]);
                 }
-                flush();
-                __syncthreads();
-                if (wid == 0)
-                {
-                    if (l == 0)
-                        scan_pick(
-                            s_w,
-                            [&](uint64_t total) {
-                                // target = u * p' * S, as the smallest integer the integer prefix sums can reach
-                                const double t = ceil((double) u * (double) a.pprime * (double) total);
-                                uint64_t T = t >= 18446744073709551615.0 ? total : (uint64_t) t;
-                                T = T > total ? total : T;
-                                return T < 1 ? (uint64_t) 1 : T;
-                            },
-                            &s_d, &s_before, &s_need);
-                    else
-                        scan_pick(s_w, [&](uint64_t) { return target; }, &s_d, &s_before, &s_need);
-                }
-                __syncthreads();
-                const int d = s_d & (kBuckets - 1);
-                target = s_need - s_before;
-                prefix |= (uint64_t) d << sh;
-                mask |= 255ull << sh;
-                if (s_cnt[d] == 1u)
-                {
-                    chosen = (int) s_min[d];
-                    break;
-                }
-                __syncthreads(); // the histograms are cleared next
-            }
-        }
-    }
+            });
 
     // ---- bookkeeping: a second copy of greedy_step_kernel's (decode_step.hip), not shared code - the RoPE row above, the commit,
     // step_epoch and the next input row below must be edited in both kernels together
@@ -432,11 +462,149 @@ __global__ __launch_bounds__(kThreads) void sampling_step_kernel(const SampleArg
     }
 }
 
+// The draw on all n rows of a verify pass (SpecSampleParams in kernels.h): workgroup (b, i) draws, from logits row b * n + i, the
+// token plain sampled decoding would put behind t[0..i].  Nothing of the step's bookkeeping: the accept step commits.
+struct SpecSampleArgs
+{
+    SampleArgs a;
+    int32_t n = 0;
+    const int32_t* ids = nullptr;
+    const int32_t* limit = nullptr;
+    int32_t* draws = nullptr;
+};
+
+__global__ __launch_bounds__(kThreads) void spec_sample_rows_kernel(const SpecSampleArgs q)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+    const SampleArgs& a = q.a;
+    const GreedyParams& g = a.p.g;
+    const int n = q.n, b = blockIdx.x / n, i = blockIdx.x - b * n, tid = threadIdx.x;
+    const int V = g.vocab, S = g.max_input_len;
+    const int p = g.seq_len[b];
+    const int lim = q.limit ? q.limit[b] : 0x7fffffff;
+    const bool frozen = (g.finished && g.finished[b] != 0) || p >= lim || p < 0;
+    const int gnum = (int) ((int64_t) p + i + 2 - a.p.g_base); // the token of slot p + i + 1
+    const int64_t row = (int64_t) b * n + i;
+
+    const float u = draw_uniform(a.p.random_seed, b, gnum);
+    if (a.p.u_out && tid == 0)
+        a.p.u_out[row] = u;
+
+    int chosen = g.end_id;
+    if (!frozen) // uniform over the workgroup
+        chosen = draw_row(
+            a, V, g.end_id, gnum, u, dyn, [&](int v) -> float { return g.logits[row * g.vocab_part + v]; },
+            [&](auto mark) {
+                const int32_t* h = a.p.history + (int64_t) b * a.p.history_stride;
+                const int32_t* t = q.ids + (int64_t) b * n;
+                const int n_prompt = g.input_lengths ? min(g.input_lengths[b], S) : S;
+                const int rec_end = min(p, a.p.history_stride); // the record: the prompt and the tokens committed before the pass
+                for (int s = tid; s < rec_end; s += kThreads)
+                {
+                    if (s >= n_prompt && s < S) // padding slots
+                        continue;
+                    mark(h[s]);
+                }
+                for (int j = tid; j <= i; j += kThreads) // t[0..i] in the places of slots p .. p + i
+                {
+                    const int64_t s = (int64_t) p + j;
+                    if (s >= n_prompt && s < S)
+                        continue;
+                    mark(t[j]);
+                }
+            });
+    if (tid == 0)
+        q.draws[row] = chosen;
+}
+
 } // namespace
 
 bool sampling_is_greedy(const SamplingParams& p)
 {
     return p.top_k == 1 && p.temperature == 1.f && p.repetition_penalty == 1.f && p.presence_penalty == 0.f && p.min_length <= 1;
+}
+
+// What both launchers derive from the configuration: the checks of its fields, k' and p', the penalty mode, and the dynamic LDS
+// (history bitmap, then the staged row when it fits beside it).  *dyn_out = bytes of dynamic LDS.
+static int derive_args(SampleArgs& a, size_t& dyn_out, const SamplingParams& p, const char* who)
+{
+    const GreedyParams& g = p.g;
+    if (!(p.temperature > 0.f) || p.top_k < 0 || !(p.top_p >= 0.f) || !(p.repetition_penalty > 0.f))
+    {
+        set_error("%s: needs temperature > 0, top_k >= 0, top_p >= 0, repetition_penalty > 0", who);
+        return -1;
+    }
+    if (p.repetition_penalty != 1.f && p.presence_penalty != 0.f)
+    {
+        set_error("%s: repetition_penalty and presence_penalty are mutually exclusive", who);
+        return -1;
+    }
+    a.p = p;
+    // layers/topKSamplingLayer.cu:42-60
+    int k = p.top_k;
+    float pp = p.top_p > 1.f ? 1.f : p.top_p;
+    if (k == 0 && pp == 0.f)
+        k = 1;
+    else if (k > 0 && pp == 0.f)
+        pp = 1.f;
+    k = k == 0 ? g.vocab : (k > 1024 ? 1024 : k);
+    a.kprime = k > g.vocab ? g.vocab : k;
+    a.pprime = pp;
+    a.use_temp = p.temperature != 1.f;
+    a.inv_temp = 1.f / (p.temperature + 1e-6f);
+    a.pen_mode = p.repetition_penalty != 1.f ? 1 : (p.presence_penalty != 0.f ? 2 : 0);
+    a.pen = a.pen_mode == 1 ? p.repetition_penalty : p.presence_penalty;
+    if (a.pen_mode && (!p.history || p.history_stride <= 0))
+    {
+        set_error("%s: a penalty needs the row's token history", who);
+        return -1;
+    }
+    a.bm_words = a.pen_mode ? (g.vocab + 31) / 32 : 0;
+    const size_t bm_bytes = (size_t) a.bm_words * 4, row_bytes = (size_t) g.vocab * 4;
+    if (bm_bytes > kDynLdsBudget)
+    {
+        set_error("%s: the history bitmap of a vocabulary of %d does not fit the LDS", who, g.vocab);
+        return -1;
+    }
+    a.staged = bm_bytes + row_bytes <= kDynLdsBudget;
+    dyn_out = bm_bytes + (a.staged ? row_bytes : 0);
+    return 0;
+}
+
+int launch_spec_sample_rows(const SpecSampleParams& p, hipStream_t stream)
+{
+    const GreedyParams& g = p.s.g;
+    if (g.batch <= 0)
+        return 0;
+    if (p.n < 1 || p.n > kVerifyMaxTokens)
+    {
+        set_error("spec sample rows: n %d outside [1, %d]", p.n, kVerifyMaxTokens);
+        return -1;
+    }
+    if (g.nparts != 1)
+    {
+        set_error("spec sample rows: the verify rows come in one vocabulary part (got %d parts)", g.nparts);
+        return -1;
+    }
+    if (!g.logits || !g.seq_len || !p.ids || !p.draws || g.vocab <= 0 || g.vocab_part < g.vocab || g.max_input_len < 0)
+    {
+        set_error("spec sample rows: bad arguments (the logits rows, seq_len, the ids and the draws are needed, vocab %d <= vocab_part %d)",
+            g.vocab, g.vocab_part);
+        return -1;
+    }
+    SpecSampleArgs q;
+    size_t dyn = 0;
+    if (derive_args(q.a, dyn, p.s, "spec sample rows"))
+        return -1;
+    q.n = p.n;
+    q.ids = p.ids;
+    q.limit = p.limit;
+    q.draws = p.draws;
+    const void* kfn = reinterpret_cast<const void*>(spec_sample_rows_kernel);
+    if (dyn > 64 * 1024)
+        launch_util::ensure_dynamic_lds(kfn, kDynLdsBudget);
+    hipLaunchKernelGGL(spec_sample_rows_kernel, dim3(g.batch * p.n), dim3(kThreads), dyn, stream, q);
+    return launch_util::check_launch("spec_sample_rows");
 }
 
 int launch_sampling_step(const SamplingParams& p, hipStream_t stream)
@@ -460,46 +628,10 @@ int launch_sampling_step(const SamplingParams& p, hipStream_t stream)
         set_error("sampling step: the RoPE row needs its table, input_lengths and rope_half <= %d", kThreads - 64);
         return -1;
     }
-    if (!(p.temperature > 0.f) || p.top_k < 0 || !(p.top_p >= 0.f) || !(p.repetition_penalty > 0.f))
-    {
-        set_error("sampling step: needs temperature > 0, top_k >= 0, top_p >= 0, repetition_penalty > 0");
-        return -1;
-    }
-    if (p.repetition_penalty != 1.f && p.presence_penalty != 0.f)
-    {
-        set_error("sampling step: repetition_penalty and presence_penalty are mutually exclusive");
-        return -1;
-    }
     SampleArgs a;
-    a.p = p;
-    // layers/topKSamplingLayer.cu:42-60
-    int k = p.top_k;
-    float pp = p.top_p > 1.f ? 1.f : p.top_p;
-    if (k == 0 && pp == 0.f)
-        k = 1;
-    else if (k > 0 && pp == 0.f)
-        pp = 1.f;
-    k = k == 0 ? g.vocab : (k > 1024 ? 1024 : k);
-    a.kprime = k > g.vocab ? g.vocab : k;
-    a.pprime = pp;
-    a.use_temp = p.temperature != 1.f;
-    a.inv_temp = 1.f / (p.temperature + 1e-6f);
-    a.pen_mode = p.repetition_penalty != 1.f ? 1 : (p.presence_penalty != 0.f ? 2 : 0);
-    a.pen = a.pen_mode == 1 ? p.repetition_penalty : p.presence_penalty;
-    if (a.pen_mode && (!p.history || p.history_stride <= 0))
-    {
-        set_error("sampling step: a penalty needs the row's token history");
+    size_t dyn = 0;
+    if (derive_args(a, dyn, p, "sampling step"))
         return -1;
-    }
-    a.bm_words = a.pen_mode ? (g.vocab + 31) / 32 : 0;
-    const size_t bm_bytes = (size_t) a.bm_words * 4, row_bytes = (size_t) g.vocab * 4;
-    if (bm_bytes > kDynLdsBudget)
-    {
-        set_error("sampling step: the history bitmap of a vocabulary of %d does not fit the LDS", g.vocab);
-        return -1;
-    }
-    a.staged = bm_bytes + row_bytes <= kDynLdsBudget;
-    const size_t dyn = bm_bytes + (a.staged ? row_bytes : 0);
     const void* kfn = reinterpret_cast<const void*>(sampling_step_kernel);
     if (dyn > 64 * 1024)
         launch_util::ensure_dynamic_lds(kfn, kDynLdsBudget);

@@ -651,6 +651,41 @@ int32_t tllm_sample_tokens(const float* logits, int32_t nparts, int32_t rows, in
     return launch_sampling_step(sp, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
+int32_t tllm_spec_sample_rows(const float* logits, int32_t nparts, int32_t batch, int32_t n, int32_t vocab_part, int32_t vocab,
+    const tllm_sampling_config_t* cfg, int32_t end_id, const int32_t* ids, const int32_t* out_ids, int32_t out_stride,
+    const int32_t* seq_len, const int32_t* input_lengths, int32_t max_input_len, const int32_t* finished, const int32_t* limit,
+    int32_t* draws, float* u_out, tllm_stream_t stream)
+{
+    if (!logits || !cfg || !ids || !seq_len || !draws || batch < 1 || max_input_len < 0 || (out_ids && out_stride < 1))
+    {
+        set_error("tllm_spec_sample_rows: bad arguments");
+        return 1;
+    }
+    if (const int rc = check_sampling_config("tllm_spec_sample_rows", *cfg))
+        return rc;
+    SpecSampleParams sp;
+    sampling_from_config(sp.s, *cfg);
+    sp.s.g.logits = logits;
+    sp.s.g.batch = batch;
+    sp.s.g.vocab_part = vocab_part;
+    sp.s.g.nparts = nparts;
+    sp.s.g.vocab = vocab;
+    sp.s.g.seq_len = const_cast<int32_t*>(seq_len); // read only
+    sp.s.g.finished = const_cast<int32_t*>(finished);
+    sp.s.g.end_id = end_id;
+    sp.s.g.input_lengths = input_lengths;
+    sp.s.g.max_input_len = max_input_len;
+    sp.s.g_base = max_input_len;
+    sp.s.history = out_ids;
+    sp.s.history_stride = out_ids ? out_stride : 0;
+    sp.s.u_out = u_out;
+    sp.n = n;
+    sp.ids = ids;
+    sp.limit = limit;
+    sp.draws = draws;
+    return launch_spec_sample_rows(sp, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
 int32_t tllm_token_logprobs(const float* logits, int32_t nparts, int32_t rows, int32_t vocab_part, int32_t vocab,
     const int32_t* targets, float* partials, float* log_probs, float* lse, int32_t* top1_ids, tllm_stream_t stream)
 {

@@ -480,23 +480,25 @@ int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* m
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------ speculative greedy decoding
-static int32_t verify_session_ok(tllm_session_t s, const char* who)
+// ------------------------------------------------------------------------------------------ speculative decoding
+// What a session must be for a verify pass.  The greedy entries refuse a sampling configuration that is not plain arg-max (their
+// accept rule compares with the arg-max); the *_sampled entries take it.
+static int32_t verify_session_ok(tllm_session_t s, const char* who, bool sampled)
 {
     RUN(append_session_ok(s, who));
-    if (s->sampling_on && !sampling_is_greedy(s->sampling))
+    if (!sampled && s->sampling_on && !sampling_is_greedy(s->sampling))
     {
-        set_error("%s: the session samples (top-k / top-p / penalties): the accept rule is greedy - speculative sampling is not built", who);
+        set_error("%s: the session samples (top-k / top-p / penalties): the accept rule is greedy - speculative sampling is not built "
+                  "into this entry: use %s_sampled", who, who);
         return 1;
     }
     return 0;
 }
 
-int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
-    tllm_stream_t stream)
+static int32_t verify_entry(tllm_session_t s, const char* who, bool sampled, const int32_t* ids, int32_t n, int32_t* accepted,
+    float* log_probs, tllm_stream_t stream)
 {
-    const char* who = "tllm_session_verify";
-    RUN(verify_session_ok(s, who) ? 1 : 0);
+    RUN(verify_session_ok(s, who, sampled) ? 1 : 0);
     if (!accepted)
     {
         set_error("%s: null argument", who);
@@ -515,7 +517,7 @@ int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int
     const int B = s->B;
     HIP_OK(hipMemcpyAsync(s->ids_in, ids, (size_t) B * n * 4, hipMemcpyHostToDevice, st));
     HIP_OK(hipStreamSynchronize(st)); // the caller's buffer may go out of scope
-    RUN(s->run_verify(n, max_past, nullptr, st) ? 1 : 0);
+    RUN(s->run_verify(n, max_past, nullptr, sampled, st) ? 1 : 0);
     HIP_OK(hipMemcpyAsync(accepted, s->verify.accepted, (size_t) B * 4, hipMemcpyDeviceToHost, st));
     if (log_probs) // row (b, i - 1) scored ids[b][i]; its last row had no target and scored 0
     {
@@ -527,6 +529,18 @@ int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int
     }
     HIP_OK(hipStreamSynchronize(st));
     return s->check_comm() ? 1 : 0;
+}
+
+int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
+    tllm_stream_t stream)
+{
+    return verify_entry(s, "tllm_session_verify", false, ids, n, accepted, log_probs, stream);
+}
+
+int32_t tllm_session_verify_sampled(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
+    tllm_stream_t stream)
+{
+    return verify_entry(s, "tllm_session_verify_sampled", true, ids, n, accepted, log_probs, stream);
 }
 
 int32_t tllm_session_verify_top1(tllm_session_t s, int32_t* top1, int32_t n, tllm_stream_t stream)
@@ -542,12 +556,39 @@ int32_t tllm_session_verify_top1(tllm_session_t s, int32_t* top1, int32_t n, tll
     return 0;
 }
 
-int32_t tllm_session_generate_lookup(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
-    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg, int32_t* output_ids,
-    tllm_lookup_stats_t* stats, tllm_stream_t stream)
+int32_t tllm_session_verify_draws(tllm_session_t s, int32_t* draws, int32_t n, tllm_stream_t stream)
 {
-    const char* who = "tllm_session_generate_lookup";
-    RUN(verify_session_ok(s, who) ? 1 : 0);
+    if (!s || !s->B || !draws || !s->verify_cmp || n != s->verify_n)
+    {
+        set_error("tllm_session_verify_draws: bad arguments, or no verify pass of n = %d ids has run since setup", n);
+        return 1;
+    }
+    hipStream_t st = s->pick(stream);
+    HIP_OK(hipMemcpyAsync(draws, s->verify_cmp, (size_t) s->B * n * 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int32_t tllm_session_verify_logits(tllm_session_t s, float* logits, int32_t n, tllm_stream_t stream)
+{
+    if (!s || !s->B || !logits || !s->verify.logits || n != s->verify_n)
+    {
+        set_error("tllm_session_verify_logits: bad arguments, or no verify pass of n = %d ids has run since setup", n);
+        return 1;
+    }
+    hipStream_t st = s->pick(stream);
+    // the rows are Vr floats apart on the device, vocab of them are ids
+    HIP_OK(hipMemcpy2DAsync(logits, (size_t) s->vocab * 4, s->verify.logits, (size_t) s->Vr * 4, (size_t) s->vocab * 4,
+        (size_t) s->B * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+static int32_t generate_lookup_entry(tllm_session_t s, const char* who, bool sampled, const int32_t* input_ids,
+    const int32_t* input_lengths, int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg,
+    int32_t* output_ids, tllm_lookup_stats_t* stats, tllm_stream_t stream)
+{
+    RUN(verify_session_ok(s, who, sampled) ? 1 : 0);
     if (!input_ids || !input_lengths || !output_ids || !cfg)
     {
         set_error("%s: null argument", who);
@@ -643,7 +684,7 @@ int32_t tllm_session_generate_lookup(tllm_session_t s, const int32_t* input_ids,
             }
             for (int b = 0; b < B; ++b)
                 acc.drafted += state[(size_t) b * 4 + 2];
-            RUN(s->run_verify(n, max_past, s->verify.limit, st) ? 1 : 0);
+            RUN(s->run_verify(n, max_past, s->verify.limit, sampled, st) ? 1 : 0);
             verify_pending = true;
             acc.verify_rounds += 1;
         }
@@ -655,6 +696,22 @@ int32_t tllm_session_generate_lookup(tllm_session_t s, const int32_t* input_ids,
     if (stats)
         *stats = acc;
     return 0;
+}
+
+int32_t tllm_session_generate_lookup(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg, int32_t* output_ids,
+    tllm_lookup_stats_t* stats, tllm_stream_t stream)
+{
+    return generate_lookup_entry(s, "tllm_session_generate_lookup", false, input_ids, input_lengths, max_new_tokens, end_id, pad_id,
+        cfg, output_ids, stats, stream);
+}
+
+int32_t tllm_session_generate_lookup_sampled(tllm_session_t s, const int32_t* input_ids, const int32_t* input_lengths,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, const tllm_lookup_config_t* cfg, int32_t* output_ids,
+    tllm_lookup_stats_t* stats, tllm_stream_t stream)
+{
+    return generate_lookup_entry(s, "tllm_session_generate_lookup_sampled", true, input_ids, input_lengths, max_new_tokens, end_id,
+        pad_id, cfg, output_ids, stats, stream);
 }
 
 int32_t tllm_session_get_logits(tllm_session_t s, float* logits, tllm_stream_t stream)

@@ -257,11 +257,13 @@ struct tllm_session
         float* rec = nullptr;       // [B * kVerifyMaxTokens, 8] token_logprob records
         float* log_probs = nullptr; // [B * kVerifyMaxTokens]
         int32_t* top1 = nullptr;    // [B * kVerifyMaxTokens]
+        int32_t* draws = nullptr;   // [B * kVerifyMaxTokens] the sampler's draw of every row (a sampled pass: launch_spec_sample_rows)
         int32_t* accepted = nullptr; // [B]
         int32_t* limit = nullptr;    // [B] largest sequence length the lookup loop may leave
         int32_t* state = nullptr;    // [B, 4] the prompt lookup's {seq_len, finished, draft_len, frozen}
     } verify;
     int verify_n = 0; // ids per sequence of the last verify pass (0: none since setup)
+    const int32_t* verify_cmp = nullptr; // what that pass's accept step compared the drafts with: verify.top1 or verify.draws
     std::vector<int32_t> score_pos;  // host: output slot b * max_in + t + 1 of every scored row of the current call
     std::vector<float> score_lp_host;
     std::vector<int32_t> score_top_host;
@@ -340,8 +342,10 @@ struct tllm_session
     int run_append(int n, int max_past, hipStream_t st);
     int append_layers(int n, int max_past, hipStream_t st); // embedding + every layer on the B * n rows (ids in ids_in)
     // tllm_session_verify: append_layers, then the head on ALL B * n rows (fp32, verify.logits), their scoring (verify.top1 /
-    // .log_probs against the next id of the row) and the accept step in the sampler's place; limit: device int32 [B] or null
-    int run_verify(int n, int max_past, const int32_t* limit, hipStream_t st);
+    // .log_probs against the next id of the row) and the accept step in the sampler's place; limit: device int32 [B] or null.
+    // sampled (tllm_session_verify_sampled) under a configuration that is not plain arg-max: the sampler draws on all B * n rows
+    // (verify.draws) and the accept step compares the drafts with the draws; otherwise no launch is added and none differs.
+    int run_verify(int n, int max_past, const int32_t* limit, bool sampled, hipStream_t st);
     int verify_buffers(); // allocates `verify` on first use after a setup
     // ln_f of R hidden rows into tmp (fp16), and lm_head as a prefill GEMM on `rows` of them with fp32 output [rows, Vr]: the
     // head of scoring and of a verify pass (run_head's fused GEMV leaves at most B rows, in the session's logits)

@@ -318,6 +318,7 @@ int tllm_session::verify_buffers()
     RUN(dalloc(&vb.rec, rows * 8 * 4));
     RUN(dalloc(&vb.log_probs, rows * 4));
     RUN(dalloc(&vb.top1, rows * 4));
+    RUN(dalloc(&vb.draws, rows * 4));
     RUN(dalloc(&vb.accepted, (size_t) B * 4));
     RUN(dalloc(&vb.limit, (size_t) B * 4));
     RUN(dalloc(&vb.state, (size_t) B * 4 * 4));
@@ -329,7 +330,11 @@ int tllm_session::verify_buffers()
 // ids[b][0..i].  The rows are scored against the next id of their sequence (top1 = the arg-max the accept rule compares the
 // drafts with, log_probs for the caller) and the accept step commits the longest right prefix in the sampler's place
 // (kernels.h SpecAcceptParams).  sequence_length is read by every layer's attention and written by the accept step alone.
-int tllm_session::run_verify(int n, int max_past, const int32_t* limit, hipStream_t st)
+// A sampled pass (kernels.h SpecSampleParams) puts one launch between the scoring and the accept step: the
+// sampler on all R rows, each with the history and the token number plain sampled decoding would have had there, and the accept
+// step compares the drafts with those draws.  log_probs stay the raw model's.  Under a configuration that is plain arg-max (or
+// none) that launch is not made: the pass is the greedy one.
+int tllm_session::run_verify(int n, int max_past, const int32_t* limit, bool sampled, hipStream_t st)
 {
     const int R = B * n;
     RUN(verify_buffers());
@@ -350,12 +355,29 @@ int tllm_session::run_verify(int n, int max_past, const int32_t* limit, hipStrea
     RUN(launch_token_logprob_merge(verify.rec, 1, R, vocab, verify.targets, verify.log_probs, nullptr, verify.top1, st) ? 1 : 0);
     head_partials_live = false; // the session's logits are a copied row from here on, no head launch's partials belong to them
     logit_rows = B;
+    verify_cmp = verify.top1;
+    if (sampled && sampling_on && !sampling_is_greedy(sampling))
+    {
+        SpecSampleParams sp;
+        sp.s = sampling;
+        sp.s.g = greedy_params();
+        sp.s.g.logits = verify.logits;
+        sp.s.history = out_ids;
+        sp.s.history_stride = Smax;
+        sp.s.g_base = max_in;
+        sp.n = n;
+        sp.ids = ids_in;
+        sp.limit = limit;
+        sp.draws = verify.draws;
+        RUN(launch_spec_sample_rows(sp, st) ? 1 : 0);
+        verify_cmp = verify.draws;
+    }
     SpecAcceptParams a;
     a.g = greedy_params();
     a.g.logits = verify.logits;
     a.n = n;
     a.ids = ids_in;
-    a.top1 = verify.top1;
+    a.top1 = verify_cmp;
     a.limit = limit;
     a.accepted = verify.accepted;
     a.logits_out = logits_local;

@@ -26,6 +26,7 @@ void tllm_session::free_runtime()
     score = ScoreBuffers();
     verify = VerifyBuffers();
     verify_n = 0;
+    verify_cmp = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------ buffers

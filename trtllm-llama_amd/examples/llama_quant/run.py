@@ -46,6 +46,9 @@ def parse_arguments(args=None):
     p.add_argument('--prompt_lookup_tokens', type=int, default=0,
                    help='N in [2, 32]: draft from earlier n-gram matches of the text and verify N ids per pass; 0 = off.')
     p.add_argument('--prompt_lookup_ngram', type=int, default=3, help='longest n-gram the lookup matches, 1 to 8')
+    p.add_argument('--prompt_lookup_sampling', action='store_true',
+                   help='let --prompt_lookup_tokens combine with --top_k / --top_p / --temperature / --repetition_penalty / '
+                   '--random_seed: a draft is kept where it equals the token the sampler draws (the same tokens as without lookup).')
     return p.parse_args(args)
 
 
@@ -78,7 +81,8 @@ def load_session(engine_dir):
 
 def generate(max_output_len, log_level='error', engine_dir='llama_outputs', input_text=None, input_file=None,
              output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55, top_k=1, top_p=0.0,
-             temperature=1.0, repetition_penalty=1.0, random_seed=None, prompt_lookup_tokens=0, prompt_lookup_ngram=3):
+             temperature=1.0, repetition_penalty=1.0, random_seed=None, prompt_lookup_tokens=0, prompt_lookup_ngram=3,
+             prompt_lookup_sampling=False):
     tensorrt_llm.logger.set_level(log_level)
     decoder, runtime_rank = load_session(engine_dir)
     sampling_config = SamplingConfig(end_id=EOS_TOKEN, pad_id=PAD_TOKEN, num_beams=num_beams, top_k=top_k, top_p=top_p,
@@ -105,7 +109,8 @@ def generate(max_output_len, log_level='error', engine_dir='llama_outputs', inpu
             # the last verify pass writes prompt_lookup_tokens cache rows from the current length: that much room behind the output
             decoder.setup(ids.shape[0], int(input_lengths.max()), max_output_len + prompt_lookup_tokens)
             output_ids = decoder.decode_lookup(ids, input_lengths, sampling_config, num_draft_tokens=prompt_lookup_tokens,
-                                               max_ngram=prompt_lookup_ngram, max_new_tokens=max_output_len)
+                                               max_ngram=prompt_lookup_ngram, max_new_tokens=max_output_len,
+                                               speculative_sampling=prompt_lookup_sampling)
             output_ids = output_ids[:, :, :ids.shape[1] + max_output_len]
         else:
             decoder.setup(ids.shape[0], int(input_lengths.max()), max_output_len)

@@ -223,13 +223,24 @@ class GenerationSession(object):
             return torch.from_numpy(out).to(input_ids.device)
         return out
 
-    def verify(self, input_ids):
+    def verify(self, input_ids, sampling_config: Optional[SamplingConfig] = None):
         """Verify input_ids int32 [batch, n] (n <= 32) in one pass over the live cache (tllm_session_verify): token 0 takes the
         pending token's place, the others are drafts of what follows; the longest prefix greedy decoding would have produced is
         kept and the session continues behind it.  Returns a dict: accepted int32 [batch] (drafts kept; -1 for a finished
         sequence), log_probs f32 [batch, n] (log p of every id given what precedes it, 0 for token 0), logits f32 [batch, vocab]
-        (the row behind the last kept token).  Greedy sessions only."""
-        acc, lp = self.runtime.verify(self._append_ids(input_ids))
+        (the row behind the last kept token).  Without sampling_config: greedy sessions only.
+        With a sampling_config (num_beams 1) that is not plain arg-max the session samples under it from here on and the pass is
+        tllm_session_verify_sampled's: a draft is kept only where it equals the token the sampler draws there (the token decode()
+        would have produced for that configuration and seed); log_probs stay the raw model's."""
+        ids = self._append_ids(input_ids)
+        sampled = False
+        if sampling_config is not None:
+            self._check_sampling_config(sampling_config)
+            if sampling_config.num_beams != 1:
+                raise ValueError('verify() needs num_beams 1')
+            self.runtime.set_sampling(self._native_sampling(sampling_config))
+            sampled = not self._is_greedy(sampling_config)
+        acc, lp = self.runtime.verify(ids, sampled=True) if sampled else self.runtime.verify(ids)
         out = dict(accepted=acc, log_probs=lp, logits=self.runtime.logits())
         if hasattr(input_ids, 'cpu'):
             import torch
@@ -237,24 +248,33 @@ class GenerationSession(object):
         return out
 
     @staticmethod
-    def _check_lookup_args(scfg: SamplingConfig, num_draft_tokens: int, max_ngram: int):
+    def _is_greedy(scfg: SamplingConfig) -> bool:
+        """plain arg-max, as the device's sampling_is_greedy() decides it"""
+        return scfg.top_k == 1 and scfg.temperature == 1.0 and scfg.repetition_penalty == 1.0 and scfg.presence_penalty == 0.0 \
+            and scfg.min_length <= 1
+
+    @staticmethod
+    def _check_lookup_args(scfg: SamplingConfig, num_draft_tokens: int, max_ngram: int, speculative_sampling: bool = False):
         """What decode_lookup() refuses before anything reaches the device."""
         if scfg.num_beams != 1:
             raise ValueError('decode_lookup() needs num_beams 1')
-        if scfg.top_k != 1 or scfg.temperature != 1.0 or scfg.repetition_penalty != 1.0 or scfg.presence_penalty != 0.0 \
-                or scfg.min_length > 1:
+        if not speculative_sampling and not GenerationSession._is_greedy(scfg):
             raise NotImplementedError('decode_lookup() is greedy: the sampling configuration must be plain arg-max (top_k 1, '
                                       'temperature 1, no penalty, min_length <= 1) - speculative sampling is not built')
         if not 2 <= num_draft_tokens <= 32 or not 1 <= max_ngram <= 8:
             raise ValueError(f'num_draft_tokens {num_draft_tokens} must lie in [2, 32] and max_ngram {max_ngram} in [1, 8]')
 
     def decode_lookup(self, input_ids, input_lengths, sampling_config: SamplingConfig, num_draft_tokens: int = 8, max_ngram: int = 3,
-                      max_new_tokens: Optional[int] = None):
+                      max_new_tokens: Optional[int] = None, speculative_sampling: bool = False):
         """decode() with prompt-lookup speculation (tllm_session_generate_lookup): the same tokens, greedy; where the text repeats
         an n-gram of the prompt or of itself, up to num_draft_tokens - 1 following tokens are verified in one pass.  max_new_tokens
         None: setup()'s less num_draft_tokens, the room the last verify pass needs.  Returns what decode() returns; the counters of
-        the call are kept in self.lookup_stats (rounds, verify_rounds, step_rounds, drafted, accepted)."""
-        self._check_lookup_args(sampling_config, num_draft_tokens, max_ngram)
+        the call are kept in self.lookup_stats (rounds, verify_rounds, step_rounds, drafted, accepted).
+        speculative_sampling=True (tllm_session_generate_lookup_sampled) takes any single-beam sampling_config: a draft is kept
+        where it equals the token the sampler draws there, so the tokens are decode()'s for that configuration and random_seed."""
+        self._check_lookup_args(sampling_config, num_draft_tokens, max_ngram, speculative_sampling)
+        if speculative_sampling:
+            self._check_sampling_config(sampling_config)
         if getattr(self, 'beam_width', 1) != 1:
             raise ValueError(f'decode_lookup() needs beam_width 1 (the session is set up with {self.beam_width})')
         is_torch = hasattr(input_ids, 'cpu')
@@ -268,7 +288,8 @@ class GenerationSession(object):
         self.runtime.set_sampling(self._native_sampling(sampling_config))
         out, self.lookup_stats = self.runtime.generate_lookup(ids.astype(np.int32), lens.astype(np.int32), new,
                                                               end_id=sampling_config.end_id, pad_id=sampling_config.pad_id,
-                                                              num_draft_tokens=num_draft_tokens, max_ngram=max_ngram)
+                                                              num_draft_tokens=num_draft_tokens, max_ngram=max_ngram,
+                                                              **(dict(sampled=True) if speculative_sampling else {}))
         out = out.reshape(self.batch_size, 1, -1)
         if is_torch:
             import torch

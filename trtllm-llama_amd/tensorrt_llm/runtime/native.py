@@ -117,6 +117,18 @@ def _lib():
     lib.tllm_prompt_lookup.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p,
                                        c.c_int32, c.c_int32, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.tllm_prompt_lookup.restype = c.c_int32
+    lib.tllm_session_verify_sampled.argtypes = lib.tllm_session_verify.argtypes
+    lib.tllm_session_verify_sampled.restype = c.c_int32
+    lib.tllm_session_verify_draws.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
+    lib.tllm_session_verify_draws.restype = c.c_int32
+    lib.tllm_session_verify_logits.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
+    lib.tllm_session_verify_logits.restype = c.c_int32
+    lib.tllm_session_generate_lookup_sampled.argtypes = lib.tllm_session_generate_lookup.argtypes
+    lib.tllm_session_generate_lookup_sampled.restype = c.c_int32
+    lib.tllm_spec_sample_rows.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_int32,
+                                          c.POINTER(SamplingConfigC), c.c_int32, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p,
+                                          c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
+    lib.tllm_spec_sample_rows.restype = c.c_int32
     _bound = True
     return lib
 
@@ -274,6 +286,32 @@ def sample_tokens(logits, g, out_ids, *, vocab=None, end_id=-1, history=None, in
     _check(_lib().tllm_sample_tokens(logits.data_ptr(), nparts, rows, vpart, vocab or nparts * vpart, ctypes.byref(cfg), end_id,
                                      ptr(history), stride, ptr(input_lengths), max_input_len, g.data_ptr(), out_ids.data_ptr(),
                                      ptr(u_out), stream), 'sample_tokens')
+
+
+def spec_sample_rows(logits, ids, seq_len, draws, *, max_input_len: int, vocab=None, end_id=-1, out_ids=None, input_lengths=None,
+                     finished=None, limit=None, u_out=None, nparts: int = 1, stream: int = 0, **config):
+    """tllm_spec_sample_rows on torch cuda tensors (the rule: csrc/kernels/kernels.h SpecSampleParams, spec_ref.sample_rows): the
+    sampler on all n rows per sequence of a verify pass.  logits f32 [batch * n, vocab_part] (never written), ids int32
+    [batch, n], seq_len / input_lengths / finished / limit int32 [batch], out_ids int32 [batch, Smax] the token record (needed
+    with a penalty), draws int32 [batch, n], u_out optional f32 [batch, n].  **config: the fields of tllm_sampling_config_t.
+    Asynchronous on `stream`."""
+    import torch
+    B, n = ids.shape
+    assert logits.is_cuda and logits.is_contiguous() and logits.dtype == torch.float32 and logits.dim() == 2
+    assert logits.shape[0] == B * n
+    for t, k in ((ids, B * n), (draws, B * n), (seq_len, B), (input_lengths, B), (finished, B), (limit, B)):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() >= k)
+    assert u_out is None or (u_out.is_cuda and u_out.is_contiguous() and u_out.dtype == torch.float32 and u_out.numel() >= B * n)
+    stride = 0
+    if out_ids is not None:
+        assert out_ids.is_cuda and out_ids.is_contiguous() and out_ids.dtype == torch.int32 and out_ids.shape[0] == B
+        stride = out_ids.shape[1]
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    cfg = _sampling_config(**config)
+    vpart = logits.shape[1]
+    _check(_lib().tllm_spec_sample_rows(logits.data_ptr(), nparts, B, n, vpart, vocab or vpart, ctypes.byref(cfg), end_id,
+                                        ids.data_ptr(), ptr(out_ids), stride, seq_len.data_ptr(), ptr(input_lengths), max_input_len,
+                                        ptr(finished), ptr(limit), draws.data_ptr(), ptr(u_out), stream), 'spec_sample_rows')
 
 
 def token_logprobs(logits, targets, *, vocab=None, partials=None, stream: int = 0):
@@ -508,18 +546,39 @@ class NativeSession:
     attention_append = staticmethod(attention_append)
     spec_accept = staticmethod(spec_accept)
     prompt_lookup = staticmethod(prompt_lookup)
+    spec_sample_rows = staticmethod(spec_sample_rows)
 
-    def verify(self, ids, stream: int = 0):
+    def verify(self, ids, sampled: bool = False, stream: int = 0):
         """Verify ids [batch, n] in one append pass (tllm_session_verify): ids[:, 0] takes the pending token's place, ids[:, 1:] are
         drafts; the longest prefix greedy decoding would have produced is kept.  Returns (accepted int32 [batch]: drafts kept, -1 for
         a finished sequence; log_probs f32 [batch, n]: log p(ids[b][i] | everything before it), 0 at i = 0).  logits() then holds
-        the row behind the last kept token and the arg-max of that row is the new pending token."""
+        the row behind the last kept token and the arg-max of that row is the new pending token.
+        sampled=True (tllm_session_verify_sampled): under the configuration of set_sampling() a draft is kept only where it equals
+        the token the sampler draws there, the draw behind the last kept draft is the new pending token; log_probs stay the raw
+        model's.  With a greedy configuration the two are the same call."""
         ids = self._i32(ids)
         assert ids.ndim == 2 and (not self.batch or ids.shape[0] == self.batch), 'ids must be [batch, n]'
         acc = np.empty(ids.shape[0], np.int32)
         lp = np.empty(ids.shape, np.float32)
-        _check(_lib().tllm_session_verify(self._h, ids.ctypes.data, ids.shape[1], acc.ctypes.data, lp.ctypes.data, stream), 'verify')
+        fn = _lib().tllm_session_verify_sampled if sampled else _lib().tllm_session_verify
+        _check(fn(self._h, ids.ctypes.data, ids.shape[1], acc.ctypes.data, lp.ctypes.data, stream),
+               'verify_sampled' if sampled else 'verify')
         return acc, lp
+
+    def verify_draws(self, n: int, stream: int = 0) -> np.ndarray:
+        """the ids [batch, n] the last verify() of n ids compared the drafts with: the sampler's draws after a sampled pass, the
+        arg-maxes after a greedy one (tests)"""
+        d = np.empty((self.batch, n), np.int32)
+        _check(_lib().tllm_session_verify_draws(self._h, d.ctypes.data, n, stream), 'verify_draws')
+        return d
+
+    def verify_logits(self, n: int, vocab: Optional[int] = None, stream: int = 0) -> np.ndarray:
+        """the fp32 logits rows [batch, n, vocab] of the last verify() of n ids (tests)"""
+        v = _lib().tllm_session_vocab_size(self._h)
+        assert vocab is None or vocab == v
+        out = np.empty((self.batch, n, v), np.float32)
+        _check(_lib().tllm_session_verify_logits(self._h, out.ctypes.data, n, stream), 'verify_logits')
+        return out
 
     def verify_top1(self, n: int, stream: int = 0) -> np.ndarray:
         """the arg-max ids [batch, n] of the logits rows of the last verify() of n ids (tests)"""
@@ -528,15 +587,17 @@ class NativeSession:
         return top
 
     def generate_lookup(self, input_ids, input_lengths, max_new_tokens: int, end_id: int = -1, pad_id: int = 0,
-                        num_draft_tokens: int = 8, max_ngram: int = 3, stream: int = 0):
+                        num_draft_tokens: int = 8, max_ngram: int = 3, sampled: bool = False, stream: int = 0):
         """generate() with prompt-lookup drafts verified num_draft_tokens ids at a time (tllm_session_generate_lookup): the same
         tokens.  max_new_tokens + num_draft_tokens <= setup's max_new_tokens.  Returns (output_ids [batch, max_seq_len], stats:
-        dict(rounds, verify_rounds, step_rounds, drafted, accepted))."""
+        dict(rounds, verify_rounds, step_rounds, drafted, accepted)).  sampled=True (tllm_session_generate_lookup_sampled): under
+        the configuration of set_sampling(), the tokens generate() yields for that configuration and seed."""
         ids, lens = self._i32(input_ids), self._i32(input_lengths)
         out = np.empty((self.batch, self.max_in + self.max_new), np.int32)
         cfg, st = LookupConfigC(int(num_draft_tokens), int(max_ngram)), LookupStatsC()
-        _check(_lib().tllm_session_generate_lookup(self._h, ids.ctypes.data, lens.ctypes.data, max_new_tokens, end_id, pad_id,
-                                                   ctypes.byref(cfg), out.ctypes.data, ctypes.byref(st), stream), 'generate_lookup')
+        fn = _lib().tllm_session_generate_lookup_sampled if sampled else _lib().tllm_session_generate_lookup
+        _check(fn(self._h, ids.ctypes.data, lens.ctypes.data, max_new_tokens, end_id, pad_id, ctypes.byref(cfg), out.ctypes.data,
+                  ctypes.byref(st), stream), 'generate_lookup_sampled' if sampled else 'generate_lookup')
         return out, {k: int(getattr(st, k)) for k, _ in LookupStatsC._fields_}
 
     def attention_tap(self, layer: int, heads_x_dh: int, quantised: bool, stream: int = 0) -> np.ndarray:

@@ -13,8 +13,15 @@ The tokens are those of plain greedy decoding whatever the drafts were: a draft 
 prompt_lookup: drafts from the sequence's own record.  The logical sequence is out_ids[0 .. input_lengths) followed by
 out_ids[max_input_len .. seq_len]; its last element is the pending token.  For g = max_ngram down to 1 the last g tokens are the
 suffix; the most recent start s with s + g < len whose g tokens equal it wins, at the first (largest) g that has one.  The draft is
-the up to n - 1 tokens behind the match that exist; the row is [pending, draft..., pending...]."""
+the up to n - 1 tokens behind the match that exist; the row is [pending, draft..., pending...].
+
+sample_rows (speculative sampling by exact match; kernels.h SpecSampleParams): the sampler on all n rows of
+a verify pass.  Row i of sequence b is drawn as sampling_ref.draw draws generated token number g = p + i + 2 - max_input_len (the
+token of slot p + i + 1), with the history prompt + record[max_input_len .. p) + t[0..i].  accept() fed with these draws in the
+arg-maxes' place is the accept rule of a sampled pass: a draft survives only where it equals the draw."""
 import numpy as np
+
+from . import sampling_ref
 
 INT32_MAX = 0x7FFFFFFF
 
@@ -65,6 +72,26 @@ def accept(seq_len, finished, ids, top1, end_id=-1, limit=None, out_ids=None, cu
     if pos is not None:
         r['rope_pos'] = pos
     return r
+
+
+def sample_rows(logits_rows, cfg, b, p, ids_row, record_row, input_length, max_input_len, end_id=-1, finished=0, limit=None):
+    """logits_rows f32 [n, vocab]: the verify rows of sequence b; cfg a sampling_ref.Config; p = seq_len[b]; ids_row int [n] = t;
+    record_row int [Smax] the sequence's token record (prompt slots [0, max_input_len), committed tokens behind).  Returns the
+    sampling_ref.Draw of every row, a list of n; None for every row of a frozen sequence (finished, or p >= limit), where the
+    device writes end_id without drawing."""
+    logits_rows = np.asarray(logits_rows)
+    n = logits_rows.shape[0]
+    if finished or (limit is not None and p >= limit):
+        return [None] * n
+    t = np.asarray(ids_row, np.int64)
+    rec = np.array(record_row, np.int64)
+    out = []
+    for i in range(n):
+        g = p + i + 2 - max_input_len
+        # t[0..i] in the places of slots p .. p + i: from the ids, not from the record (t[0] stands in the pending token's place)
+        hist = np.concatenate([rec[:p], t[:i + 1]])
+        out.append(sampling_ref.draw(logits_rows[i], cfg, b, g, end_id, sampling_ref.history_ids(hist, input_length, max_input_len, g)))
+    return out
 
 
 def logical_sequence(row, input_length, max_input_len, seq_len):
