@@ -181,7 +181,7 @@ int32_t tllm_session_force_tokens(tllm_session_t s, const int32_t* ids, tllm_str
  * Reads sequence_length back, so it synchronises the stream.  Refused, with nothing enqueued: before setup; before any context
  * (every sequence_length must be >= max_input_len); n < 1, n > max_input_len (the activation buffers are sized for that) or
  * sequence_length[b] + n > max_seq_len; beam_width > 1, the paged cache, tensor parallel > 1; a token id outside [0, vocab_size).
- * Packed-input sessions are accepted (the appended rows are dense either way).  Not built: a different n per sequence.  The
+ * Packed-input sessions are accepted (the appended rows are dense either way).  A different n per sequence: tllm_session_append_ragged.  The
  * scoring of the appended tokens is tllm_session_verify's. */
 int32_t tllm_session_append(tllm_session_t s, const int32_t* ids, int32_t n, tllm_stream_t stream);
 /* tllm_session_append, then up to max_new_tokens generated tokens as tllm_session_generate produces them (the first by the
@@ -193,8 +193,26 @@ int32_t tllm_session_append(tllm_session_t s, const int32_t* ids, int32_t n, tll
  * repeat the request, because the append has consumed the state it started from. */
 int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32_t n, int32_t max_new_tokens, int32_t end_id,
     int32_t pad_id, int32_t* output_ids, tllm_stream_t stream);
-/* Attention launches tllm_session_append has enqueued since setup, by kernel (one per layer and call): *wave, *mfma (either may
- * be NULL).  For tests: which kernel served a chunk. */
+/* tllm_session_append with a different number of tokens per sequence, in the padded layout
+ *   ids      HOST int32 [B, W];   lengths  HOST int32 [B], 1 <= lengths[b] <= W <= max_input_len.
+ * For sequence b the call is tllm_session_append with n = n_b = lengths[b]: placement, RoPE position, visibility, numerics and the
+ * store rule are that entry's with n_b in place of n.  Only ids[b][0 .. n_b) are read - what stands behind them in a row is never
+ * looked at, range-checked or copied into the token record.  The cache is written in slots [p_b, p_b + n_b) alone, the token
+ * record in [p_b, p_b + n_b] (its last slot by the sampler), sequence_length[b] += n_b, finished[b] = 0, and the session's logits
+ * row b belongs to appended token n_b - 1.  The pass runs on B * N rows, N = max_b n_b (not W), and N chooses the attention kernel;
+ * rows i >= n_b are padding that nothing outliving the call depends on.  With every n_b = W the call is tllm_session_append bit
+ * for bit.  Refused, with nothing enqueued: everything tllm_session_append refuses, with the capacity check per sequence
+ * (sequence_length[b] + n_b > max_seq_len); lengths NULL; an n_b < 1 or > W; an id outside [0, vocab_size) among the first n_b of a
+ * row.  Not built: a sequence that sits the call out (n_b = 0); a packed row layout (sum of n_b rows). */
+int32_t tllm_session_append_ragged(tllm_session_t s, const int32_t* ids, const int32_t* lengths, int32_t W, tllm_stream_t stream);
+/* tllm_session_append_ragged, then tllm_session_append_generate from there: every sequence gets the same number of generation
+ * steps, sequence_length[b] + n_b + max_new_tokens <= max_seq_len per sequence, and the tail fill of output_ids starts behind
+ * sequence_length[b] + n_b + (tokens produced).  The failure contract for an expired in-launch wait is
+ * tllm_session_append_generate's. */
+int32_t tllm_session_append_ragged_generate(tllm_session_t s, const int32_t* ids, const int32_t* lengths, int32_t W,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, int32_t* output_ids, tllm_stream_t stream);
+/* Attention launches tllm_session_append and tllm_session_append_ragged have enqueued since setup, by kernel (one per layer and
+ * call): *wave, *mfma (either may be NULL).  For tests: which kernel served a chunk. */
 int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* mfma);
 
 /* Speculative greedy decoding (the rules are stated in csrc/kernels/kernels.h, SpecAcceptParams and
@@ -677,6 +695,14 @@ typedef struct
     void* out;
 } tllm_attention_append_params_t;
 int32_t tllm_attention_append(const tllm_attention_append_params_t* p, tllm_stream_t stream);
+/* tllm_attention_append with a different number of tokens per sequence: sequence b appends n_b = n_per_seq[b] tokens (DEVICE int32
+ * [batch]; clamped into [0, p->n] on the device), and everything above holds with n_b in place of n.  p->n stays the row stride
+ * of qkv and out, the upper bound of every n_b and what chooses the kernel; p->max_past is ignored - max_end is the caller's
+ * promise max_end >= every sequence_length[b] + n_b, and max_end > max_seq_len (or < 1) is refused with nothing launched.  Rows
+ * i >= n_b of a sequence are padding: their qkv bits stay as they are (no RoPE), nothing of them is stored to the cache or read
+ * as a query, key or value - NaN there reaches nothing - and their rows of out are written as zeros. */
+int32_t tllm_attention_append_ragged(const tllm_attention_append_params_t* p, const int32_t* n_per_seq, int32_t max_end,
+    tllm_stream_t stream);
 /* the attention kernel tllm_attention_append would run for p (n, head_size and append_kernel are read; no pointer is followed; no
  * GPU needed): TLLM_APPEND_ATTN_WAVE or _MFMA in *kind.  Non-zero: a forced append_kernel the launch cannot run. */
 int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* p, int32_t* kind);

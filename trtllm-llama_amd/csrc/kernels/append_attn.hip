@@ -9,6 +9,10 @@
 //                               blocks - first the past blocks from the cache, then the chunk's blocks from the QKV buffer;
 //   (c) append_attn_wave_kernel one wave per query: every n, head sizes 32 / 64 / 128 / 256;
 //   (d) append_advance_kernel   sequence_length[b] += n, finished[b] = 0 (the session's bookkeeping, a launch of its own).
+// A different number of tokens per sequence (n_per_seq, device [B]; null = n for all): sequence b appends n_b = n_per_seq[b]
+// clamped into [0, n], n stays the row stride of the QKV buffer and of `out`, and the rule above holds with n_b in place of n.  Rows
+// i >= n_b are padding: (a) leaves them alone (no RoPE, no cache store - their bits in the QKV buffer stay), (b) and (c) write
+// their `out` rows as zeros and never load them - not as a query, not as a key, not as a value - and (d) adds n_b.
 // Numerics, both attention kernels: past slots are read as the decode kernel reads them - a one-byte element becomes the exact
 // fp16 value of its byte, kv_scale_quant_orig is applied once to the score and once to the sum of p.v; the appended tokens' own
 // k and v enter un-quantised from the QKV buffer (as the prefill does for the prompt and decode for the current token).  Scores,
@@ -72,6 +76,8 @@ __global__ __launch_bounds__(256) void append_rope_kv_kernel(const AppendAttnPar
     constexpr int LPR = DH / 8, HG = 256 / LPR;
     const int i = blockIdx.x, h = blockIdx.y * HG + threadIdx.x / LPR, b = blockIdx.z;
     if (h >= p.num_heads) // whole lane groups (the shuffles stay inside a group)
+        return;
+    if (p.n_per_seq && i >= clampi(p.n_per_seq[b], 0, p.n)) // a padding row (uniform over the workgroup)
         return;
     const int li = threadIdx.x % LPR;
     const int H = p.num_heads, Hkv = p.num_kv_heads, Smax = p.max_seq_len;
@@ -177,6 +183,12 @@ __global__ __launch_bounds__(256) void append_attn_wave_kernel(const AppendAttnP
         return;
     const int li = lane % LPR, grp = lane / LPR;
     const int H = p.num_heads, Hkv = p.num_kv_heads, Smax = p.max_seq_len;
+    if (p.n_per_seq && qi >= clampi(p.n_per_seq[b], 0, p.n)) // a padding row (uniform over the wave): zeros, no key is read
+    {
+        if (grp == 0)
+            *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p.out) + (((int64_t) b * p.n + qi) * H + h) * DH + li * 8) = make_uint4(0, 0, 0, 0);
+        return;
+    }
     const int kvh = h / (H / Hkv);
     const int pb = clampi(p.sequence_length[b], 0, Smax);
     const int64_t rs = (int64_t) (H + 2 * Hkv) * DH;
@@ -328,6 +340,17 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
     const int u = wv >> 1; // key half: keys 32 u .. 32 u + 31 of every 64-key block
     const int h = blockIdx.x, qb = blockIdx.y, b = blockIdx.z;
     const int H = p.num_heads, Hkv = p.num_kv_heads, Smax = p.max_seq_len, n = p.n;
+    const int nb = p.n_per_seq ? clampi(p.n_per_seq[b], 0, n) : n; // this sequence's tokens; rows nb .. n - 1 are padding
+    if (qb * 64 >= nb) // a query block of padding alone (uniform over the workgroup, before the first barrier): zeros
+    {
+        for (int x = tid; x < 64 * LPR; x += 256)
+        {
+            const int row = qb * 64 + x / LPR;
+            if (row < n)
+                *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(p.out) + (((int64_t) b * n + row) * H + h) * DH + (x % LPR) * 8) = make_uint4(0, 0, 0, 0);
+        }
+        return;
+    }
     const int kvh = h / (H / Hkv);
     const int pb = clampi(p.sequence_length[b], 0, Smax);
     const int64_t rs = (int64_t) (H + 2 * Hkv) * DH;
@@ -338,10 +361,10 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
     const char* vc = reinterpret_cast<const char*>(p.kv_cache) + ((((int64_t) b * 2 + 1) * Hkv + kvh) * Smax) * DH * ESZ;
     const int32_t* mask = p.masked_tokens ? p.masked_tokens + (int64_t) b * Smax : nullptr;
     const float s_qo = KV != 0 ? p.kv_scale_quant_orig[0] : 1.f;
-    const int qi = qb * 64 + w * 32 + r; // this lane's query (index into the chunk); rows >= n compute on row n - 1 and are not stored
+    const int qi = qb * 64 + w * 32 + r; // this lane's query (index into the chunk); rows >= nb compute on row nb - 1: stored as zeros below n, not at all from n on
     f16x8_t qf[KT];
     {
-        const uint16_t* qrow = base + (int64_t) min(qi, n - 1) * rs + (int64_t) h * DH + 8 * hh;
+        const uint16_t* qrow = base + (int64_t) min(qi, nb - 1) * rs + (int64_t) h * DH + 8 * hh;
 #pragma unroll
         for (int t = 0; t < KT; ++t)
             qf[t] = *reinterpret_cast<const f16x8_t*>(qrow + 16 * t);
@@ -376,14 +399,14 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
                 if (past)
                     kr[ps] = load_kv8<KV>(kc + ((int64_t) min(key, Smax - 1) * DH + c * 8) * ESZ);
                 else
-                    kr[ps] = *reinterpret_cast<const uint4*>(kb + (int64_t) min(key, n - 1) * rs + c * 8);
+                    kr[ps] = *reinterpret_cast<const uint4*>(kb + (int64_t) min(key, nb - 1) * rs + c * 8);
             }
 #pragma unroll
             for (int ps = 0; ps < KPASS; ++ps)
                 *reinterpret_cast<uint4*>(sK + (ps * KPP + tid / LPR) * KP + c * 16) = kr[ps];
             // V rows, transposed: lane = key, so a wave writes 64 consecutive halfs of a V^T row per element
             const int kl = tid & 63, key = k0 + kl;
-            const bool ok = past ? (key < pb && (!mask || mask[key] == 0)) : key < n;
+            const bool ok = past ? (key < pb && (!mask || mask[key] == 0)) : key < nb;
             if (tid < 64)
                 sOk[kl] = ok ? 1 : 0;
             const int col = (kl & ~12) | ((kl & 4) << 1) | ((kl & 8) >> 1);
@@ -425,7 +448,7 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
         for (int i = 0; i < 16; ++i)
         {
             const int kl = 32 * u + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            const bool ok = past ? sOk[kl] != 0 : k0 + kl <= qi; // (chunk: qi < n for every stored row, so k0 + kl < n too)
+            const bool ok = past ? sOk[kl] != 0 : k0 + kl <= qi; // (chunk: qi < nb for every row stored as computed, so k0 + kl < nb too)
             sacc[i] = ok ? sacc[i] * kscale : -INFINITY;
             mt = fmaxf(mt, sacc[i]);
         }
@@ -491,7 +514,15 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
     }
     if (qi < n)
     {
-        const float inv = 1.f / (l + 1.e-6f);
+        const float inv = qi < nb ? 1.f / (l + 1.e-6f) : 0.f;
+        if (qi >= nb) // a padding row of a partly filled block: zeros, whatever the clamped loads gave
+        {
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    oacc[dt][i] = 0.f;
+        }
         uint16_t* orow = reinterpret_cast<uint16_t*>(p.out) + (((int64_t) b * n + qi) * H + h) * DH + 4 * hh;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
@@ -503,11 +534,12 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
 }
 
 // ---- (d) one workgroup
-__global__ __launch_bounds__(256) void append_advance_kernel(int32_t* sequence_length, int32_t* finished, int32_t batch, int32_t n)
+__global__ __launch_bounds__(256) void append_advance_kernel(int32_t* sequence_length, int32_t* finished, const int32_t* n_per_seq,
+    int32_t batch, int32_t n)
 {
     for (int b = threadIdx.x; b < batch; b += 256)
     {
-        sequence_length[b] += n;
+        sequence_length[b] += n_per_seq ? clampi(n_per_seq[b], 0, n) : n;
         if (finished)
             finished[b] = 0;
     }
@@ -611,7 +643,15 @@ int launch_append_attention(const AppendAttnParams& pin, hipStream_t stream)
         set_error("append attention: qkv, kv_cache and out must be 16-byte aligned");
         return -1;
     }
-    if (p.max_past < 0 || (int64_t) p.max_past + p.n > p.max_seq_len)
+    if (p.n_per_seq)
+    {
+        if (p.max_end < 1 || p.max_end > p.max_seq_len)
+        {
+            set_error("append attention: max_end %d outside [1, the cache capacity %d]", p.max_end, p.max_seq_len);
+            return -1;
+        }
+    }
+    else if (p.max_past < 0 || (int64_t) p.max_past + p.n > p.max_seq_len)
     {
         set_error("append attention: max_past %d + n %d exceeds the cache capacity %d", p.max_past, p.n, p.max_seq_len);
         return -1;
@@ -642,7 +682,19 @@ int launch_append_advance(int32_t* sequence_length, int32_t* finished, int32_t b
         set_error("append advance: bad arguments");
         return -1;
     }
-    hipLaunchKernelGGL(append_advance_kernel, dim3(1), dim3(256), 0, stream, sequence_length, finished, batch, n);
+    hipLaunchKernelGGL(append_advance_kernel, dim3(1), dim3(256), 0, stream, sequence_length, finished, (const int32_t*) nullptr, batch, n);
+    return launch_util::check_launch("append advance");
+}
+
+int launch_append_advance_ragged(int32_t* sequence_length, int32_t* finished, const int32_t* n_per_seq, int32_t batch, int32_t n,
+    hipStream_t stream)
+{
+    if (!sequence_length || !n_per_seq || batch < 1 || n < 1)
+    {
+        set_error("append advance: bad arguments");
+        return -1;
+    }
+    hipLaunchKernelGGL(append_advance_kernel, dim3(1), dim3(256), 0, stream, sequence_length, finished, n_per_seq, batch, n);
     return launch_util::check_launch("append advance");
 }
 

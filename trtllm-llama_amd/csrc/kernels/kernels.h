@@ -414,7 +414,14 @@ enum AppendAttnKernel
 };
 struct AppendAttnParams
 {
-    int32_t batch = 0, n = 0; // n: tokens appended per sequence, the same for all
+    // n: tokens appended per sequence; with n_per_seq their upper bound - and the row stride of qkv and out either way
+    int32_t batch = 0, n = 0;
+    // [B] device or null (= n for every sequence): sequence b appends n_per_seq[b] tokens, clamped into [0, n] on the device; rows
+    // behind them are padding - no RoPE, no cache store, never read, `out` rows zero
+    const int32_t* n_per_seq = nullptr;
+    // with n_per_seq, in place of max_past: >= every sequence_length[b] + n_per_seq[b], promised by the caller; max_end >
+    // max_seq_len is refused with nothing enqueued (max_past + n would refuse a long past with a short turn beside a long turn)
+    int32_t max_end = 0;
     int32_t num_heads = 0, num_kv_heads = 0, head_size = 0; // num_kv_heads as MmhaParams (0 = num_heads)
     int32_t rotary_dim = 0, neox = 1;
     float inv_sqrt_dh = 1.f;
@@ -441,6 +448,9 @@ int append_attention_kernel(int32_t head_size, int32_t n, int32_t forced_kernel,
 int launch_append_attention(const AppendAttnParams& p, hipStream_t stream);
 // sequence_length[b] += n; finished[b] = 0 (finished may be null): one workgroup, a launch of its own
 int launch_append_advance(int32_t* sequence_length, int32_t* finished, int32_t batch, int32_t n, hipStream_t stream);
+// sequence_length[b] += n_per_seq[b] clamped into [0, n] (n_per_seq [B] device)
+int launch_append_advance_ragged(int32_t* sequence_length, int32_t* finished, const int32_t* n_per_seq, int32_t batch, int32_t n,
+    hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // MFMA GEMMs for M > 8 (prefill): C[m,n] = sum_k A[m,k] * B[n,k].

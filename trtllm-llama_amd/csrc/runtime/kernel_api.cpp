@@ -269,21 +269,25 @@ int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* q, in
     return 0;
 }
 
-int32_t tllm_attention_append(const tllm_attention_append_params_t* q, tllm_stream_t stream)
+// n_per_seq null: tllm_attention_append (q->max_past holds); else tllm_attention_append_ragged (max_end in its place)
+static int32_t attention_append(const char* who, const tllm_attention_append_params_t* q, const int32_t* n_per_seq, int32_t max_end,
+    tllm_stream_t stream)
 {
     if (!q || q->batch < 1 || q->n < 1 || q->num_heads < 1 || q->head_size < 1 || q->max_seq_len < 1)
     {
-        set_error("tllm_attention_append: bad arguments (batch, n, num_heads, head_size, max_seq_len)");
+        set_error("%s: bad arguments (batch, n, num_heads, head_size, max_seq_len)", who);
         return 1;
     }
     if (q->kv_cache_type != 0 && q->kv_cache_type != TLLM_HALF && q->kv_cache_type != TLLM_INT8 && q->kv_cache_type != TLLM_FP8)
     {
-        set_error("tllm_attention_append: kv_cache_type %d is not TLLM_HALF, TLLM_INT8 or TLLM_FP8", q->kv_cache_type);
+        set_error("%s: kv_cache_type %d is not TLLM_HALF, TLLM_INT8 or TLLM_FP8", who, q->kv_cache_type);
         return 1;
     }
     AppendAttnParams p;
     p.batch = q->batch;
     p.n = q->n;
+    p.n_per_seq = n_per_seq;
+    p.max_end = max_end;
     p.num_heads = q->num_heads;
     p.num_kv_heads = q->num_kv_heads;
     p.head_size = q->head_size;
@@ -310,6 +314,22 @@ int32_t tllm_attention_append(const tllm_attention_append_params_t* q, tllm_stre
             return 1;
     }
     return launch_append_attention(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_attention_append(const tllm_attention_append_params_t* q, tllm_stream_t stream)
+{
+    return attention_append("tllm_attention_append", q, nullptr, 0, stream);
+}
+
+int32_t tllm_attention_append_ragged(const tllm_attention_append_params_t* q, const int32_t* n_per_seq, int32_t max_end,
+    tllm_stream_t stream)
+{
+    if (!n_per_seq)
+    {
+        set_error("tllm_attention_append_ragged: n_per_seq is null");
+        return 1;
+    }
+    return attention_append("tllm_attention_append_ragged", q, n_per_seq, max_end, stream);
 }
 
 static GemvParams gemv_params(const tllm_gemv_params_t* q)

@@ -354,9 +354,10 @@ static int32_t append_session_ok(tllm_session_t s, const char* who)
 }
 
 // The checks of tllm_session_append; they enqueue nothing but the read of sequence_length.  past[b] = sequence_length[b] before
-// the call, *max_past_out their maximum.
-static int32_t append_checks(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, int32_t reserve_new,
-    std::vector<int32_t>& past, int* max_past_out, tllm_stream_t stream)
+// the call, *max_past_out their maximum.  lengths (host [B], or null = n for every sequence): sequence b appends lengths[b] of the
+// n ids of its row - what stands behind them is not looked at; *max_end_out (may be null) = max_b (past[b] + its tokens).
+static int32_t append_checks(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, const int32_t* lengths,
+    int32_t reserve_new, std::vector<int32_t>& past, int* max_past_out, int* max_end_out, tllm_stream_t stream)
 {
     RUN(append_session_ok(s, who));
     if (!ids)
@@ -375,46 +376,83 @@ static int32_t append_checks(tllm_session_t s, const char* who, const int32_t* i
         return 1;
     }
     const int B = s->B, Smax = s->Smax;
-    for (size_t k = 0; k < (size_t) B * n; ++k)
-        if (ids[k] < 0 || ids[k] >= s->vocab)
+    if (lengths)
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 1 || lengths[b] > n)
+            {
+                set_error("%s: lengths[%d] = %d out of range [1, %d] (a sequence that sits the call out is not built)", who, b,
+                    lengths[b], n);
+                return 1;
+            }
+    for (int b = 0; b < B; ++b)
+        for (int i = 0, nb = lengths ? lengths[b] : n; i < nb; ++i)
         {
-            set_error("%s: token id %d (sequence %d, token %d) outside [0, %d)", who, ids[k], (int) (k / n), (int) (k % n), s->vocab);
-            return 1;
+            const int32_t id = ids[(size_t) b * n + i];
+            if (id < 0 || id >= s->vocab)
+            {
+                set_error("%s: token id %d (sequence %d, token %d) outside [0, %d)", who, id, b, i, s->vocab);
+                return 1;
+            }
         }
     hipStream_t st = s->pick(stream);
     past.assign(B, 0);
     HIP_OK(hipMemcpyAsync(past.data(), s->seq_len, (size_t) B * 4, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     RUN(s->check_comm());
-    int max_past = 0;
+    int max_past = 0, max_end = 0;
     for (int b = 0; b < B; ++b)
     {
+        const int nb = lengths ? lengths[b] : n;
         if (past[b] < s->max_in)
         {
             set_error("%s: sequence_length[%d] = %d is below max_input_len %d - no context has run", who, b, past[b], s->max_in);
             return 1;
         }
-        if ((int64_t) past[b] + n + reserve_new > Smax)
+        if ((int64_t) past[b] + nb + reserve_new > Smax)
         {
-            set_error("%s: sequence %d: %d slots in use + %d appended + %d new exceed the cache capacity %d", who, b, past[b], n,
+            set_error("%s: sequence %d: %d slots in use + %d appended + %d new exceed the cache capacity %d", who, b, past[b], nb,
                 reserve_new, Smax);
             return 1;
         }
         max_past = std::max(max_past, past[b]);
+        max_end = std::max(max_end, past[b] + nb);
     }
     *max_past_out = max_past;
+    if (max_end_out)
+        *max_end_out = max_end;
     return 0;
 }
 
 // append_checks (nothing is enqueued before every one has passed), then: the ids to the device and into the token record, the
-// append pass, the advance launch, the sampler.
-static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, int32_t reserve_new,
-    std::vector<int32_t>& past, tllm_stream_t stream)
+// append pass, the advance launch, the sampler.  With lengths (host [B]; ids [B, n] padded) the pass runs on B * N rows, N their
+// maximum: the ids are compacted to [B, N] on the host, the padded positions filled with the row's own last id (a valid row for the
+// embedding; nothing that outlives the call depends on those rows), and the lengths go to append_last once - the attention's
+// n_per_seq, the head's gather and the advance launch all read them there.
+static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, const int32_t* lengths,
+    int32_t reserve_new, std::vector<int32_t>& past, tllm_stream_t stream)
 {
-    int max_past = 0;
-    RUN(append_checks(s, who, ids, n, reserve_new, past, &max_past, stream));
+    int max_past = 0, max_end = 0;
+    RUN(append_checks(s, who, ids, n, lengths, reserve_new, past, &max_past, &max_end, stream));
     hipStream_t st = s->pick(stream);
     const int B = s->B, Smax = s->Smax;
+    if (lengths)
+    {
+        const int N = *std::max_element(lengths, lengths + B);
+        std::vector<int32_t> dense((size_t) B * N);
+        for (int b = 0; b < B; ++b)
+            for (int i = 0; i < N; ++i)
+                dense[(size_t) b * N + i] = ids[(size_t) b * n + std::min(i, lengths[b] - 1)];
+        HIP_OK(hipMemcpyAsync(s->ids_in, dense.data(), dense.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s->append_last, lengths, (size_t) B * 4, hipMemcpyHostToDevice, st));
+        for (int b = 0; b < B; ++b)
+            HIP_OK(hipMemcpyAsync(s->out_ids + (size_t) b * Smax + past[b], ids + (size_t) b * n, (size_t) lengths[b] * 4,
+                hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st)); // the caller's buffers (and dense) may go out of scope
+        RUN(s->run_append_ragged(N, max_end, st));
+        RUN(launch_append_advance_ragged(s->seq_len, s->finished, s->append_last, B, N, st) ? 1 : 0);
+        RUN(s->run_sampler(0, st));
+        return 0;
+    }
     HIP_OK(hipMemcpyAsync(s->ids_in, ids, (size_t) B * n * 4, hipMemcpyHostToDevice, st));
     for (int b = 0; b < B; ++b)
         HIP_OK(hipMemcpyAsync(s->out_ids + (size_t) b * Smax + past[b], ids + (size_t) b * n, (size_t) n * 4, hipMemcpyHostToDevice, st));
@@ -428,13 +466,26 @@ static int32_t append_enqueue(tllm_session_t s, const char* who, const int32_t* 
 int32_t tllm_session_append(tllm_session_t s, const int32_t* ids, int32_t n, tllm_stream_t stream)
 {
     std::vector<int32_t> past;
-    return append_enqueue(s, "tllm_session_append", ids, n, 0, past, stream) ? 1 : 0;
+    return append_enqueue(s, "tllm_session_append", ids, n, nullptr, 0, past, stream) ? 1 : 0;
 }
 
-int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32_t n, int32_t max_new_tokens, int32_t end_id,
-    int32_t pad_id, int32_t* output_ids, tllm_stream_t stream)
+int32_t tllm_session_append_ragged(tllm_session_t s, const int32_t* ids, const int32_t* lengths, int32_t W, tllm_stream_t stream)
 {
-    const char* who = "tllm_session_append_generate";
+    const char* who = "tllm_session_append_ragged";
+    RUN(append_session_ok(s, who) ? 1 : 0);
+    if (!lengths)
+    {
+        set_error("%s: null argument", who);
+        return 1;
+    }
+    std::vector<int32_t> past;
+    return append_enqueue(s, who, ids, W, lengths, 0, past, stream) ? 1 : 0;
+}
+
+// tllm_session_append_generate (lengths null) and tllm_session_append_ragged_generate
+static int32_t append_generate_entry(tllm_session_t s, const char* who, const int32_t* ids, int32_t n, const int32_t* lengths,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, int32_t* output_ids, tllm_stream_t stream)
+{
     if (!s || !s->B || !output_ids || max_new_tokens < 1)
     {
         set_error("%s: bad arguments (max_new_tokens >= 1, output_ids set) / setup not called", who);
@@ -447,7 +498,7 @@ int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32
     }
     std::vector<int32_t> past;
     // the last of the max_new_tokens tokens is chosen by a sampler that writes slot past + n + max_new_tokens - 1
-    int rc = append_enqueue(s, who, ids, n, max_new_tokens, past, stream);
+    int rc = append_enqueue(s, who, ids, n, lengths, max_new_tokens, past, stream);
     int produced = 0;
     if (!rc)
         rc = generate_steps(s, max_new_tokens, end_id, &produced, stream);
@@ -461,9 +512,27 @@ int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32
         return 1;
     std::vector<int> first(s->B);
     for (int b = 0; b < s->B; ++b)
-        first[b] = past[b] + n;
+        first[b] = past[b] + (lengths ? lengths[b] : n);
     fill_output_tail(s, output_ids, first, produced, end_id, pad_id);
     return 0;
+}
+
+int32_t tllm_session_append_generate(tllm_session_t s, const int32_t* ids, int32_t n, int32_t max_new_tokens, int32_t end_id,
+    int32_t pad_id, int32_t* output_ids, tllm_stream_t stream)
+{
+    return append_generate_entry(s, "tllm_session_append_generate", ids, n, nullptr, max_new_tokens, end_id, pad_id, output_ids, stream);
+}
+
+int32_t tllm_session_append_ragged_generate(tllm_session_t s, const int32_t* ids, const int32_t* lengths, int32_t W,
+    int32_t max_new_tokens, int32_t end_id, int32_t pad_id, int32_t* output_ids, tllm_stream_t stream)
+{
+    const char* who = "tllm_session_append_ragged_generate";
+    if (s && s->B && !lengths)
+    {
+        set_error("%s: null argument", who);
+        return 1;
+    }
+    return append_generate_entry(s, who, ids, W, lengths, max_new_tokens, end_id, pad_id, output_ids, stream);
 }
 
 int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* mfma)
@@ -512,7 +581,7 @@ static int32_t verify_entry(tllm_session_t s, const char* who, bool sampled, con
     std::vector<int32_t> past;
     int max_past = 0;
     // (one slot behind the n rows: the accept step writes the new pending token to slot p + m + 1 <= p + n)
-    RUN(append_checks(s, who, ids, n, 1, past, &max_past, stream) ? 1 : 0);
+    RUN(append_checks(s, who, ids, n, nullptr, 1, past, &max_past, nullptr, stream) ? 1 : 0);
     hipStream_t st = s->pick(stream);
     const int B = s->B;
     HIP_OK(hipMemcpyAsync(s->ids_in, ids, (size_t) B * n * 4, hipMemcpyHostToDevice, st));

@@ -181,7 +181,9 @@ struct tllm_session
     int32_t *ids_in = nullptr, *cur_ids = nullptr, *out_ids = nullptr, *seq_len = nullptr, *in_len = nullptr,
             *masked = nullptr, *finished = nullptr, *last_tok = nullptr;
     bool has_context = false;       // a prompt has been uploaded since setup (tllm_session_append needs a live cache)
-    int32_t* append_last = nullptr; // [B]: n for every sequence (the gather of the appended rows' last one)
+    int32_t* append_last = nullptr; // [B]: tokens appended per sequence (the gather of the appended rows' last one): n for every
+                                    // sequence, or the lengths of a ragged append - then the attention's n_per_seq too
+    int append_max_end = 0;         // > 0 during a ragged append pass: max_b (past[b] + n_b), and append_last holds the lengths
     int64_t append_wave_launches = 0, append_mfma_launches = 0; // attention launches of tllm_session_append since setup, by kernel
     const float* rope = nullptr;
     int rope_len = 0;
@@ -340,6 +342,8 @@ struct tllm_session
     // tllm_session_append: the prefill schedule on B * n appended rows (ids in ids_in) onto the live cache, head on row n - 1
     int append_attention(const Layer& L, int n, int max_past, hipStream_t st);
     int run_append(int n, int max_past, hipStream_t st);
+    // the ragged pass: lengths already in append_last, n = their maximum, max_end as AppendAttnParams
+    int run_append_ragged(int n, int max_end, hipStream_t st);
     int append_layers(int n, int max_past, hipStream_t st); // embedding + every layer on the B * n rows (ids in ids_in)
     // tllm_session_verify: append_layers, then the head on ALL B * n rows (fp32, verify.logits), their scoring (verify.top1 /
     // .log_probs against the next id of the row) and the accept step in the sampler's place; limit: device int32 [B] or null.

@@ -267,6 +267,11 @@ int tllm_session::append_attention(const Layer& L, int n, int max_past, hipStrea
     a.max_seq_len = Smax;
     a.max_input_len = max_in;
     a.max_past = max_past;
+    if (append_max_end > 0) // a ragged pass: the lengths are in append_last
+    {
+        a.n_per_seq = append_last;
+        a.max_end = append_max_end;
+    }
     a.qkv = qkv;
     a.kv_cache = L.kv;
     a.sequence_length = seq_len;
@@ -300,6 +305,19 @@ int tllm_session::run_append(int n, int max_past, hipStream_t st)
     RUN(append_layers(n, max_past, st));
     // row n - 1 of every sequence (append_last holds n for every sequence: the padded-layout gather takes row last - 1)
     RUN(launch_fill_i32(append_last, n, B, st));
+    RUN(launch_gather_last_token(last_hidden, x, append_last, B, n, hidden, st));
+    RUN(run_head(last_hidden, B, st));
+    return 0;
+}
+
+// The pass on B * n rows, n = max_b n_b, with the lengths n_b in append_last (uploaded by the caller): the attention takes them as
+// n_per_seq, the head runs on row n_b - 1 of every sequence.
+int tllm_session::run_append_ragged(int n, int max_end, hipStream_t st)
+{
+    append_max_end = max_end;
+    const int rc = append_layers(n, 0, st);
+    append_max_end = 0;
+    RUN(rc);
     RUN(launch_gather_last_token(last_hidden, x, append_last, B, n, hidden, st));
     RUN(run_head(last_hidden, B, st));
     return 0;

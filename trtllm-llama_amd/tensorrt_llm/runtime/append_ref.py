@@ -61,10 +61,13 @@ def effective(cache_rows, kv_type, scale_quant_orig=None):
 
 
 def append_ref(q16, k16, v16, cache, past, num_heads, num_kv_heads, head_size, score_scale, kv_type='fp16',
-               kv_scale_quant_orig=None, masked_tokens=None):
+               kv_scale_quant_orig=None, masked_tokens=None, lengths=None):
     """q16 [B, n, H*Dh], k16 / v16 [B, n, Hkv*Dh]: the fp16 values of the appended rows after RoPE (any float dtype); cache
     [B, 2, Hkv, Smax, Dh] float16 / int8 / uint8 as it was BEFORE the append (only slots < past[b] are read); past int [B];
-    masked_tokens int [B, Smax] or None.  Returns (out, absmass) float64 [B, n, H*Dh]."""
+    masked_tokens int [B, Smax] or None.  Returns (out, absmass) float64 [B, n, H*Dh].
+    lengths int [B] or None (= n for every sequence): sequence b appends its first lengths[b] rows alone - for it the call is the
+    one on q16[b, :lengths[b]] ...; rows from lengths[b] on are padding that is never read (NaN there reaches nothing) and whose
+    rows of out and absmass are zero."""
     H, Hkv, Dh = int(num_heads), int(num_kv_heads), int(head_size)
     if not (1 <= Hkv <= H and H % Hkv == 0):
         raise ValueError(f'num_kv_heads {Hkv} must divide num_heads {H}')
@@ -76,20 +79,25 @@ def append_ref(q16, k16, v16, cache, past, num_heads, num_kv_heads, head_size, s
     v = np.asarray(v16, dtype=F64).reshape(B, n, Hkv, Dh)
     out = np.zeros((B, n, H, Dh), F64)
     absmass = np.zeros((B, n, H, Dh), F64)
+    if lengths is not None:
+        lengths = np.asarray(lengths)
+        if lengths.shape != (B, ) or (lengths < 0).any() or (lengths > n).any():
+            raise ValueError(f'lengths must be [B] with values in [0, n = {n}]')
     for b in range(B):
         p = int(past[b])
+        nb = n if lengths is None else int(lengths[b])  # the rows of this sequence; the rest is padding, never touched
         seen, _ = visible(p, 0, None if masked_tokens is None else masked_tokens[b])
-        allowed = np.concatenate([np.broadcast_to(seen, (n, p)), np.tril(np.ones((n, n), dtype=bool))], axis=1)
-        for h in range(H):
-            kk = np.concatenate([effective(cache[b, 0, h // G, :p], kv_type, kv_scale_quant_orig), k[b, :, h // G]], axis=0)
-            vv = np.concatenate([effective(cache[b, 1, h // G, :p], kv_type, kv_scale_quant_orig), v[b, :, h // G]], axis=0)
+        allowed = np.concatenate([np.broadcast_to(seen, (nb, p)), np.tril(np.ones((nb, nb), dtype=bool))], axis=1)
+        for h in range(H if nb else 0):
+            kk = np.concatenate([effective(cache[b, 0, h // G, :p], kv_type, kv_scale_quant_orig), k[b, :nb, h // G]], axis=0)
+            vv = np.concatenate([effective(cache[b, 1, h // G, :p], kv_type, kv_scale_quant_orig), v[b, :nb, h // G]], axis=0)
             # a slot that is not seen never enters a product (what it holds, NaN included, is irrelevant)
-            kk = np.where(np.concatenate([seen, np.ones(n, dtype=bool)])[:, None], kk, 0.0)
-            vv = np.where(np.concatenate([seen, np.ones(n, dtype=bool)])[:, None], vv, 0.0)
-            s = (q[b, :, h] @ kk.T) * F64(score_scale)
+            kk = np.where(np.concatenate([seen, np.ones(nb, dtype=bool)])[:, None], kk, 0.0)
+            vv = np.where(np.concatenate([seen, np.ones(nb, dtype=bool)])[:, None], vv, 0.0)
+            s = (q[b, :nb, h] @ kk.T) * F64(score_scale)
             s[~allowed] = -np.inf
             e = np.exp(s - s.max(axis=1, keepdims=True))
             pr = e / e.sum(axis=1, keepdims=True)
-            out[b, :, h] = pr @ vv
-            absmass[b, :, h] = pr @ np.abs(vv)
+            out[b, :nb, h] = pr @ vv
+            absmass[b, :nb, h] = pr @ np.abs(vv)
     return out.reshape(B, n, H * Dh), absmass.reshape(B, n, H * Dh)

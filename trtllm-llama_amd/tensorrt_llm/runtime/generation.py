@@ -166,8 +166,9 @@ class GenerationSession(object):
         return out
 
     @staticmethod
-    def _check_append_args(ids, batch_size: int, max_input_length: int, vocab_size: int, beam_width: int = 1):
-        """What append() / decode_append() refuse before anything reaches the device."""
+    def _check_append_args(ids, batch_size: int, max_input_length: int, vocab_size: int, beam_width: int = 1, lengths=None):
+        """What append() / decode_append() refuse before anything reaches the device.  lengths (ndarray [batch] or None): tokens
+        per sequence in the padded ids [batch, W], each in [1, W]; ids are range-checked below their length only."""
         if beam_width != 1:
             raise ValueError(f'append() needs beam_width 1 (the session is set up with {beam_width})')
         if ids.ndim != 2 or ids.shape[0] != batch_size:
@@ -177,46 +178,72 @@ class GenerationSession(object):
         if not 1 <= ids.shape[1] <= max_input_length:
             raise ValueError(f'n = {ids.shape[1]} must lie in [1, max_input_length {max_input_length}] '
                              '(longer input: append it in chunks)')
+        if lengths is not None:
+            if lengths.shape != (batch_size, ):
+                raise ValueError(f'input_lengths {lengths.shape}: [batch {batch_size}]')
+            if not np.issubdtype(lengths.dtype, np.integer):
+                raise TypeError('input_lengths must be integers')
+            if lengths.min() < 1 or lengths.max() > ids.shape[1]:
+                raise ValueError(f'input_lengths must lie in [1, {ids.shape[1]}] (a sequence cannot sit an append out)')
+            ids = ids[np.arange(ids.shape[1])[None, :] < lengths[:, None]]
         if ids.size and (ids.min() < 0 or ids.max() >= vocab_size):
             raise ValueError(f'token ids must lie in [0, {vocab_size})')
 
-    def _append_ids(self, input_ids) -> np.ndarray:
+    def _append_ids(self, input_ids, input_lengths=None):
+        """the checked ids as int32 - and, with input_lengths, (ids, lengths)"""
         ids = input_ids.cpu().numpy() if hasattr(input_ids, 'cpu') else np.asarray(input_ids)
+        lens = None
+        if input_lengths is not None:
+            lens = input_lengths.cpu().numpy() if hasattr(input_lengths, 'cpu') else np.asarray(input_lengths)
         if self.mapping.tp_size > 1 or self._model_config.paged_kv_cache:
             raise NotImplementedError('append() is not built for tensor parallelism or the paged KV cache')
-        self._check_append_args(ids, self.batch_size, self.max_input_length, self.vocab_size, getattr(self, 'beam_width', 1))
-        return ids.astype(np.int32)
+        self._check_append_args(ids, self.batch_size, self.max_input_length, self.vocab_size, getattr(self, 'beam_width', 1), lens)
+        if lens is None:
+            return ids.astype(np.int32)
+        return ids.astype(np.int32), lens.astype(np.int32)
 
-    def append(self, input_ids):
+    def append(self, input_ids, input_lengths=None):
         """Append input_ids int32 [batch, n] (torch tensor or ndarray; the same n for every sequence, n <= max_input_length) to
         the live KV cache in one prefill pass (tllm_session_append) - the next user turn of a chat, the next chunk of a long
         prompt, n tokens to verify.  Token 0 takes the place of the pending token the last decode() / append() chose (pass that
         token first to keep it).  Returns the fp32 logits [batch, vocab] of the last appended token; the session has chosen
         the next pending token and generation can continue (decode_append, or another append).  Needs a decode() / score()
-        before it and room in the cache: setup()'s max_new_tokens bounds everything behind the prompt."""
-        self.runtime.append(self._append_ids(input_ids))
+        before it and room in the cache: setup()'s max_new_tokens bounds everything behind the prompt.
+        input_lengths int [batch] (tllm_session_append_ragged): input_ids is padded [batch, W] and sequence b appends its first
+        input_lengths[b] ids alone, 1 <= input_lengths[b] <= W; what stands behind them is never read, and the logits of row b are
+        those of its own last appended token."""
+        if input_lengths is None:
+            self.runtime.append(self._append_ids(input_ids))
+        else:
+            self.runtime.append(*self._append_ids(input_ids, input_lengths))
         logits = self.runtime.logits()
         if hasattr(input_ids, 'cpu'):
             import torch
             return torch.from_numpy(logits).to(input_ids.device)
         return logits
 
-    def decode_append(self, input_ids, sampling_config: SamplingConfig, max_new_tokens: Optional[int] = None):
+    def decode_append(self, input_ids, sampling_config: SamplingConfig, max_new_tokens: Optional[int] = None, input_lengths=None):
         """append(input_ids), then generation as decode() runs it (tllm_session_append_generate), under sampling_config
-        (num_beams 1).  max_new_tokens None: as many as the cache still has room for.  Returns int32 [batch, 1, max_input_length
+        (num_beams 1).  max_new_tokens None: as many as the cache still has room for (with input_lengths, as append() takes
+        them: the room of the sequence that has the least left; every sequence generates the same number).  Returns int32 [batch, 1, max_input_length
         + max_new_tokens(setup)]: the whole token record - prompt, earlier turns, the appended ids, the new tokens - its unused
         tail filled with end_id (pad_id when end_id < 0)."""
         self._check_sampling_config(sampling_config)
         if sampling_config.num_beams != 1:
             raise ValueError('decode_append() needs num_beams 1')
-        ids = self._append_ids(input_ids)
+        lens = None
+        if input_lengths is None:
+            ids = self._append_ids(input_ids)
+        else:
+            ids, lens = self._append_ids(input_ids, input_lengths)
         if max_new_tokens is None:
-            used = int(self.runtime.step_state()['sequence_length'].max())
-            max_new_tokens = self.max_input_length + self.max_new_tokens - used - ids.shape[1]
+            used = self.runtime.step_state()['sequence_length'] + (ids.shape[1] if lens is None else lens)
+            max_new_tokens = self.max_input_length + self.max_new_tokens - int(used.max())
         if max_new_tokens < 1:
             raise ValueError('no room left in the KV cache for a new token: set up with a larger max_new_tokens')
         self.runtime.set_sampling(self._native_sampling(sampling_config))
-        out = self.runtime.append_generate(ids, max_new_tokens, end_id=sampling_config.end_id, pad_id=sampling_config.pad_id)
+        out = self.runtime.append_generate(ids, max_new_tokens, end_id=sampling_config.end_id, pad_id=sampling_config.pad_id,
+                                           lengths=lens)
         out = out.reshape(self.batch_size, 1, -1)
         if hasattr(input_ids, 'cpu'):
             import torch

@@ -99,6 +99,13 @@ def _lib():
     lib.tllm_session_append_generate.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32, c.c_void_p,
                                                  c.c_void_p]
     lib.tllm_session_append_generate.restype = c.c_int32
+    lib.tllm_session_append_ragged.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
+    lib.tllm_session_append_ragged.restype = c.c_int32
+    lib.tllm_session_append_ragged_generate.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int32, c.c_int32, c.c_int32,
+                                                        c.c_int32, c.c_void_p, c.c_void_p]
+    lib.tllm_session_append_ragged_generate.restype = c.c_int32
+    lib.tllm_attention_append_ragged.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p, c.c_int32, c.c_void_p]
+    lib.tllm_attention_append_ragged.restype = c.c_int32
     lib.tllm_session_append_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64), c.POINTER(c.c_int64)]
     lib.tllm_session_append_launches.restype = c.c_int32
     lib.tllm_attention_append.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p]
@@ -236,23 +243,35 @@ def attention_append_kernel(n: int, head_size: int, append_kernel: int = 0) -> i
 
 
 def attention_append(qkv, kv_cache, out, sequence_length, input_lengths, *, num_heads, num_kv_heads=0, head_size, max_input_len,
-                     max_past, masked_tokens=None, kv_cache_type=0, kv_scale_orig_quant=None, kv_scale_quant_orig=None,
-                     rotary_dim=None, neox=1, q_scaling=1.0, append_kernel=0, stream: int = 0):
+                     max_past=None, masked_tokens=None, kv_cache_type=0, kv_scale_orig_quant=None, kv_scale_quant_orig=None,
+                     rotary_dim=None, neox=1, q_scaling=1.0, append_kernel=0, n_per_seq=None, max_end=None, stream: int = 0):
     """tllm_attention_append on torch cuda tensors: qkv fp16 [B, n, (H + 2 Hkv) * Dh] (q and k rewritten in place), kv_cache
     [B, 2, Hkv, Smax, Dh] fp16 / int8 / uint8, out fp16 [B, n, H * Dh], sequence_length / input_lengths int32 [B], masked_tokens
-    int32 [B, Smax] or None, the two scales f32 [1] (one-byte caches; kv_cache_type capi.INT8 / capi.FP8).  Asynchronous."""
+    int32 [B, Smax] or None, the two scales f32 [1] (one-byte caches; kv_cache_type capi.INT8 / capi.FP8).  Asynchronous.
+    n_per_seq (int32 [B] on the device) with max_end >= every sequence_length[b] + n_per_seq[b]: tllm_attention_append_ragged -
+    sequence b appends n_per_seq[b] of its n rows, max_past is ignored."""
     B, n = qkv.shape[0], qkv.shape[1]
-    for t in (qkv, kv_cache, out, sequence_length, input_lengths, masked_tokens, kv_scale_orig_quant, kv_scale_quant_orig):
+    if (n_per_seq is None) != (max_end is None):
+        raise ValueError('n_per_seq and max_end go together')
+    if n_per_seq is None and max_past is None:
+        raise ValueError('max_past must be given (or n_per_seq with max_end)')
+    for t in (qkv, kv_cache, out, sequence_length, input_lengths, masked_tokens, kv_scale_orig_quant, kv_scale_quant_orig,
+              n_per_seq):
         assert t is None or (t.is_cuda and t.is_contiguous())
     ptr = lambda t: t.data_ptr() if t is not None else None
     p = AttentionAppendParamsC(batch=B, n=n, num_heads=num_heads, num_kv_heads=num_kv_heads, head_size=head_size,
                                rotary_dim=head_size if rotary_dim is None else rotary_dim, neox=neox, q_scaling=q_scaling,
                                kv_cache_type=kv_cache_type, max_seq_len=kv_cache.shape[3], max_input_len=max_input_len,
-                               max_past=max_past, append_kernel=append_kernel, qkv=ptr(qkv), kv_cache=ptr(kv_cache),
+                               max_past=max_past or 0, append_kernel=append_kernel, qkv=ptr(qkv), kv_cache=ptr(kv_cache),
                                sequence_length=ptr(sequence_length), input_lengths=ptr(input_lengths),
                                masked_tokens=ptr(masked_tokens), kv_scale_orig_quant=ptr(kv_scale_orig_quant),
                                kv_scale_quant_orig=ptr(kv_scale_quant_orig), out=ptr(out))
-    _check(_lib().tllm_attention_append(ctypes.byref(p), stream), 'attention_append')
+    if n_per_seq is None:
+        _check(_lib().tllm_attention_append(ctypes.byref(p), stream), 'attention_append')
+    else:
+        assert str(n_per_seq.dtype) == 'torch.int32' and tuple(n_per_seq.shape) == (B, ), 'n_per_seq must be int32 [B]'
+        _check(_lib().tllm_attention_append_ragged(ctypes.byref(p), n_per_seq.data_ptr(), int(max_end), stream),
+               'attention_append_ragged')
 
 
 def _sampling_config(top_k=1, top_p=0.0, temperature=1.0, repetition_penalty=1.0, presence_penalty=0.0, min_length=1,
@@ -519,22 +538,42 @@ class NativeSession:
         assert ids.shape == (self.batch, )
         _check(_lib().tllm_session_force_tokens(self._h, ids.ctypes.data, stream), 'force_tokens')
 
-    def append(self, ids, stream: int = 0):
+    def _lengths(self, ids, lengths):
+        lengths = self._i32(lengths)
+        assert lengths.shape == (ids.shape[0], ), 'lengths must be [batch]'
+        return lengths
+
+    def append(self, ids, lengths=None, stream: int = 0):
         """Append ids [batch, n] to the live cache in one prefill pass (tllm_session_append): the parallel form of n times
         force_tokens(ids[:, i]); step(1).  Token 0 replaces the pending token (pass it as ids[:, 0] to keep it).  Afterwards
-        logits() holds the last appended token's logits and a new pending token is chosen.  beam_width 1, linear cache, tp 1."""
+        logits() holds the last appended token's logits and a new pending token is chosen.  beam_width 1, linear cache, tp 1.
+        lengths [batch] (tllm_session_append_ragged): sequence b appends ids[b, :lengths[b]] alone, 1 <= lengths[b] <= n; what
+        stands behind them in the row is never read."""
         ids = self._i32(ids)
         assert ids.ndim == 2 and (not self.batch or ids.shape[0] == self.batch), 'ids must be [batch, n]'
-        _check(_lib().tllm_session_append(self._h, ids.ctypes.data, ids.shape[1], stream), 'append')
+        if lengths is None:
+            _check(_lib().tllm_session_append(self._h, ids.ctypes.data, ids.shape[1], stream), 'append')
+        else:
+            lengths = self._lengths(ids, lengths)
+            _check(_lib().tllm_session_append_ragged(self._h, ids.ctypes.data, lengths.ctypes.data, ids.shape[1], stream),
+                   'append_ragged')
 
-    def append_generate(self, ids, max_new_tokens: int, end_id: int = -1, pad_id: int = 0, stream: int = 0) -> np.ndarray:
+    def append_generate(self, ids, max_new_tokens: int, end_id: int = -1, pad_id: int = 0, stream: int = 0,
+                        lengths=None) -> np.ndarray:
         """append(ids), then up to max_new_tokens generated tokens (tllm_session_append_generate): the token record
-        [batch, max_seq_len], its unused tail filled as generate() fills it."""
+        [batch, max_seq_len], its unused tail filled as generate() fills it.  lengths as append()
+        (tllm_session_append_ragged_generate): every sequence gets the same number of generation steps."""
         ids = self._i32(ids)
         assert ids.ndim == 2 and (not self.batch or ids.shape[0] == self.batch), 'ids must be [batch, n]'
         out = np.empty((self.batch, self.max_in + self.max_new), np.int32)
-        _check(_lib().tllm_session_append_generate(self._h, ids.ctypes.data, ids.shape[1], max_new_tokens, end_id, pad_id,
-                                                   out.ctypes.data, stream), 'append_generate')
+        if lengths is None:
+            _check(_lib().tllm_session_append_generate(self._h, ids.ctypes.data, ids.shape[1], max_new_tokens, end_id, pad_id,
+                                                       out.ctypes.data, stream), 'append_generate')
+        else:
+            lengths = self._lengths(ids, lengths)
+            _check(_lib().tllm_session_append_ragged_generate(self._h, ids.ctypes.data, lengths.ctypes.data, ids.shape[1],
+                                                              max_new_tokens, end_id, pad_id, out.ctypes.data, stream),
+                   'append_ragged_generate')
         return out
 
     def append_launches(self):
