@@ -392,6 +392,9 @@ int32_t tllm_session_fused_retries(tllm_session_t s);
  * residual as a stage of that launch, bit 2 = the gated MLP (gate|up GEMV + down GEMV) in one launch (kernels/mlp_fused.hip, r06;
  * opt-in with the session key fuse_mlp = 1: bit-identical, measured slower than the two GEMVs).  -1 before setup. */
 int32_t tllm_session_decode_form(tllm_session_t s);
+/* Step graphs this session has captured since it was created (tllm_session_step with use_graph: one per capture, none per
+ * replay).  A test sees with it that select / commit / clear of LoRA adapters did not cost a capture.  -1: null session. */
+int64_t tllm_session_graph_captures(tllm_session_t s);
 /* Greedy-step launches this session has enqueued WITH the lm_head launch's arg-max pairs since its last setup (session key
  * greedy_partials; batch 1, tp 1, greedy).  A step captured into the graph counts once, when it is captured, not per replay.
  * 0 after generation steps = every greedy step scanned the logits.  -1: null session. */
@@ -441,6 +444,68 @@ int32_t tllm_gemv(const tllm_gemv_params_t* p, tllm_stream_t stream);
  * index}: per wave of the launch the arg-max of the outputs it finished (ties: lowest index), {-inf, INT32_MAX} elsewhere. */
 #define TLLM_ARGMAX_PAIRS 2048
 int32_t tllm_gemv_head(const tllm_gemv_params_t* p, int32_t resident_rows, void* argmax_part, tllm_stream_t stream);
+
+/* Kernel-level entries of the two LoRA launches (kernels/lora.hip; the rule: kernels.h LoraShrinkParams / LoraExpandParams), so
+ * that tests reach them without a model.  table: device array of num_adapters records {const void* a; const void* b; float
+ * scale; int32 reserved} (24 bytes each): A fp16 [nseg * r, K], B fp16 [sum seg_n, r].  row_adapter: device int32 [M], a value
+ * outside [0, num_adapters) = no adapter for that row.
+ *   shrink  t[m][j] = sum_k A[j][k] xh[m][k] (fp32), xh = x (pro 0) or RMSNorm(x) gamma (pro 1), R = nseg * r rows of A;
+ *   expand  y[m][n] = f16(f32(y[m][n]) + scale * sum_j B[n][j] t[m][seg(n) r + j]) in place; segment g has seg_n[g] columns that
+ *           start at seg_y[g] with row stride seg_ldy[g] (elements). */
+#define TLLM_LORA_MAX_ADAPTERS 8
+#define TLLM_LORA_MAX_SEGMENTS 3
+typedef struct
+{
+    int32_t M, K, R, pro;
+    const void* x;
+    int64_t ldx;
+    const void* gamma;
+    float eps;
+    const int32_t* row_adapter;
+    const void* table;
+    int32_t num_adapters;
+    float* t;
+} tllm_lora_shrink_params_t;
+int32_t tllm_lora_shrink(const tllm_lora_shrink_params_t* p, tllm_stream_t stream);
+typedef struct
+{
+    int32_t M, r, nseg;
+    int32_t seg_n[TLLM_LORA_MAX_SEGMENTS];
+    void* seg_y[TLLM_LORA_MAX_SEGMENTS];
+    int64_t seg_ldy[TLLM_LORA_MAX_SEGMENTS];
+    const float* t;
+    const int32_t* row_adapter;
+    const void* table;
+    int32_t num_adapters;
+} tllm_lora_expand_params_t;
+int32_t tllm_lora_expand(const tllm_lora_expand_params_t* p, tllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LoRA adapters per sequence.  Session keys: lora_max_rank (0 = off; 8, 16, 32 or 64),
+ * lora_max_adapters (1 .. 8, default 1), lora_target_modules (comma list out of q,k,v,o,gate,up,down; default q,k,v,o).
+ * Refused with the key's name: SmoothQuant weights, tp_size > 1 (create), beam_width > 1 (setup).
+ *   lora_set_tensor  stages one tensor of adapter slot `slot`: "layers.{i}.{attention.q|attention.k|attention.v|attention.dense|
+ *                    mlp.fc|mlp.gate|mlp.proj}.lora_a" fp16 [r, K] or ".lora_b" fp16 [N_module, r], r <= lora_max_rank.
+ *                    location as tllm_session_set_tensor (0 host, 1 device); the data is copied before the call returns.
+ *   lora_commit      checks the staged tensors against the configuration (a module outside lora_target_modules is refused by
+ *                    name, one of the list that the adapter lacks is zeros, the ranks of a and b of a module must agree), packs
+ *                    them into the sites' layout zero-padded to lora_max_rank, sets scale = alpha / r (flags & 1, rsLoRA:
+ *                    alpha / sqrt(r)), r the adapter's own rank, and drops the staged tensors.  A refused commit leaves the slot
+ *                    as it was and drops the staged tensors.
+ *   lora_clear       the slot is uncommitted again (sequences that selected it go back to none).
+ *   lora_select      slots: HOST int32 [batch], -1 = none; after setup, holds until changed, all -1 after every setup.  An
+ *                    uncommitted or out-of-range slot is refused with nothing written.
+ * The adapters live at fixed device addresses and the selection is a device array: a captured step graph stays valid across
+ * select, commit and clear.
+ * Ordering: these entry points take no stream.  commit, clear and select wait for the device to be idle (hipDeviceSynchronize)
+ * before they write, so work that an earlier tllm_session_step / _context / _append left in flight on ANY stream - the caller's
+ * non-blocking one included - finishes under the old adapters and selection, and whatever is enqueued afterwards sees the new.
+ * ---------------------------------------------------------------------------------------------- */
+int32_t tllm_session_lora_set_tensor(tllm_session_t s, int32_t slot, const char* name, int32_t dtype, const int64_t* dims,
+    int32_t nbDims, const void* data, int32_t location);
+int32_t tllm_session_lora_commit(tllm_session_t s, int32_t slot, float alpha, int32_t flags);
+int32_t tllm_session_lora_clear(tllm_session_t s, int32_t slot);
+int32_t tllm_session_lora_select(tllm_session_t s, const int32_t* slots);
 
 /* Kernel-level entry for the greedy step that ends a generation step (kernels/decode_step.hip; kernels.h GreedyParams), for parity
  * tests: the arg-max of logits f32 [nparts, batch, vocab_part] (ids >= vocab are padding), then the bookkeeping on the caller's

@@ -759,6 +759,69 @@ struct BeamParams
 };
 int launch_beam_step(const BeamParams& p, hipStream_t stream);
 
+// ---------------------------------------------------------------------------------------------
+// LoRA adapters per row (kernels/lora.hip; the numpy float64 restatement is
+// tensorrt_llm/runtime/lora_ref.py).  A projection site is the fused QKV, attention.dense, fc|gate or mlp.proj.  For row m with
+// adapter a = row_adapter[m] in [0, num_adapters), rank r and scale s_a (alpha / r, or alpha / sqrt(r) under rsLoRA):
+//   shrink  t[m][g r + j] = sum_k f32(A_a[g r + j][k]) f32(xh[m][k]), accumulated and kept in fp32.  xh is the fp16 row the base
+//           projection consumes - x itself (PRO_NONE) or RMSNorm(x) gamma with the rounding points of the GEMV's PRO_RMSNORM
+//           (gemv_impl.h: inv = 1 / sqrt(ss / K + eps) in fp32, n = f16(x inv), xh = f16(n gamma)); g is the segment of the site
+//           (q | k | v of the fused QKV, fc | gate of the MLP's first projections, one segment otherwise);
+//   expand  y[m][n] <- f16(f32(y[m][n]) + s_a sum_j f32(B_a[n][j]) t[m][seg(n) r + j]), in place on the fp16 buffer the base
+//           projection left its result in: qkv, g, u (before SwiGLU), x (behind the residual add of O and of down).  Segments may
+//           be unequal (grouped heads) and may live in different buffers (g and u).
+// A row whose adapter is outside [0, num_adapters) (-1 = none) is not read by shrink, its t row is neither written nor read, and
+// expand leaves its y bits alone.  Adapters of lower rank are zero-padded to r by the caller, so one r serves every launch.
+// No floating-point atomics, a fixed reduction order: the result is a function of the inputs, launch after launch, eager or
+// replayed from a graph.  Nothing step-dependent is a launch argument: the adapters' A / B base pointers and scales come from a
+// device table, the row -> adapter map from a device array.
+// Operands: K % 8 == 0; r one of 8, 16, 32, 64; x, A, B rows 16-byte aligned (ldx % 8 == 0); every index is predicated.
+// Geometry: shrink - one workgroup per (A row, adapter, tile of 8 rows of x), the 256 threads split K, each A row is read once
+// per workgroup and serves the tile's rows of that adapter (four A rows per workgroup beyond 8 rows); expand - r / 8 lanes per B
+// row with 16-byte loads, 2048 / r output columns per workgroup, a tile of 8 (32 beyond 8 rows) rows of t staged in LDS.  A
+// workgroup whose adapter no row of its tile uses returns before its first load.
+// ---------------------------------------------------------------------------------------------
+struct LoraAdapterRec // one adapter slot of one site, 24 bytes in device memory
+{
+    const void* a = nullptr; // fp16 [nseg * r, K]
+    const void* b = nullptr; // fp16 [sum of the segments' N, r]
+    float scale = 0.f;
+    int32_t reserved = 0;
+};
+constexpr int kLoraMaxAdapters = 8;
+constexpr int kLoraMaxSegments = 3;
+struct LoraShrinkParams
+{
+    int32_t M = 0, K = 0;
+    int32_t R = 0;                 // rows of A = nseg * r
+    int32_t pro = PRO_NONE;        // PRO_NONE | PRO_RMSNORM
+    const void* x = nullptr;       // fp16 [M, ldx]
+    int64_t ldx = 0;               // elements
+    const void* gamma = nullptr;   // fp16 [K] (PRO_RMSNORM)
+    float eps = 1e-6f;
+    const int32_t* row_adapter = nullptr; // device int32 [M]
+    const LoraAdapterRec* table = nullptr; // device [num_adapters]
+    int32_t num_adapters = 0;      // 1 .. kLoraMaxAdapters
+    float* t = nullptr;            // f32 [M, R]
+};
+int launch_lora_shrink(const LoraShrinkParams& p, hipStream_t stream);
+struct LoraExpandParams
+{
+    int32_t M = 0, r = 0, nseg = 1; // nseg 1 .. kLoraMaxSegments
+    int32_t seg_n[kLoraMaxSegments] = {0, 0, 0};   // output columns of every segment; B row of column n of segment g: sum(seg_n[< g]) + n
+    void* seg_y[kLoraMaxSegments] = {nullptr, nullptr, nullptr}; // fp16: column 0 of the segment in row 0
+    int64_t seg_ldy[kLoraMaxSegments] = {0, 0, 0}; // elements
+    const float* t = nullptr;      // f32 [M, nseg * r]
+    const int32_t* row_adapter = nullptr;
+    const LoraAdapterRec* table = nullptr;
+    int32_t num_adapters = 0;
+};
+int launch_lora_expand(const LoraExpandParams& p, hipStream_t stream);
+// rows[m] = sel[sequence of row m]: rows_per_seq > 0 - sequence m / rows_per_seq (padded prompt rows, appended rows); else the
+// packed layout, sequence b owns rows [cu_seqlens[b], cu_seqlens[b + 1]).  A row no sequence owns gets -1.
+int launch_lora_row_adapter(int32_t* rows, const int32_t* sel, int32_t batch, int32_t M, int32_t rows_per_seq,
+    const int32_t* cu_seqlens, hipStream_t stream);
+
 // deterministic pseudo-random fill (fp16 ~U(-scale, scale) or int8 ~U[-127,127]) for synthetic KV caches
 int launch_fill_random(void* dst, int32_t dtype, int64_t n, uint32_t seed, float scale, hipStream_t stream);
 // int32 fill

@@ -383,6 +383,49 @@ int32_t tllm_gemv_head(const tllm_gemv_params_t* q, int32_t resident_rows, void*
     return launch_gemv(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
+int32_t tllm_lora_shrink(const tllm_lora_shrink_params_t* q, tllm_stream_t stream)
+{
+    static_assert(TLLM_LORA_MAX_ADAPTERS == kLoraMaxAdapters && TLLM_LORA_MAX_SEGMENTS == kLoraMaxSegments,
+        "the header's constants are the kernels'");
+    if (!q)
+        return 1;
+    LoraShrinkParams p;
+    p.M = q->M;
+    p.K = q->K;
+    p.R = q->R;
+    p.pro = q->pro;
+    p.x = q->x;
+    p.ldx = q->ldx;
+    p.gamma = q->gamma;
+    p.eps = q->eps;
+    p.row_adapter = q->row_adapter;
+    p.table = static_cast<const LoraAdapterRec*>(q->table);
+    p.num_adapters = q->num_adapters;
+    p.t = q->t;
+    return launch_lora_shrink(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_lora_expand(const tllm_lora_expand_params_t* q, tllm_stream_t stream)
+{
+    if (!q)
+        return 1;
+    LoraExpandParams p;
+    p.M = q->M;
+    p.r = q->r;
+    p.nseg = q->nseg;
+    for (int g = 0; g < kLoraMaxSegments; ++g)
+    {
+        p.seg_n[g] = q->seg_n[g];
+        p.seg_y[g] = q->seg_y[g];
+        p.seg_ldy[g] = q->seg_ldy[g];
+    }
+    p.t = q->t;
+    p.row_adapter = q->row_adapter;
+    p.table = static_cast<const LoraAdapterRec*>(q->table);
+    p.num_adapters = q->num_adapters;
+    return launch_lora_expand(p, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
 static bool greedy_args_ok(const tllm_greedy_params_t* q)
 {
     return q && q->logits && q->cur_ids && q->out_ids && q->seq_len && q->batch >= 1 && q->nparts >= 1 && q->vocab_part >= 1

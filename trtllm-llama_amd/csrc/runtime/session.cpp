@@ -15,6 +15,8 @@ tllm_session::~tllm_session()
     if (own_stream)
         (void) hipStreamDestroy(own_stream);
     free_runtime();
+    for (auto p : lora_allocs)
+        (void) hipFree(p);
     for (auto& kv : tensors)
         if (kv.second.owned && kv.second.dev)
             (void) hipFree(kv.second.dev);
@@ -169,6 +171,7 @@ int32_t tllm_session_step(tllm_session_t s, int32_t n_steps, int32_t use_graph, 
         }
         s->graph_stream = st;
         s->graph_comm_gen = comm::p2p::generation();
+        ++s->graph_captures;
     }
     for (int i = 0; i < n_steps; ++i)
     {
@@ -1088,6 +1091,11 @@ int32_t tllm_session_time_kernel(tllm_session_t s, int32_t which, int32_t sweeps
 int64_t tllm_session_greedy_partials_used(tllm_session_t s)
 {
     return s ? s->greedy_partials_used : -1;
+}
+
+int64_t tllm_session_graph_captures(tllm_session_t s)
+{
+    return s ? s->graph_captures : -1;
 }
 
 int32_t tllm_session_decode_form(tllm_session_t s)

@@ -4,6 +4,7 @@
 //   session_setup.cpp    buffer allocation, the decision which decode form runs, check_comm (which withdraws that decision)
 //   session_context.cpp  the prefill schedule
 //   session_decode.cpp   the generation-step schedule, head, sampler, all-reduce
+//   session_lora.cpp     LoRA adapters per sequence: their buffers, load / commit / clear / select, the two launches behind a projection
 //   session.cpp          the rest of the C API: prompt upload, graph capture, the generate loop, getters, instrumentation
 #pragma once
 #include "../../../include/tllm_runtime_api.h"
@@ -269,7 +270,54 @@ struct tllm_session
     std::vector<int32_t> score_pos;  // host: output slot b * max_in + t + 1 of every scored row of the current call
     std::vector<float> score_lp_host;
     std::vector<int32_t> score_top_host;
+    // ---- LoRA adapters per sequence (session_lora.cpp; the rule: kernels.h LoraShrinkParams).  Session keys
+    // lora_max_rank (0 = off), lora_max_adapters, lora_target_modules.  The adapters' device buffers are allocated by the first
+    // lora call and live until the session is destroyed, at fixed addresses; what a setup allocates is the selection, the row map
+    // of the prefill passes and the shrink's result.
+    enum LoraModule { LM_Q = 0, LM_K, LM_V, LM_O, LM_GATE, LM_UP, LM_DOWN, LM_COUNT };
+    enum LoraSite { LS_QKV = 0, LS_DENSE, LS_GATE_UP, LS_PROJ, LS_COUNT };
+    int lora_rank = 0, lora_adapters = 1;
+    bool lora_mod[LM_COUNT] = {false, false, false, false, false, false, false}; // lora_target_modules
+    bool lora_site_on(int site) const
+    {
+        if (lora_rank <= 0)
+            return false;
+        switch (site)
+        {
+        case LS_QKV: return lora_mod[LM_Q] || lora_mod[LM_K] || lora_mod[LM_V];
+        case LS_DENSE: return lora_mod[LM_O];
+        case LS_GATE_UP: return lora_mod[LM_GATE] || lora_mod[LM_UP];
+        default: return lora_mod[LM_DOWN];
+        }
+    }
+    struct LoraSiteBuf
+    {
+        void* a[tllm::kernels::kLoraMaxAdapters]; // fp16 [nseg * lora_rank, K] per slot
+        void* b[tllm::kernels::kLoraMaxAdapters]; // fp16 [N, lora_rank] per slot
+        tllm::kernels::LoraAdapterRec* table;     // device [lora_adapters]
+    };
+    std::vector<LoraSiteBuf> lora_sites; // [num_layers][LS_COUNT]; empty until the first lora call
+    std::vector<void*> lora_allocs;
+    bool lora_committed[tllm::kernels::kLoraMaxAdapters] = {false, false, false, false, false, false, false, false};
+    struct LoraStaged
+    {
+        std::vector<int64_t> dims;
+        std::vector<uint16_t> data;
+    };
+    std::map<std::string, LoraStaged> lora_staged[tllm::kernels::kLoraMaxAdapters]; // host copies between set_tensor and commit
+    std::vector<int32_t> lora_sel_host; // [B], -1 = none
+    int32_t* lora_sel = nullptr;        // device [B]: the row -> adapter map of a generation step
+    int32_t* lora_rows = nullptr;       // device [prompt rows]: ... of a prefill / append pass (lora_map_rows)
+    float* lora_t = nullptr;            // f32 [rows, 3 * lora_rank]
+    int lora_alloc();                   // the adapters' buffers and tables, once
+    void lora_site_shape(int site, int* K, int* nseg, int* seg_n) const;
+    int lora_map_rows(int M, int rows_per_seq, hipStream_t st); // lora_rows <- lora_sel (rows_per_seq 0: the packed prompt layout)
+    // shrink + expand of one site of layer li on M rows: xin (fp16 [M, K of the site]) through prologue pro (PRO_NONE |
+    // PRO_RMSNORM with gamma) is the row the base projection consumed; the site's output buffers are updated in place
+    int lora_apply(int li, int site, int M, const void* xin, int pro, const void* gamma, const int32_t* rows, hipStream_t st);
+
     hipGraphExec_t graph = nullptr;
+    int64_t graph_captures = 0; // step graphs captured since the session was created (tllm_session_graph_captures)
     hipStream_t graph_stream = nullptr;
     uint64_t graph_comm_gen = 0;   // comm::p2p::generation() the step graph was captured under
     uint64_t comm_err_seen = 0;    // comm::p2p::error_generation() at this session's last check_comm
@@ -334,10 +382,10 @@ struct tllm_session
     int profile_prefill_gemms(int M);
     int context_norm(int M, const void* gamma, const float* static_scale, hipStream_t st);
     int context_attention(const Layer& L, bool q_in_attn, hipStream_t st);
-    int context_gate_up(const Layer& L, int M, const void* a_in, const void** p_in, hipStream_t st);
+    int context_gate_up(int li, int M, const void* a_in, const void** p_in, hipStream_t st);
     int context_proj_residual(const Linear& L, int M, const void* in, bool fuse_res, hipStream_t st);
     // one decoder layer of the prefill schedule on M rows; append_n > 0: with the append attention (n rows per sequence)
-    int context_layer(Layer& L, int M, int append_n, int max_past, hipStream_t st);
+    int context_layer(int li, int M, int append_n, int max_past, hipStream_t st);
     int run_context(hipStream_t st);
     // tllm_session_append: the prefill schedule on B * n appended rows (ids in ids_in) onto the live cache, head on row n - 1
     int append_attention(const Layer& L, int n, int max_past, hipStream_t st);

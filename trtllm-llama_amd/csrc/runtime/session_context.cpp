@@ -133,8 +133,9 @@ int tllm_session::context_attention(const Layer& L, bool q_in_attn, hipStream_t 
 }
 
 // fc and gate on a_in, SwiGLU, and the down-projection's quantiser where the mode has one.  *p_in: where the result is
-int tllm_session::context_gate_up(const Layer& L, int M, const void* a_in, const void** p_in, hipStream_t st)
+int tllm_session::context_gate_up(int li, int M, const void* a_in, const void** p_in, hipStream_t st)
 {
+    const Layer& L = layers[li];
     *p_in = inter_buf;
     if (sq && !per_token && M >= 32 && dual_mlp_cfg != 0)
     {
@@ -171,6 +172,13 @@ int tllm_session::context_gate_up(const Layer& L, int M, const void* a_in, const
         }
     }
     RUN(gemm(L.fc, M, a_in, g, DT_HALF, st));
+    if (lora_site_on(LS_GATE_UP))
+    {
+        // gate or up among the adapters' modules (never SmoothQuant): both projections in memory, the adapters on both, then SwiGLU
+        RUN(gemm(L.gate, M, a_in, u, DT_HALF, st));
+        RUN(lora_apply(li, LS_GATE_UP, M, a_in, PRO_NONE, nullptr, lora_rows, st));
+        return launch_swiglu(inter_buf, g, u, (int64_t) M * Ir, st);
+    }
     if (!sq)
     {
         // fp16 / weight-only: SwiGLU folded into the second projection's epilogue (g is read there instead of in a pass of
@@ -200,8 +208,9 @@ int tllm_session::context_proj_residual(const Linear& L, int M, const void* in, 
 // One decoder layer of the prefill schedule on the M rows of x.  append_n == 0: the prompt's layer (context attention);
 // append_n > 0: the layer of an append pass on B * append_n rows (append attention onto the live cache, max_past as
 // AppendAttnParams) - everything but the attention launch is the same code.
-int tllm_session::context_layer(Layer& L, int M, int append_n, int max_past, hipStream_t st)
+int tllm_session::context_layer(int li, int M, int append_n, int max_past, hipStream_t st)
 {
+    Layer& L = layers[li];
     const int D = hidden;
     const void* a_in = sq ? (const void*) q8 : tmp; // what context_norm leaves
     // (weight-only: gemm_woq.hip adds the residual in its epilogue too - same two roundings; its own serve conditions)
@@ -214,6 +223,10 @@ int tllm_session::context_layer(Layer& L, int M, int append_n, int max_past, hip
     // --- attention block
     RUN(context_norm(M, L.ln1, L.ln1_scale, st));
     RUN(gemm(L.qkv, M, a_in, qkv, DT_HALF, st));
+    // LoRA: behind every base projection, on the rows' own adapters (lora_rows, derived per pass from the
+    // selection).  tmp holds the normalised fp16 row the GEMM consumed; the expands update qkv, g / u and x in place.  append,
+    // score and verify run this body and inherit the hooks
+    RUN(lora_apply(li, LS_QKV, M, a_in, PRO_NONE, nullptr, lora_rows, st));
     // SmoothQuant static: the O-projection's input quantiser rides in the context attention's epilogue (padded inputs; with
     // packed inputs M counts real tokens only and the pass below covers exactly those).  The append attention has no such
     // epilogue: the quantiser pass follows it
@@ -227,11 +240,13 @@ int tllm_session::context_layer(Layer& L, int M, int append_n, int max_past, hip
     else if (sq && !q_in_attn)
         RUN(launch_quantize_tensor(q8, ctx, DT_HALF, (int64_t) M * Dr, L.attn_qscale, st));
     RUN(context_proj_residual(L.dense, M, sq ? (const void*) q8 : ctx, fuse_res, st));
+    RUN(lora_apply(li, LS_DENSE, M, ctx, PRO_NONE, nullptr, lora_rows, st));
     // --- MLP block
     RUN(context_norm(M, L.ln2, L.ln2_scale, st));
     const void* p_in = nullptr; // inter_buf or q8, as the path through gate|up leaves it
-    RUN(context_gate_up(L, M, a_in, &p_in, st));
+    RUN(context_gate_up(li, M, a_in, &p_in, st));
     RUN(context_proj_residual(L.proj, M, p_in, fuse_res, st));
+    RUN(lora_apply(li, LS_PROJ, M, p_in, PRO_NONE, nullptr, lora_rows, st));
     return 0;
 }
 
@@ -240,8 +255,9 @@ int tllm_session::run_context(hipStream_t st)
 {
     const int S = max_in, M = packed ? ctx_tokens : Bc * S, D = hidden;
     RUN(launch_embedding(x, ids_in, emb, M, D, vocab, st));
+    RUN(lora_map_rows(M, packed ? 0 : S, st));
     for (int li = 0; li < num_layers; ++li)
-        RUN(context_layer(layers[li], M, 0, 0, st));
+        RUN(context_layer(li, M, 0, 0, st));
     // head: last real token of every sequence -> ln_f -> lm_head -> fp32 logits  (Q/llama_model.py:272-279)
     if (packed)
         RUN(launch_gather_rows(last_hidden, x, last_rows, Bc, D, st));
@@ -294,8 +310,9 @@ int tllm_session::append_layers(int n, int max_past, hipStream_t st)
 {
     const int M = B * n;
     RUN(launch_embedding(x, ids_in, emb, M, hidden, vocab, st));
+    RUN(lora_map_rows(M, n, st));
     for (int li = 0; li < num_layers; ++li)
-        RUN(context_layer(layers[li], M, n, max_past, st));
+        RUN(context_layer(li, M, n, max_past, st));
     return 0;
 }
 

@@ -395,8 +395,11 @@ int tllm_session::stage_qkv(const DecodeStep& ds, int li)
         return gemv(L.qkv, B, PRO_NONE, EPI_NONE, ar_norm, hidden, nullptr, nullptr, nullptr, nullptr, qkv, QKVr, DT_HALF, nullptr,
             ds.st, ds.ar_rows);
     }
-    return gemv(L.qkv, B, ds.pro_norm, EPI_NONE, x, hidden, L.ln1, L.ln1_scale, nullptr, nullptr, qkv, QKVr, DT_HALF, nullptr,
-        ds.st, nullptr, ds.taps ? tap_ptr(0, li) : nullptr);
+    RUN(gemv(L.qkv, B, ds.pro_norm, EPI_NONE, x, hidden, L.ln1, L.ln1_scale, nullptr, nullptr, qkv, QKVr, DT_HALF, nullptr,
+        ds.st, nullptr, ds.taps ? tap_ptr(0, li) : nullptr));
+    // LoRA (tp 1, no SmoothQuant): the GEMV normalised x inside its prologue and left no fp16 row, so the shrink normalises again
+    // with the same rounding points; the expand updates qkv in place, ahead of RoPE and the cache write
+    return lora_apply(li, LS_QKV, B, x, PRO_RMSNORM, L.ln1, lora_sel, ds.st);
 }
 
 // K2 / K3: RoPE + KV append + split-KV attention, merged in the launch (attn_plan.in_launch_merge) or by its combine launch
@@ -456,8 +459,9 @@ int tllm_session::stage_o_proj(const DecodeStep& ds, int li)
     if (ds.fused_ar)
         return gemv(L.dense, B, pro, EPI_NONE, o_in, Dr, nullptr, L.attn_qscale, nullptr, nullptr, ar_partial, hidden, DT_HALF,
             nullptr, ds.st, nullptr, tap);
-    return gemv(L.dense, B, pro, ds.epi_res, o_in, Dr, nullptr, L.attn_qscale, x, nullptr, x, hidden, DT_HALF, nullptr, ds.st,
-        nullptr, tap);
+    RUN(gemv(L.dense, B, pro, ds.epi_res, o_in, Dr, nullptr, L.attn_qscale, x, nullptr, x, hidden, DT_HALF, nullptr, ds.st,
+        nullptr, tap));
+    return lora_apply(li, LS_DENSE, B, ctx, PRO_NONE, nullptr, lora_sel, ds.st); // on x, behind the residual add
 }
 
 // Behind a row-parallel projection: x <- sum over ranks.  The fused seam also adds the residual and leaves
@@ -534,6 +538,17 @@ int tllm_session::stage_gate_up(const DecodeStep& ds, int li)
         return gemv(L.fc, B, PRO_NONE, epi, ar_norm, hidden, nullptr, nullptr, nullptr, L.mlp_qscale, out, Ir, out_dtype, &L.gate,
             ds.st, ds.ar_rows);
     }
+    if (lora_site_on(LS_GATE_UP))
+    {
+        // gate or up among the adapters' modules: the SwiGLU epilogue would consume the two projections before the adapter has
+        // reached them, so they go to g / u as two GEMVs, the LoRA launches update both, and the SwiGLU pass follows - the
+        // unfused sequence of the prefill (context_gate_up), same rounding points
+        RUN(gemv(L.fc, B, ds.pro_norm, EPI_NONE, x, hidden, L.ln2, nullptr, nullptr, nullptr, g, Ir, DT_HALF, nullptr, ds.st, nullptr,
+            ds.taps ? tap_ptr(2, li) : nullptr));
+        RUN(gemv(L.gate, B, ds.pro_norm, EPI_NONE, x, hidden, L.ln2, nullptr, nullptr, nullptr, u, Ir, DT_HALF, nullptr, ds.st));
+        RUN(lora_apply(li, LS_GATE_UP, B, x, PRO_RMSNORM, L.ln2, lora_sel, ds.st));
+        return timed(PC_OTHER, ds.st, [&] { return launch_swiglu(inter_buf, g, u, (int64_t) B * Ir, ds.st) ? 1 : 0; });
+    }
     return gemv(L.fc, B, ds.pro_norm, epi, x, hidden, L.ln2, L.ln2_scale, nullptr, L.mlp_qscale, out, Ir, out_dtype, &L.gate, ds.st,
         nullptr, ds.taps ? tap_ptr(2, li) : nullptr);
 }
@@ -552,8 +567,9 @@ int tllm_session::stage_down(const DecodeStep& ds, int li)
     if (ds.fused_ar)
         return gemv(L.proj, B, pro, EPI_NONE, in, Ir, nullptr, L.mlp_qscale, nullptr, nullptr, ar_partial, hidden, DT_HALF, nullptr,
             ds.st, nullptr, tap);
-    return gemv(L.proj, B, pro, ds.epi_res, in, Ir, nullptr, L.mlp_qscale, x, nullptr, x, hidden, DT_HALF, nullptr, ds.st, nullptr,
-        tap);
+    RUN(gemv(L.proj, B, pro, ds.epi_res, in, Ir, nullptr, L.mlp_qscale, x, nullptr, x, hidden, DT_HALF, nullptr, ds.st, nullptr,
+        tap));
+    return lora_apply(li, LS_PROJ, B, inter_buf, PRO_NONE, nullptr, lora_sel, ds.st); // on x, behind the residual add
 }
 
 int tllm_session::run_decode_step(hipStream_t st)

@@ -130,6 +130,20 @@ int tllm_session::alloc_buffers()
     RUN(dalloc(&step_epoch, 64));
     HIP_OK(hipMemset(step_epoch, 0, 64));
     fused_err = step_epoch + 8;
+    lora_sel = lora_rows = nullptr;
+    lora_t = nullptr;
+    lora_sel_host.assign(B, -1);
+    if (lora_rank > 0)
+    {
+        // the selection (all -1 after a setup), the row map of a prefill pass, the shrink's result; the adapters themselves are
+        // not the setup's: they keep their addresses and contents across setups
+        RUN(lora_alloc());
+        RUN(dalloc(&lora_sel, (size_t) B * 4));
+        HIP_OK(hipMemcpy(lora_sel, lora_sel_host.data(), (size_t) B * 4, hipMemcpyHostToDevice));
+        RUN(dalloc(&lora_rows, M * 4));
+        HIP_OK(hipMemset(lora_rows, 0xff, M * 4));
+        RUN(dalloc(&lora_t, M * kLoraMaxSegments * lora_rank * 4));
+    }
     return 0;
 }
 
@@ -153,6 +167,10 @@ int tllm_session::decide_decode_form()
     o_fused = false;
     mlp_fused_dec = false;
     if (layers.empty())
+        return 0;
+    // LoRA: the adapters' launches sit behind the QKV, O and down GEMVs (stage_qkv, stage_o_proj, stage_down), so the step runs
+    // the separate launches - neither the one-launch front nor the one-launch MLP
+    if (lora_rank > 0)
         return 0;
     // the one-launch MLP: batch 1, tp 1, static SmoothQuant, only when asked for
     if (fuse_mlp_cfg > 0 && B == 1 && beam == 1 && tp == 1 && sq && !per_token && mlp_fused_serves(D, Ir, D))
@@ -370,6 +388,11 @@ int32_t tllm_session_setup_beam(tllm_session_t s, int32_t batch_size, int32_t be
         // the device-side beam step stages the cache-indirection rows it re-parents in LDS (decode_step.hip beam_step_kernel)
         set_error("tllm_session_setup: beam_width %d x max_seq_len %d exceeds the beam step's LDS staging (24576 int32)", beam_width,
             max_input_len + max_new_tokens);
+        return 1;
+    }
+    if (beam_width > 1 && s->lora_rank > 0)
+    {
+        set_error("tllm_session_setup: lora_max_rank with beam_width %d is not built (beam_width 1 only)", beam_width);
         return 1;
     }
     s->free_runtime();

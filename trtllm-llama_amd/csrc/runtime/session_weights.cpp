@@ -241,6 +241,64 @@ tllm_session_t tllm_session_create(const char* config_text)
         s->wtype = W_INT8_SQ;
     for (int i = 0; i < s->tp; ++i)
         s->group.push_back(i);
+    // LoRA adapters per sequence
+    s->lora_rank = geti("lora_max_rank", 0);
+    if (s->lora_rank != 0)
+    {
+        const int r = s->lora_rank;
+        if (r != 8 && r != 16 && r != 32 && r != 64)
+        {
+            set_error("tllm_session_create: lora_max_rank %d is not 0 (off), 8, 16, 32 or 64", r);
+            return nullptr;
+        }
+        s->lora_adapters = geti("lora_max_adapters", 1);
+        if (s->lora_adapters < 1 || s->lora_adapters > kLoraMaxAdapters)
+        {
+            set_error("tllm_session_create: lora_max_adapters %d outside [1, %d]", s->lora_adapters, kLoraMaxAdapters);
+            return nullptr;
+        }
+        if (s->sq)
+        {
+            set_error("tllm_session_create: lora_max_rank with SmoothQuant weights is not built (the smoother is folded into the norm "
+                      "weights and would have to be folded into the columns of every lora_a)");
+            return nullptr;
+        }
+        if (s->tp > 1)
+        {
+            set_error("tllm_session_create: lora_max_rank with tp_size %d is not built (tp_size 1 only)", s->tp);
+            return nullptr;
+        }
+        if (s->hidden % 8 || s->Dr % 8 || s->Ir % 8)
+        {
+            set_error("tllm_session_create: lora_max_rank needs hidden_size and inter_size to be multiples of 8");
+            return nullptr;
+        }
+        static const char* keys[tllm_session::LM_COUNT] = {"q", "k", "v", "o", "gate", "up", "down"};
+        std::istringstream mods(kv.count("lora_target_modules") ? kv["lora_target_modules"] : std::string("q,k,v,o"));
+        std::string m;
+        int found = 0;
+        while (std::getline(mods, m, ','))
+        {
+            const size_t a = m.find_first_not_of(" \t"), b = m.find_last_not_of(" \t");
+            m = a == std::string::npos ? std::string() : m.substr(a, b - a + 1);
+            int which = -1;
+            for (int i = 0; i < tllm_session::LM_COUNT; ++i)
+                if (m == keys[i])
+                    which = i;
+            if (which < 0)
+            {
+                set_error("tllm_session_create: lora_target_modules names '%s'; the modules are q,k,v,o,gate,up,down", m.c_str());
+                return nullptr;
+            }
+            s->lora_mod[which] = true;
+            ++found;
+        }
+        if (!found)
+        {
+            set_error("tllm_session_create: lora_target_modules is empty");
+            return nullptr;
+        }
+    }
     return s.release();
 }
 

@@ -76,7 +76,22 @@ def parse_arguments(args=None):
                         'model directory holds a calibrated one)')
     p.add_argument('--random_seed', type=int, default=None)
     p.add_argument('--paged_kv_cache', action='store_true', default=False)
+    # LoRA adapters per sequence over this engine (run.py --lora_dir): the engine reserves device memory for --lora_max_adapters
+    # adapters of rank <= --lora_max_rank on --lora_target_modules and runs the separate-launch generation step
+    p.add_argument('--lora_max_rank', type=int, default=0, choices=[0, 8, 16, 32, 64], help='0 = no adapters')
+    p.add_argument('--lora_max_adapters', type=int, default=1, help='adapter slots, 1 to 8')
+    p.add_argument('--lora_target_modules', type=str, default='q,k,v,o', help='comma list out of q,k,v,o,gate,up,down')
     args = p.parse_args(args)
+    if args.lora_max_rank:
+        if args.use_smooth_quant:
+            p.error('--lora_max_rank with --use_smooth_quant is not built (the smoother would have to be folded into every lora_a)')
+        if args.world_size > 1:
+            p.error('--lora_max_rank with --world_size > 1 is not built')
+        if not 1 <= args.lora_max_adapters <= 8:
+            p.error('--lora_max_adapters must lie in [1, 8]')
+        bad = [m for m in args.lora_target_modules.split(',') if m.strip() not in ('q', 'k', 'v', 'o', 'gate', 'up', 'down')]
+        if bad or not args.lora_target_modules.strip():
+            p.error(f'--lora_target_modules {args.lora_target_modules!r}: a comma list out of q,k,v,o,gate,up,down')
     logger.set_level(args.log_level)
     if args.dtype == 'bfloat16':
         raise SystemExit('bfloat16 engines are not built on MI355X')
@@ -189,7 +204,9 @@ def build(rank, args):
             max_position_embeddings=args.n_positions, max_batch_size=args.max_batch_size,
             max_input_len=args.max_input_len, max_output_len=args.max_output_len, int8=int8_trt_flag,
             opt_level=args.builder_opt, multi_query_mode=args.multi_query_mode, inter_size=args.inter_size,
-            quant_mode=int(args.quant_mode), num_kv_heads=args.n_kv_head)
+            quant_mode=int(args.quant_mode), num_kv_heads=args.n_kv_head,
+            **(dict(lora_max_rank=args.lora_max_rank, lora_max_adapters=args.lora_max_adapters,
+                    lora_target_modules=args.lora_target_modules) if args.lora_max_rank else {}))
         engine_name = get_engine_name(MODEL_NAME, args.dtype, args.world_size, cur_rank)
         engine = build_rank_engine(builder, builder_config, engine_name, cur_rank, args)
         assert engine is not None, f'Failed to build engine for rank {cur_rank}'

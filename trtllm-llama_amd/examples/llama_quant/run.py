@@ -49,6 +49,11 @@ def parse_arguments(args=None):
     p.add_argument('--prompt_lookup_sampling', action='store_true',
                    help='let --prompt_lookup_tokens combine with --top_k / --top_p / --temperature / --repetition_penalty / '
                    '--random_seed: a draft is kept where it equals the token the sampler draws (the same tokens as without lookup).')
+    # LoRA adapters (an engine built with --lora_max_rank): HF PEFT directories go into slots 0, 1, ... in the order given
+    p.add_argument('--lora_dir', type=str, nargs='+', default=None, help='HF PEFT adapter directories (adapter_config.json + '
+                   'adapter_model.safetensors)')
+    p.add_argument('--lora_slots', type=str, default=None, help='comma list, one slot per sequence of the batch, -1 = no adapter '
+                   '(default: slot 0 for every sequence when --lora_dir is given)')
     return p.parse_args(args)
 
 
@@ -72,7 +77,8 @@ def load_session(engine_dir):
                                gpt_attention_plugin=bool(config['plugin_config']['gpt_attention_plugin']),
                                multi_query_mode=bc.get('multi_query_mode', False),
                                remove_input_padding=config['plugin_config']['remove_input_padding'],
-                               num_kv_heads=bc.get('num_kv_heads', bc['num_heads']) // world_size)
+                               num_kv_heads=bc.get('num_kv_heads', bc['num_heads']) // world_size,
+                               lora_max_rank=int(bc.get('lora_max_rank') or 0), lora_target_modules=bc.get('lora_target_modules'))
     path = Path(engine_dir) / get_engine_name('llama', dtype, world_size, runtime_rank)
     with open(path, 'rb') as f:
         engine_buffer = f.read()
@@ -82,9 +88,15 @@ def load_session(engine_dir):
 def generate(max_output_len, log_level='error', engine_dir='llama_outputs', input_text=None, input_file=None,
              output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55, top_k=1, top_p=0.0,
              temperature=1.0, repetition_penalty=1.0, random_seed=None, prompt_lookup_tokens=0, prompt_lookup_ngram=3,
-             prompt_lookup_sampling=False):
+             prompt_lookup_sampling=False, lora_dir=None, lora_slots=None):
     tensorrt_llm.logger.set_level(log_level)
     decoder, runtime_rank = load_session(engine_dir)
+    for slot, d in enumerate(lora_dir or []):
+        decoder.load_lora(d, slot)
+    if isinstance(lora_slots, str):
+        lora_slots = [int(v) for v in lora_slots.split(',')]
+    if lora_slots is None and lora_dir:
+        lora_slots = [0]  # one prompt per run
     sampling_config = SamplingConfig(end_id=EOS_TOKEN, pad_id=PAD_TOKEN, num_beams=num_beams, top_k=top_k, top_p=top_p,
                                      temperature=temperature, repetition_penalty=repetition_penalty)
     sampling_config.random_seed = random_seed
@@ -110,11 +122,11 @@ def generate(max_output_len, log_level='error', engine_dir='llama_outputs', inpu
             decoder.setup(ids.shape[0], int(input_lengths.max()), max_output_len + prompt_lookup_tokens)
             output_ids = decoder.decode_lookup(ids, input_lengths, sampling_config, num_draft_tokens=prompt_lookup_tokens,
                                                max_ngram=prompt_lookup_ngram, max_new_tokens=max_output_len,
-                                               speculative_sampling=prompt_lookup_sampling)
+                                               speculative_sampling=prompt_lookup_sampling, lora_slots=lora_slots)
             output_ids = output_ids[:, :, :ids.shape[1] + max_output_len]
         else:
             decoder.setup(ids.shape[0], int(input_lengths.max()), max_output_len)
-            output_ids = decoder.decode(ids, input_lengths, sampling_config)
+            output_ids = decoder.decode(ids, input_lengths, sampling_config, lora_slots=lora_slots)
         if tokenizer is not None and runtime_rank == 0:
             outputs = output_ids[0, 0, ids.shape[1]:].tolist()
             tokenizer.decode(outputs)

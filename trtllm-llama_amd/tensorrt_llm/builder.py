@@ -98,6 +98,11 @@ class Builder():
         # grouped-query attention: the key travels only when it differs, so that multi-head engines stay byte-identical
         if int(cfg.get('num_kv_heads') or cfg['num_heads']) != int(cfg['num_heads']):
             header['num_kv_heads'] = int(cfg['num_kv_heads'])
+        # LoRA: the three session keys travel only when set - engines built without them stay byte-identical
+        if int(cfg.get('lora_max_rank') or 0) > 0:
+            header['lora_max_rank'] = int(cfg['lora_max_rank'])
+            header['lora_max_adapters'] = int(cfg.get('lora_max_adapters') or 1)
+            header['lora_target_modules'] = str(cfg.get('lora_target_modules') or 'q,k,v,o')
         tactics = self._profile_gemm_tactics(cfg, inter_size)
         if tactics:
             header['gemm_tactics'] = tactics

@@ -32,6 +32,8 @@ class ModelConfig:
     tokens_per_block: int = 64
     use_prompt_tuning: bool = False
     num_kv_heads: int = None  # grouped-query attention: K/V heads of this rank (None: num_heads); the engine header is what the session runs
+    lora_max_rank: int = 0  # LoRA: what the engine was built with (build.py --lora_max_rank / --lora_target_modules); load_lora() checks
+    lora_target_modules: str = None  # an adapter against them before the session does
 
 
 @dataclass
@@ -100,8 +102,31 @@ class GenerationSession(object):
         self.beam_width = beam_width
         self.runtime.setup(batch_size, max_input_length, max_new_tokens, beam_width)
 
+    def load_lora(self, adapter_dir, slot: int = 0):
+        """Load a Hugging Face PEFT LoRA adapter directory (adapter_config.json + adapter_model.safetensors) into adapter slot `slot`
+        of an engine built with --lora_max_rank (tensorrt_llm/runtime/lora.py reads it; `peft` is not needed).  Select it per
+        sequence with the lora_slots argument of decode() / append() / score() / decode_append() / decode_lookup()."""
+        from .lora import load_peft_adapter
+        mc = dict(num_layers=self.num_layers)
+        if self._model_config.lora_max_rank:
+            mc['lora_max_rank'] = self._model_config.lora_max_rank
+        if self._model_config.lora_target_modules:
+            mc['lora_target_modules'] = self._model_config.lora_target_modules
+        ad = load_peft_adapter(adapter_dir, mc)
+        self.runtime.lora_load(slot, ad['tensors'], ad['alpha'], use_rslora=ad['use_rslora'])
+        return ad
+
+    def _select_lora(self, lora_slots):
+        """lora_slots: None (the selection stays what it is: none after setup()) or one adapter slot per sequence, -1 = none"""
+        if lora_slots is None:
+            return
+        slots = np.asarray(lora_slots.cpu() if hasattr(lora_slots, 'cpu') else lora_slots)
+        if slots.shape != (self.batch_size, ) or not np.issubdtype(slots.dtype, np.integer):
+            raise ValueError(f'lora_slots must be {self.batch_size} integers, one slot per sequence (-1 = no adapter)')
+        self.runtime.lora_select(slots.astype(np.int32))
+
     def decode(self, input_ids, input_lengths, sampling_config: SamplingConfig, prompt_embedding_table=None,
-               tasks=None, prompt_vocab_size=None, max_new_tokens: Optional[int] = None):
+               tasks=None, prompt_vocab_size=None, max_new_tokens: Optional[int] = None, lora_slots=None):
         """input_ids: int32 [batch, max_input_length] (torch tensor or ndarray), padded with pad_id.
         max_new_tokens: fewer than setup()'s (None: all of them) - a first turn that leaves cache room for decode_append().
         Returns int32 [batch, num_beams, max_input_length + max_new_tokens] like the reference (generation.py:991-997):
@@ -121,6 +146,7 @@ class GenerationSession(object):
         new = self.max_new_tokens if max_new_tokens is None else int(max_new_tokens)
         if not 0 <= new <= self.max_new_tokens:
             raise ValueError(f'max_new_tokens {new} outside [0, {self.max_new_tokens}] (setup)')
+        self._select_lora(lora_slots)
         out = self.runtime.generate(ids.astype(np.int32), lens.astype(np.int32), new,
                                     end_id=sampling_config.end_id, pad_id=sampling_config.pad_id)
         out = out.reshape(self.batch_size, sampling_config.num_beams, -1)
@@ -144,7 +170,7 @@ class GenerationSession(object):
         if lens.size and (lens.min() < 1 or lens.max() > max_input_length):
             raise ValueError(f'input_lengths must lie in [1, {max_input_length}]')
 
-    def score(self, input_ids, input_lengths):
+    def score(self, input_ids, input_lengths, lora_slots=None):
         """Teacher-forced scoring of the prompts in one prefill (tllm_session_score).  input_ids int32 [batch, max_input_length]
         and input_lengths [batch] as decode() takes them (torch tensor or ndarray).  Returns a dict:
           log_probs  f32 [batch, max_input_length]: log p(ids[b][t] | ids[b][:t]) for 1 <= t < len_b, 0 elsewhere;
@@ -157,6 +183,7 @@ class GenerationSession(object):
         ids = input_ids.cpu().numpy() if is_torch else np.asarray(input_ids)
         lens = input_lengths.cpu().numpy() if hasattr(input_lengths, 'cpu') else np.asarray(input_lengths)
         self._check_score_args(ids, lens, self.batch_size, self.max_input_length, getattr(self, 'beam_width', 1))
+        self._select_lora(lora_slots)
         lp, top = self.runtime.score(ids.astype(np.int32), lens.astype(np.int32))
         ppl = np.array([perplexity(lp[b], lens[b:b + 1]) for b in range(len(lens))], np.float32)
         out = dict(log_probs=lp, top1_ids=top, perplexity=ppl)
@@ -202,7 +229,7 @@ class GenerationSession(object):
             return ids.astype(np.int32)
         return ids.astype(np.int32), lens.astype(np.int32)
 
-    def append(self, input_ids, input_lengths=None):
+    def append(self, input_ids, input_lengths=None, lora_slots=None):
         """Append input_ids int32 [batch, n] (torch tensor or ndarray; the same n for every sequence, n <= max_input_length) to
         the live KV cache in one prefill pass (tllm_session_append) - the next user turn of a chat, the next chunk of a long
         prompt, n tokens to verify.  Token 0 takes the place of the pending token the last decode() / append() chose (pass that
@@ -212,6 +239,7 @@ class GenerationSession(object):
         input_lengths int [batch] (tllm_session_append_ragged): input_ids is padded [batch, W] and sequence b appends its first
         input_lengths[b] ids alone, 1 <= input_lengths[b] <= W; what stands behind them is never read, and the logits of row b are
         those of its own last appended token."""
+        self._select_lora(lora_slots)
         if input_lengths is None:
             self.runtime.append(self._append_ids(input_ids))
         else:
@@ -222,7 +250,8 @@ class GenerationSession(object):
             return torch.from_numpy(logits).to(input_ids.device)
         return logits
 
-    def decode_append(self, input_ids, sampling_config: SamplingConfig, max_new_tokens: Optional[int] = None, input_lengths=None):
+    def decode_append(self, input_ids, sampling_config: SamplingConfig, max_new_tokens: Optional[int] = None, input_lengths=None,
+                      lora_slots=None):
         """append(input_ids), then generation as decode() runs it (tllm_session_append_generate), under sampling_config
         (num_beams 1).  max_new_tokens None: as many as the cache still has room for (with input_lengths, as append() takes
         them: the room of the sequence that has the least left; every sequence generates the same number).  Returns int32 [batch, 1, max_input_length
@@ -242,6 +271,7 @@ class GenerationSession(object):
         if max_new_tokens < 1:
             raise ValueError('no room left in the KV cache for a new token: set up with a larger max_new_tokens')
         self.runtime.set_sampling(self._native_sampling(sampling_config))
+        self._select_lora(lora_slots)
         out = self.runtime.append_generate(ids, max_new_tokens, end_id=sampling_config.end_id, pad_id=sampling_config.pad_id,
                                            lengths=lens)
         out = out.reshape(self.batch_size, 1, -1)
@@ -292,7 +322,7 @@ class GenerationSession(object):
             raise ValueError(f'num_draft_tokens {num_draft_tokens} must lie in [2, 32] and max_ngram {max_ngram} in [1, 8]')
 
     def decode_lookup(self, input_ids, input_lengths, sampling_config: SamplingConfig, num_draft_tokens: int = 8, max_ngram: int = 3,
-                      max_new_tokens: Optional[int] = None, speculative_sampling: bool = False):
+                      max_new_tokens: Optional[int] = None, speculative_sampling: bool = False, lora_slots=None):
         """decode() with prompt-lookup speculation (tllm_session_generate_lookup): the same tokens, greedy; where the text repeats
         an n-gram of the prompt or of itself, up to num_draft_tokens - 1 following tokens are verified in one pass.  max_new_tokens
         None: setup()'s less num_draft_tokens, the room the last verify pass needs.  Returns what decode() returns; the counters of
@@ -313,6 +343,7 @@ class GenerationSession(object):
             raise ValueError(f'max_new_tokens {new} outside [1, {self.max_new_tokens - num_draft_tokens}]: setup()\'s less '
                              'num_draft_tokens')
         self.runtime.set_sampling(self._native_sampling(sampling_config))
+        self._select_lora(lora_slots)
         out, self.lookup_stats = self.runtime.generate_lookup(ids.astype(np.int32), lens.astype(np.int32), new,
                                                               end_id=sampling_config.end_id, pad_id=sampling_config.pad_id,
                                                               num_draft_tokens=num_draft_tokens, max_ngram=max_ngram,

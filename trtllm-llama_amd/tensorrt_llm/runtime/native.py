@@ -136,6 +136,17 @@ def _lib():
                                           c.POINTER(SamplingConfigC), c.c_int32, c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p,
                                           c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.tllm_spec_sample_rows.restype = c.c_int32
+    lib.tllm_session_lora_set_tensor.argtypes = [c.c_void_p, c.c_int32, c.c_char_p, c.c_int32, c.POINTER(c.c_int64), c.c_int32,
+                                                 c.c_void_p, c.c_int32]
+    lib.tllm_session_lora_set_tensor.restype = c.c_int32
+    lib.tllm_session_lora_commit.argtypes = [c.c_void_p, c.c_int32, c.c_float, c.c_int32]
+    lib.tllm_session_lora_commit.restype = c.c_int32
+    lib.tllm_session_lora_clear.argtypes = [c.c_void_p, c.c_int32]
+    lib.tllm_session_lora_clear.restype = c.c_int32
+    lib.tllm_session_lora_select.argtypes = [c.c_void_p, c.c_void_p]
+    lib.tllm_session_lora_select.restype = c.c_int32
+    lib.tllm_session_graph_captures.argtypes = [c.c_void_p]
+    lib.tllm_session_graph_captures.restype = c.c_int64
     _bound = True
     return lib
 
@@ -400,6 +411,37 @@ class NativeSession:
         """batch prompts x beam_width hypotheses (beam search when > 1, beam_width <= 8; beyond 8 sequences the generation GEMVs run in slabs of 8 rows)."""
         _check(_lib().tllm_session_setup_beam(self._h, batch, beam_width, max_input_len, max_new_tokens), 'setup')
         self.batch, self.max_in, self.max_new, self.beam = batch, max_input_len, max_new_tokens, beam_width
+
+    def lora_load(self, slot: int, tensors: Dict, alpha: float, use_rslora: bool = False):
+        """One LoRA adapter into slot `slot` (session keys lora_max_rank / lora_max_adapters / lora_target_modules): tensors maps
+        'layers.{i}.{attention.q|attention.k|attention.v|attention.dense|mlp.fc|mlp.gate|mlp.proj}.lora_a' to fp16 [r, K] and
+        '.lora_b' to fp16 [N, r].  scale = alpha / r, alpha / sqrt(r) with use_rslora.  A refused adapter leaves the slot as it
+        was."""
+        lib = _lib()
+        arrays = {name: np.ascontiguousarray(np.asarray(t), dtype=np.float16) for name, t in tensors.items()}
+        for name, a in arrays.items():  # before anything is staged
+            if a.ndim != 2 or a.size == 0:
+                raise ValueError(f'lora_load: {name} is not a matrix (shape {a.shape})')
+        for name, a in arrays.items():
+            dims = (ctypes.c_int64 * 2)(*a.shape)
+            _check(lib.tllm_session_lora_set_tensor(self._h, slot, name.encode(), capi.HALF, dims, 2, a.ctypes.data, 0),
+                   f'lora_set_tensor({name})')
+        _check(lib.tllm_session_lora_commit(self._h, slot, float(alpha), 1 if use_rslora else 0), 'lora_commit')
+
+    def graph_captures(self) -> int:
+        """step graphs captured since the session was created (one per capture, none per replay)"""
+        return int(_lib().tllm_session_graph_captures(self._h))
+
+    def lora_clear(self, slot: int):
+        _check(_lib().tllm_session_lora_clear(self._h, slot), 'lora_clear')
+
+    def lora_select(self, slots):
+        """slots: one adapter slot per sequence, -1 = none; after setup(), holds until changed (all -1 after every setup).  Like
+        lora_load() and lora_clear() it waits for the device to be idle first: work in flight on any stream finishes under the old
+        selection."""
+        sl = self._i32(slots)
+        assert sl.shape == (self.batch, )
+        _check(_lib().tllm_session_lora_select(self._h, sl.ctypes.data), 'lora_select')
 
     def set_sampling(self, config: Optional[Dict] = None, **fields):
         """Top-k / top-p sampling for the requests that follow (after setup(), before context() / generate(); beam_width 1):
