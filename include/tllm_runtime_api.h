@@ -40,6 +40,10 @@ typedef struct tllm_session* tllm_session_t;
  *   paged_kv_cache (0; 1: every layer's cache is a pool of [Hr, tokens_per_block, Dh] blocks reached through a per-sequence
  *   table of block pointers - K/kvCacheUtils.h:34-112, PY/runtime/kv_cache_manager.py; the table is filled at setup),
  *   tokens_per_block (64; a power of two),
+ *   paged_append (0; 1, with paged_kv_cache = 1 only - refused by name otherwise: tllm_session_append, _append_ragged, their
+ *   _generate forms, tllm_session_verify, _verify_sampled and both tllm_session_generate_lookup loops, LoRA included, serve the
+ *   paged cache through its table, bit for bit what the linear session computes; without the key a paged session refuses them
+ *   as before.  A key of the runtime, not of the engine header: tllm_session_load_engine_keys adds it to a loaded engine),
  *   debug_taps (0; 1: keep per-layer intermediates of the generation step for tllm_session_get_tap),
  *   gemm_tactics (optional; the table tllm_gemm_tactics_export wrote, as the builder stores it in the engine).
  * Returns NULL on error (tllm_last_error()). */
@@ -58,6 +62,10 @@ int32_t tllm_session_finalize(tllm_session_t s);
 /* Parse a serialized engine (format written by tensorrt_llm.Builder.build_engine: "TLLMENG1" header, config
  * text, tensor table, data) = tllm_engine_verify + create + set_tensor(location 0) + finalize. */
 tllm_session_t tllm_session_load_engine(const void* engine, size_t nbytes);
+/* The same with session keys of the runtime behind the header's: runtime_keys is "key=value" lines (NULL or empty: none).  Only
+ * the keys that are not the engine's to decide are taken - paged_append - and any other line is refused by name, so nothing the
+ * engine was built and verified with can be overridden here. */
+tllm_session_t tllm_session_load_engine_keys(const void* engine, size_t nbytes, const char* runtime_keys);
 
 /* The check tllm_session_load_engine applies before it accepts an engine, on its own (host only, no GPU needed): the traced
  * network the engine carries (`network_json`: plugin nodes in order, their inputs, fields and the weights feeding them, the
@@ -180,8 +188,10 @@ int32_t tllm_session_force_tokens(tllm_session_t s, const int32_t* ids, tllm_str
  * only).  The pass is the prefill schedule on B * n rows with the append attention in place of the context attention.
  * Reads sequence_length back, so it synchronises the stream.  Refused, with nothing enqueued: before setup; before any context
  * (every sequence_length must be >= max_input_len); n < 1, n > max_input_len (the activation buffers are sized for that) or
- * sequence_length[b] + n > max_seq_len; beam_width > 1, the paged cache, tensor parallel > 1; a token id outside [0, vocab_size).
- * Packed-input sessions are accepted (the appended rows are dense either way).  A different n per sequence: tllm_session_append_ragged.  The
+ * sequence_length[b] + n > max_seq_len; beam_width > 1, tensor parallel > 1, the paged cache without the session key paged_append;
+ * a token id outside [0, vocab_size).
+ * Packed-input sessions are accepted (the appended rows are dense either way), and paged sessions with paged_append = 1 (the
+ * attention reaches the cache through the block table; every result is the linear session's).  A different n per sequence: tllm_session_append_ragged.  The
  * scoring of the appended tokens is tllm_session_verify's. */
 int32_t tllm_session_append(tllm_session_t s, const int32_t* ids, int32_t n, tllm_stream_t stream);
 /* tllm_session_append, then up to max_new_tokens generated tokens as tllm_session_generate produces them (the first by the
@@ -237,7 +247,7 @@ int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* m
  * sequence_length[b] + n + 1 > max_seq_len; a sampling configuration that is not plain arg-max (speculative sampling is not built
  * into this entry: tllm_session_verify_sampled below takes it).
  * Not built: a draft model with a soft distribution q and the rejection rule's residual distribution (speculative sampling is
- * by exact match with the draw, below), a different n per sequence, beam / paged / tensor-parallel sessions, a verify pass in
+ * by exact match with the draw, below), a different n per sequence, beam / tensor-parallel sessions (a paged session: key paged_append), a verify pass in
  * the one-launch form of the generation step. */
 #define TLLM_VERIFY_MAX_TOKENS 32
 int32_t tllm_session_verify(tllm_session_t s, const int32_t* ids, int32_t n, int32_t* accepted, float* log_probs,
@@ -729,7 +739,7 @@ int32_t tllm_attention_context_layout(const tllm_attention_params_t* p, int32_t 
  * enter un-quantised.  sequence_length is NOT advanced (the session's advance launch does that).  Two launches: RoPE + cache
  * write, then the attention.
  *   qkv    fp16 [B, n, (H + 2 Hkv) * Dh], rows [ q | k | v ]; q and k are rewritten in place with RoPE applied;
- *   cache  [B, 2, Hkv, Smax, Dh] fp16 / int8 / fp8 E4M3 (linear only);   out  fp16 [B, n, H * Dh].
+ *   cache  [B, 2, Hkv, Smax, Dh] fp16 / int8 / fp8 E4M3 (the paged cache: tllm_attention_append_paged);   out  fp16 [B, n, H * Dh].
  * max_past is the caller's promise max_past >= every sequence_length[b]: max_past + n > max_seq_len is refused with nothing
  * launched; on the device every cache store is guarded by slot < max_seq_len and every load index is clamped all the same.
  * append_kernel: TLLM_APPEND_ATTN_WAVE (one wave per query: every n, head sizes 32 / 64 / 128 / 256) or TLLM_APPEND_ATTN_MFMA (64
@@ -768,6 +778,21 @@ int32_t tllm_attention_append(const tllm_attention_append_params_t* p, tllm_stre
  * as a query, key or value - NaN there reaches nothing - and their rows of out are written as zeros. */
 int32_t tllm_attention_append_ragged(const tllm_attention_append_params_t* p, const int32_t* n_per_seq, int32_t max_end,
     tllm_stream_t stream);
+/* tllm_attention_append (n_per_seq NULL; max_end ignored) or tllm_attention_append_ragged (n_per_seq set) on the paged cache:
+ * p->kv_cache is the pool, block_pointers a DEVICE table int64 [batch, 2, max_blocks_per_seq] - row [b][0] the K blocks of sequence
+ * b, row [b][1] its V blocks - of pointers to blocks laid out [Hkv, tokens_per_block, Dh]; slot t of a sequence is row
+ * t % tokens_per_block of its block t / tokens_per_block, and p->max_seq_len stays the capacity Smax (masked_tokens is [B, Smax]).
+ * Everything else is the linear entry's, and so is every result: out, the rewritten qkv and the rows the pool holds behind the
+ * table are bit for bit what the linear launch leaves on the same logical cache.
+ * A table entry of 0 is a block that is not mapped (a table grown on demand, KVCacheManager.extend): the store of a slot in it is
+ * skipped, never aimed at 0 + offset - mapping the blocks of the slots [p_b, p_b + n_b) before the call is the caller's part - and
+ * no load address is formed from it (such a load is pointed at the pool; slots >= p_b never enter a product).  Blocks may be
+ * shared between sequences for slots below both their p_b.
+ * Refused, with nothing launched: what the linear entries refuse; block_pointers NULL; a table without a pool; tokens_per_block
+ * that is not a power of two; max_blocks_per_seq * tokens_per_block < max_seq_len.  The kernel choice does not depend on the
+ * layout (tllm_attention_append_layout). */
+int32_t tllm_attention_append_paged(const tllm_attention_append_params_t* p, const int64_t* block_pointers, int32_t tokens_per_block,
+    int32_t max_blocks_per_seq, const int32_t* n_per_seq /* NULL = uniform */, int32_t max_end, tllm_stream_t stream);
 /* the attention kernel tllm_attention_append would run for p (n, head_size and append_kernel are read; no pointer is followed; no
  * GPU needed): TLLM_APPEND_ATTN_WAVE or _MFMA in *kind.  Non-zero: a forced append_kernel the launch cannot run. */
 int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* p, int32_t* kind);

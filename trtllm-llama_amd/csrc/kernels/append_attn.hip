@@ -13,6 +13,10 @@
 // clamped into [0, n], n stays the row stride of the QKV buffer and of `out`, and the rule above holds with n_b in place of n.  Rows
 // i >= n_b are padding: (a) leaves them alone (no RoPE, no cache store - their bits in the QKV buffer stay), (b) and (c) write
 // their `out` rows as zeros and never load them - not as a query, not as a key, not as a value - and (d) adds n_b.
+// The paged cache (block_pointers set; kernels.h): (a), (b) and (c) each have a paged instance - template parameter PG - that differs
+// from the linear one in address formation alone: slot t is row t % T of the sequence's block t / T, blocks [Hkv, T, Dh].  Same
+// arithmetic in the same order, so every result is the linear launch's bit for bit.  A table entry of 0 (a block not mapped): (a)
+// skips the store, no load address is ever formed from it, and the slots it stands for (>= p_b) never enter a product.
 // Numerics, both attention kernels: past slots are read as the decode kernel reads them - a one-byte element becomes the exact
 // fp16 value of its byte, kv_scale_quant_orig is applied once to the score and once to the sum of p.v; the appended tokens' own
 // k and v enter un-quantised from the QKV buffer (as the prefill does for the prompt and decode for the current token).  Scores,
@@ -70,7 +74,7 @@ __device__ __forceinline__ uint4 load_kv8(const char* ptr)
 }
 
 // ---- (a) grid (n, ceil(H / HG), B), 256 threads: DH / 8 lanes own the 8-element pieces of one head of one appended token
-template <int DH>
+template <int DH, bool PG>
 __global__ __launch_bounds__(256) void append_rope_kv_kernel(const AppendAttnParams p)
 {
     constexpr int LPR = DH / 8, HG = 256 / LPR;
@@ -152,6 +156,19 @@ __global__ __launch_bounds__(256) void append_rope_kv_kernel(const AppendAttnPar
     const int esz = p.kv_dtype == DT_HALF ? 2 : 1;
     char* kc = reinterpret_cast<char*>(p.kv_cache) + ((((int64_t) b * 2 + 0) * Hkv + h) * Smax + slot) * DH * esz + li * 8 * esz;
     char* vc = reinterpret_cast<char*>(p.kv_cache) + ((((int64_t) b * 2 + 1) * Hkv + h) * Smax + slot) * DH * esz + li * 8 * esz;
+    if constexpr (PG)
+    {
+        // the sequence's OWN block of slot p_b + i (slot < Smax <= max_blocks_per_seq * T: the index stays inside its row of the
+        // table).  An entry of 0 is a block the caller has not mapped: the store is skipped, never aimed at 0 + offset
+        const int T = p.tokens_per_block, lg = 31 - __builtin_clz(T);
+        const int64_t* row = p.block_pointers + (int64_t) b * 2 * p.max_blocks_per_seq + (slot >> lg);
+        const int64_t kblk = row[0], vblk = row[p.max_blocks_per_seq];
+        if (kblk == 0 || vblk == 0)
+            return;
+        const int64_t off = (((int64_t) h * T + (slot & (T - 1))) * DH + li * 8) * esz;
+        kc = reinterpret_cast<char*>(kblk) + off;
+        vc = reinterpret_cast<char*>(vblk) + off;
+    }
     if (p.kv_dtype == DT_INT8)
     {
         const float sc = p.kv_scale_orig_quant[0];
@@ -173,7 +190,7 @@ __global__ __launch_bounds__(256) void append_rope_kv_kernel(const AppendAttnPar
 
 // ---- (c) grid (ceil(n / 4), H, B); 4 waves, one query per wave; the lane groups of a wave take disjoint keys and share the
 // running maximum, so the merge at the end is a plain sum (the scheme of context_attn_kernel).
-template <int DH, int KV>
+template <int DH, int KV, bool PG>
 __global__ __launch_bounds__(256) void append_attn_wave_kernel(const AppendAttnParams p)
 {
     constexpr int LPR = DH / 8, RPW = 64 / LPR, NIT = 4, ESZ = KV == 0 ? 2 : 1;
@@ -200,6 +217,7 @@ __global__ __launch_bounds__(256) void append_attn_wave_kernel(const AppendAttnP
     const char* vc = reinterpret_cast<const char*>(p.kv_cache) + ((((int64_t) b * 2 + 1) * Hkv + kvh) * Smax) * DH * ESZ + li * 8 * ESZ;
     const int32_t* mask = p.masked_tokens ? p.masked_tokens + (int64_t) b * Smax : nullptr;
     const float s_qo = KV != 0 ? p.kv_scale_quant_orig[0] : 1.f;
+    const int pg_mask = PG ? p.tokens_per_block - 1 : 0, pg_lg = PG ? 31 - __builtin_clz(p.tokens_per_block) : 0;
 
     float m = -INFINITY, l = 0.f;
     float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -255,8 +273,23 @@ __global__ __launch_bounds__(256) void append_attn_wave_kernel(const AppendAttnP
             kk[i] = vv[i] = make_uint4(0, 0, 0, 0);
             if (ok[i])
             {
-                kk[i] = load_kv8<KV>(kc + (int64_t) t * DH * ESZ);
-                vv[i] = load_kv8<KV>(vc + (int64_t) t * DH * ESZ);
+                if constexpr (PG)
+                {
+                    // one look at the table per key row (the LPR lanes of a row read the same two entries, and the rows of a block
+                    // find them in the vector cache); t < p_b, so the block is one the sequence holds - and should its entry be 0
+                    // all the same, the load goes to the pool, not to 0 + offset.  (Looking the NIT rows of the next pass up one
+                    // pass ahead, unconditionally, was tried and was slower: profiles/append_paged.txt)
+                    const int64_t* row = p.block_pointers + (int64_t) b * 2 * p.max_blocks_per_seq + (t >> pg_lg);
+                    const int64_t kblk = row[0], vblk = row[p.max_blocks_per_seq];
+                    const int64_t off = (((int64_t) kvh * p.tokens_per_block + (t & pg_mask)) * DH + li * 8) * ESZ;
+                    kk[i] = load_kv8<KV>((kblk ? reinterpret_cast<const char*>(kblk) : reinterpret_cast<const char*>(p.kv_cache)) + off);
+                    vv[i] = load_kv8<KV>((vblk ? reinterpret_cast<const char*>(vblk) : reinterpret_cast<const char*>(p.kv_cache)) + off);
+                }
+                else
+                {
+                    kk[i] = load_kv8<KV>(kc + (int64_t) t * DH * ESZ);
+                    vv[i] = load_kv8<KV>(vc + (int64_t) t * DH * ESZ);
+                }
             }
         }
         block(kk, vv, ok, s_qo * p.inv_sqrt_dh, s_qo);
@@ -320,7 +353,13 @@ __global__ __launch_bounds__(256) void append_attn_wave_kernel(const AppendAttnP
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
-template <int DH, int KV>
+// Paged instances (PG): the table is looked up once per 64-key block, not once per row - a block of keys spans NE = max(64 / T, 1)
+// cache blocks (T = 128: half of one).  Threads 0 .. 127 hold the K (0 .. 63) and V (64 .. 127) entries of the NEXT past block in
+// a register, requested while the current block computes, and publish them in sBlk ahead of the barrier that opens the block's
+// loads; a row then takes its block's address from LDS.  An entry of 0 is published as the pool's own address (a select, never
+// 0 + offset), and the K rows, which are loaded whether their key counts or not, take the slot min(key, p_b - 1): a slot below
+// p_b, which the sequence holds (a past block exists only where p_b >= 1).  What such a row holds is masked as before.
+template <int DH, int KV, bool PG>
 __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnParams p)
 {
     constexpr int ESZ = KV == 0 ? 2 : 1;
@@ -377,6 +416,23 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
             oacc[dt][i] = 0.f;
     float m = -INFINITY, l = 0.f;
     const int npast = (pb + 63) >> 6, nblk = npast + qb + 1;
+    // paged: the entry thread tid < 128 fetches for the 64-key block at slot k0 - entry e = tid & 63 of the K (tid < 64) or V row,
+    // clamped to the block of slot p_b - 1; entries e >= NE are never read
+    int64_t* sBlk = nullptr;
+    int64_t pg_next = 0;
+    const int pg_T = PG ? p.tokens_per_block : 1, pg_lg = PG ? 31 - __builtin_clz(pg_T) : 0;
+    auto pg_entry = [&](int k0) -> int64_t {
+        const int j = min((k0 >> pg_lg) + (tid & 63), max(pb - 1, 0) >> pg_lg);
+        const int64_t e = p.block_pointers[((int64_t) b * 2 + (tid >> 6)) * p.max_blocks_per_seq + j];
+        return e ? e : reinterpret_cast<int64_t>(p.kv_cache);
+    };
+    if constexpr (PG)
+    {
+        __shared__ int64_t blk_lds[128];
+        sBlk = blk_lds;
+        if (tid < 128 && npast > 0)
+            pg_next = pg_entry(0);
+    }
     for (int blk = 0; blk < nblk; ++blk)
     {
         const bool past = blk < npast; // uniform
@@ -387,7 +443,17 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
             for (int dt = 0; dt < DT; ++dt)
                 oacc[dt] *= s_qo;
         }
+        if constexpr (PG)
+        {
+            if (past && tid < 128) // (the loads of the previous block, the last readers of sBlk, ended before its second barrier)
+                sBlk[tid] = pg_next;
+        }
         __syncthreads(); // the previous block's fragment reads are done
+        if constexpr (PG)
+        {
+            if (tid < 128 && blk + 1 < npast)
+                pg_next = pg_entry(k0 + 64);
+        }
         {
             // K rows: LPR consecutive lanes fetch one row
             const int c = tid % LPR;
@@ -397,7 +463,16 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
             {
                 const int key = k0 + ps * KPP + tid / LPR;
                 if (past)
-                    kr[ps] = load_kv8<KV>(kc + ((int64_t) min(key, Smax - 1) * DH + c * 8) * ESZ);
+                {
+                    if constexpr (PG)
+                    {
+                        const int kq = min(key, pb - 1); // >= k0: a past block starts below p_b
+                        const char* blkp = reinterpret_cast<const char*>(sBlk[(kq >> pg_lg) - (k0 >> pg_lg)]);
+                        kr[ps] = load_kv8<KV>(blkp + (((int64_t) kvh * pg_T + (kq & (pg_T - 1))) * DH + c * 8) * ESZ);
+                    }
+                    else
+                        kr[ps] = load_kv8<KV>(kc + ((int64_t) min(key, Smax - 1) * DH + c * 8) * ESZ);
+                }
                 else
                     kr[ps] = *reinterpret_cast<const uint4*>(kb + (int64_t) min(key, nb - 1) * rs + c * 8);
             }
@@ -416,7 +491,15 @@ __global__ __launch_bounds__(256) void append_attn_mfma_kernel(const AppendAttnP
             {
                 const int cc = (tid >> 6) + 4 * ps;
                 vr[ps] = make_uint4(0, 0, 0, 0);
-                if (ok)
+                if constexpr (PG)
+                {
+                    if (ok && past) // key < p_b: its entry is among the NE published ones
+                        vr[ps] = load_kv8<KV>(reinterpret_cast<const char*>(sBlk[64 + (key >> pg_lg) - (k0 >> pg_lg)])
+                            + (((int64_t) kvh * pg_T + (key & (pg_T - 1))) * DH + cc * 8) * ESZ);
+                    else if (ok)
+                        vr[ps] = *reinterpret_cast<const uint4*>(vb + (int64_t) key * rs + cc * 8);
+                }
+                else if (ok)
                     vr[ps] = past ? load_kv8<KV>(vc + ((int64_t) key * DH + cc * 8) * ESZ)
                                   : *reinterpret_cast<const uint4*>(vb + (int64_t) key * rs + cc * 8);
             }
@@ -545,11 +628,11 @@ __global__ __launch_bounds__(256) void append_advance_kernel(int32_t* sequence_l
     }
 }
 
-template <int DH>
+template <int DH, bool PG>
 int launch_dh(const AppendAttnParams& p, int kind, hipStream_t stream)
 {
     constexpr int HG = 256 / (DH / 8);
-    hipLaunchKernelGGL(append_rope_kv_kernel<DH>, dim3(p.n, (p.num_heads + HG - 1) / HG, p.batch), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((append_rope_kv_kernel<DH, PG>), dim3(p.n, (p.num_heads + HG - 1) / HG, p.batch), dim3(256), 0, stream, p);
     if (launch_util::check_launch("append attention (RoPE, cache write)"))
         return -1;
     const int kv = kv_kind(p.kv_dtype);
@@ -559,22 +642,22 @@ int launch_dh(const AppendAttnParams& p, int kind, hipStream_t stream)
         {
             const dim3 grid(p.num_heads, (p.n + 63) / 64, p.batch);
             if (kv == 0)
-                hipLaunchKernelGGL((append_attn_mfma_kernel<DH, 0>), grid, dim3(256), 0, stream, p);
+                hipLaunchKernelGGL((append_attn_mfma_kernel<DH, 0, PG>), grid, dim3(256), 0, stream, p);
             else if (kv == 1)
-                hipLaunchKernelGGL((append_attn_mfma_kernel<DH, 1>), grid, dim3(256), 0, stream, p);
+                hipLaunchKernelGGL((append_attn_mfma_kernel<DH, 1, PG>), grid, dim3(256), 0, stream, p);
             else
-                hipLaunchKernelGGL((append_attn_mfma_kernel<DH, 2>), grid, dim3(256), 0, stream, p);
+                hipLaunchKernelGGL((append_attn_mfma_kernel<DH, 2, PG>), grid, dim3(256), 0, stream, p);
         }
     }
     else
     {
         const dim3 grid((p.n + 3) / 4, p.num_heads, p.batch);
         if (kv == 0)
-            hipLaunchKernelGGL((append_attn_wave_kernel<DH, 0>), grid, dim3(256), 0, stream, p);
+            hipLaunchKernelGGL((append_attn_wave_kernel<DH, 0, PG>), grid, dim3(256), 0, stream, p);
         else if (kv == 1)
-            hipLaunchKernelGGL((append_attn_wave_kernel<DH, 1>), grid, dim3(256), 0, stream, p);
+            hipLaunchKernelGGL((append_attn_wave_kernel<DH, 1, PG>), grid, dim3(256), 0, stream, p);
         else
-            hipLaunchKernelGGL((append_attn_wave_kernel<DH, 2>), grid, dim3(256), 0, stream, p);
+            hipLaunchKernelGGL((append_attn_wave_kernel<DH, 2, PG>), grid, dim3(256), 0, stream, p);
     }
     return launch_util::check_launch("append attention");
 }
@@ -633,6 +716,21 @@ int launch_append_attention(const AppendAttnParams& pin, hipStream_t stream)
     }
     if (launch_util::check_kv_dtype("append attention", p.kv_dtype, p.kv_scale_orig_quant && p.kv_scale_quant_orig))
         return -1;
+    if (p.block_pointers)
+    {
+        const int t = p.tokens_per_block;
+        if (t < 1 || (t & (t - 1)) || (int64_t) p.max_blocks_per_seq * t < p.max_seq_len)
+        {
+            set_error("append attention: paged KV cache needs tokens_per_block a power of two and max_blocks_per_seq * "
+                      "tokens_per_block >= max_seq_len (got %d x %d for %d)", p.max_blocks_per_seq, t, p.max_seq_len);
+            return -1;
+        }
+        if (!p.kv_cache)
+        {
+            set_error("append attention: paged KV cache needs the pool in kv_cache (the block table alone is not enough)");
+            return -1;
+        }
+    }
     if (!p.qkv || !p.kv_cache || !p.out || !p.sequence_length || !p.input_lengths)
     {
         set_error("append attention: qkv, kv_cache, out, sequence_length and input_lengths must be set");
@@ -666,12 +764,22 @@ int launch_append_attention(const AppendAttnParams& pin, hipStream_t stream)
         set_error("append attention: rotary_dim %d without a RoPE table", p.rotary_dim);
         return -1;
     }
+    if (p.block_pointers) // the paged instances
+    {
+        switch (p.head_size)
+        {
+        case 32: return launch_dh<32, true>(p, kind, stream);
+        case 64: return launch_dh<64, true>(p, kind, stream);
+        case 128: return launch_dh<128, true>(p, kind, stream);
+        default: return launch_dh<256, true>(p, kind, stream);
+        }
+    }
     switch (p.head_size)
     {
-    case 32: return launch_dh<32>(p, kind, stream);
-    case 64: return launch_dh<64>(p, kind, stream);
-    case 128: return launch_dh<128>(p, kind, stream);
-    default: return launch_dh<256>(p, kind, stream);
+    case 32: return launch_dh<32, false>(p, kind, stream);
+    case 64: return launch_dh<64, false>(p, kind, stream);
+    case 128: return launch_dh<128, false>(p, kind, stream);
+    default: return launch_dh<256, false>(p, kind, stream);
     }
 }
 

@@ -442,6 +442,13 @@ struct AppendAttnParams
     int32_t rope_table_len = 0;
     void* out = nullptr; // fp16 [B, n, H * Dh]
     int32_t kernel = 0;  // an AppendAttnKernel; a forced kind runs exactly that kernel or the launch is refused, never a substitute
+    // paged KV cache, as MmhaParams (the fields stand last: the linear instances read what they read before, where it was): a table
+    // int64 [batch, 2, max_blocks_per_seq] of pointers to blocks [Hkv, tokens_per_block, Dh], slot t = row t % tokens_per_block of
+    // block t / tokens_per_block, tokens_per_block a power of two; kv_cache is then the pool the blocks live in (where the load of
+    // a slot whose entry is 0 is pointed; such a slot is never stored to and never enters a product).  Same kernels as compile-time
+    // paged instances, same arithmetic in the same order: every result is the linear launch's on the same logical cache, bit for bit
+    const int64_t* block_pointers = nullptr;
+    int32_t tokens_per_block = 0, max_blocks_per_seq = 0;
 };
 // the attention kernel a launch runs (APPEND_ATTN_WAVE / _MFMA), 0 = refused (*refused says why)
 int append_attention_kernel(int32_t head_size, int32_t n, int32_t forced_kernel, const char** refused = nullptr);

@@ -269,9 +269,10 @@ int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* q, in
     return 0;
 }
 
-// n_per_seq null: tllm_attention_append (q->max_past holds); else tllm_attention_append_ragged (max_end in its place)
+// n_per_seq null: tllm_attention_append (q->max_past holds); else tllm_attention_append_ragged (max_end in its place).
+// block_pointers set: tllm_attention_append_paged (q->kv_cache is the pool)
 static int32_t attention_append(const char* who, const tllm_attention_append_params_t* q, const int32_t* n_per_seq, int32_t max_end,
-    tllm_stream_t stream)
+    tllm_stream_t stream, const int64_t* block_pointers = nullptr, int32_t tokens_per_block = 0, int32_t max_blocks_per_seq = 0)
 {
     if (!q || q->batch < 1 || q->n < 1 || q->num_heads < 1 || q->head_size < 1 || q->max_seq_len < 1)
     {
@@ -307,6 +308,9 @@ static int32_t attention_append(const char* who, const tllm_attention_append_par
     p.kv_scale_orig_quant = q->kv_scale_orig_quant;
     p.kv_scale_quant_orig = q->kv_scale_quant_orig;
     p.out = q->out;
+    p.block_pointers = block_pointers;
+    p.tokens_per_block = tokens_per_block;
+    p.max_blocks_per_seq = max_blocks_per_seq;
     if (p.rotary_dim > 0)
     {
         p.rope_table = tllm::plugins::rope_table(p.rotary_dim, p.max_seq_len, &p.rope_table_len);
@@ -330,6 +334,18 @@ int32_t tllm_attention_append_ragged(const tllm_attention_append_params_t* q, co
         return 1;
     }
     return attention_append("tllm_attention_append_ragged", q, n_per_seq, max_end, stream);
+}
+
+int32_t tllm_attention_append_paged(const tllm_attention_append_params_t* q, const int64_t* block_pointers, int32_t tokens_per_block,
+    int32_t max_blocks_per_seq, const int32_t* n_per_seq, int32_t max_end, tllm_stream_t stream)
+{
+    if (!block_pointers)
+    {
+        set_error("tllm_attention_append_paged: block_pointers is null");
+        return 1;
+    }
+    return attention_append("tllm_attention_append_paged", q, n_per_seq, max_end, stream, block_pointers, tokens_per_block,
+        max_blocks_per_seq);
 }
 
 static GemvParams gemv_params(const tllm_gemv_params_t* q)

@@ -347,7 +347,7 @@ static int32_t append_session_ok(tllm_session_t s, const char* who)
         set_error("%s: call tllm_session_setup first", who);
         return 1;
     }
-    if (s->beam > 1 || s->paged_kv || s->tp > 1)
+    if (s->beam > 1 || (s->paged_kv && !s->paged_append) || s->tp > 1) // (a paged session serves with the key paged_append)
     {
         set_error("%s: not built for beam search, the paged cache or tensor parallelism (beam_width %d, paged %d, tp %d)", who, s->beam,
             s->paged_kv ? 1 : 0, s->tp);

@@ -141,6 +141,10 @@ struct tllm_session
     // needs no host-side block allocation between steps
     bool paged_kv = false;
     int tokens_per_block = 64, max_blocks = 0;
+    // session key paged_append (a key of the runtime, not of the engine header): the append passes - append, verify, the lookup
+    // loops - serve the paged cache through the table (the paged instances of kernels/append_attn.hip).  Without it a paged
+    // session refuses them as it always did
+    bool paged_append = false;
     size_t kv_elems = 0; // elements of one layer's cache / pool
     bool force_comm = false; // tests: run the TP collectives on a 1-rank communicator too (RCCL inside the captured graph)
     // session key no_comm = 1: a rank's launches WITHOUT its collectives (all-reduces and the logits all-gather are skipped, nothing

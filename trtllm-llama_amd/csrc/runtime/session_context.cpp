@@ -290,6 +290,9 @@ int tllm_session::append_attention(const Layer& L, int n, int max_past, hipStrea
     }
     a.qkv = qkv;
     a.kv_cache = L.kv;
+    a.block_pointers = L.kv_table; // paged session (key paged_append): the pool and its table, as the prefill and the step take them
+    a.tokens_per_block = tokens_per_block;
+    a.max_blocks_per_seq = max_blocks;
     a.sequence_length = seq_len;
     a.input_lengths = in_len;
     a.masked_tokens = masked;

@@ -183,6 +183,12 @@ tllm_session_t tllm_session_create(const char* config_text)
         set_error("tllm_session_create: tokens_per_block must be a power of two (got %d)", s->tokens_per_block);
         return nullptr;
     }
+    s->paged_append = geti("paged_append", 0) != 0;
+    if (s->paged_append && !s->paged_kv)
+    {
+        set_error("tllm_session_create: paged_append = 1 needs paged_kv_cache = 1 (the append passes of a linear cache need no key)");
+        return nullptr;
+    }
     if (kv.count("rms_norm_eps"))
         s->eps = (float) atof(kv["rms_norm_eps"].c_str());
     if (kv.count("weight_only_precision"))
@@ -534,11 +540,38 @@ int32_t tllm_engine_verify(const void* engine, size_t nbytes)
 
 tllm_session_t tllm_session_load_engine(const void* engine, size_t nbytes)
 {
+    return tllm_session_load_engine_keys(engine, nbytes, nullptr);
+}
+
+tllm_session_t tllm_session_load_engine_keys(const void* engine, size_t nbytes, const char* runtime_keys)
+{
     std::string cfg;
     std::vector<EngineEntry> ents;
     size_t data0 = 0;
     if (parse_engine(engine, nbytes, cfg, ents, data0))
         return nullptr;
+    if (runtime_keys)
+    {
+        // key=value lines behind the header's: only the keys that are the runtime's to set
+        std::istringstream in(runtime_keys);
+        std::string line;
+        while (std::getline(in, line))
+        {
+            const size_t a = line.find_first_not_of(" \t\r"), eq = line.find('=');
+            if (a == std::string::npos)
+                continue;
+            const size_t e = eq == std::string::npos ? std::string::npos : line.find_last_not_of(" \t\r", eq - 1);
+            const std::string key = eq == std::string::npos || eq == a ? std::string() : line.substr(a, e - a + 1);
+            if (key != "paged_append")
+            {
+                set_error("tllm_session_load_engine_keys: '%s' is not a runtime key (paged_append); the engine header holds the rest",
+                    line.c_str());
+                return nullptr;
+            }
+            cfg += "\n" + line;
+        }
+        cfg += "\n";
+    }
     tllm_session_t s = tllm_session_create(cfg.c_str());
     if (!s)
         return nullptr;

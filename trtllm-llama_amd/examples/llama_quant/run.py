@@ -77,6 +77,8 @@ def load_session(engine_dir):
                                gpt_attention_plugin=bool(config['plugin_config']['gpt_attention_plugin']),
                                multi_query_mode=bc.get('multi_query_mode', False),
                                remove_input_padding=config['plugin_config']['remove_input_padding'],
+                               paged_kv_cache=bool(config['plugin_config'].get('paged_kv_cache', False)),
+                               tokens_per_block=int(config['plugin_config'].get('tokens_per_block', 64)),
                                num_kv_heads=bc.get('num_kv_heads', bc['num_heads']) // world_size,
                                lora_max_rank=int(bc.get('lora_max_rank') or 0), lora_target_modules=bc.get('lora_target_modules'))
     path = Path(engine_dir) / get_engine_name('llama', dtype, world_size, runtime_rank)

@@ -67,9 +67,15 @@ class GenerationSession(object):
         if mapping.tp_size > 1:
             from ..parallel import ensure_tp_communicator
             ensure_tp_communicator(mapping)
-        self.runtime = NativeSession(engine=bytes(engine_buffer))
+        self.runtime = NativeSession(engine=bytes(engine_buffer), runtime_keys=self._runtime_keys(model_config))
         self.runtime.vocab = model_config.vocab_size
         self.batch_size = self.max_input_length = self.max_new_tokens = 0
+
+    @staticmethod
+    def _runtime_keys(model_config: ModelConfig) -> dict:
+        """Session keys that belong to the runtime and not to the engine header.  paged_append: a paged engine serves append(),
+        verify() and decode_lookup() on its block table (the key is refused on a linear cache, so only a paged engine gets it)."""
+        return dict(paged_append=1) if model_config.paged_kv_cache else {}
 
     @property
     def vocab_size(self):
@@ -222,8 +228,8 @@ class GenerationSession(object):
         lens = None
         if input_lengths is not None:
             lens = input_lengths.cpu().numpy() if hasattr(input_lengths, 'cpu') else np.asarray(input_lengths)
-        if self.mapping.tp_size > 1 or self._model_config.paged_kv_cache:
-            raise NotImplementedError('append() is not built for tensor parallelism or the paged KV cache')
+        if self.mapping.tp_size > 1:
+            raise NotImplementedError('append() is not built for tensor parallelism')
         self._check_append_args(ids, self.batch_size, self.max_input_length, self.vocab_size, getattr(self, 'beam_width', 1), lens)
         if lens is None:
             return ids.astype(np.int32)

@@ -146,6 +146,29 @@ class KVCacheManager(object):
             keep_len.append(n + 1)
         self.sequences, self.lens = keep_seq, keep_len
 
+    def extend(self, num_tokens: List[int]):
+        """The multi-token form of step() for an append (tllm_attention_append_paged): sequence i grows by num_tokens[i] >= 0
+        tokens and gets the blocks that its lens[i] + num_tokens[i] tokens need, ceil((lens[i] + num_tokens[i]) /
+        tokens_per_block) - no block is taken that it already holds, none is released, nobody finishes.  All or nothing: when the
+        pool cannot serve every sequence the call raises and changes nothing.  It maps what the appended tokens occupy, not the
+        slot behind them: count the pending token in (one more) when a generation step follows."""
+        if len(num_tokens) != len(self.sequences):
+            raise ValueError(f'num_tokens: one entry per live sequence ({len(self.sequences)}), got {len(num_tokens)}')
+        if any(int(n) < 0 for n in num_tokens):
+            raise ValueError('num_tokens must not be negative')
+        bm, T = self.blocks_manager, self.tokens_per_block
+        need = [max(-(-(have + int(n)) // T) - bm.get_number_blocks(seq), 0)
+                for seq, have, n in zip(self.sequences, self.lens, num_tokens)]
+        for seq, k in zip(self.sequences, need):
+            if bm.get_number_blocks(seq) + k > bm.max_blocks_per_seq:
+                raise RuntimeError(f'sequence {seq.get_seq_idx()} would hold more than max_blocks_per_seq = {bm.max_blocks_per_seq} blocks')
+        if sum(need) * self.beam_width > bm.num_free_blocks():
+            raise RuntimeError("Can't allocate new block for KV cache")
+        for seq, k in zip(self.sequences, need):
+            for _ in range(k):
+                bm.allocate(seq)
+        self.lens = [have + int(n) for have, n in zip(self.lens, num_tokens)]
+
     def get_pointer_arrays(self, device='cuda'):
         """One table per pool (layer), on `device`, viewed as int32 [.., 2 * max_blocks_per_seq] - the form the plugin
         input takes (TensorRT had no int64 tensors; the plugin reinterprets the pairs)."""

@@ -31,6 +31,8 @@ def _lib():
     lib.tllm_session_finalize.restype = c.c_int32
     lib.tllm_session_load_engine.argtypes = [c.c_void_p, c.c_size_t]
     lib.tllm_session_load_engine.restype = c.c_void_p
+    lib.tllm_session_load_engine_keys.argtypes = [c.c_void_p, c.c_size_t, c.c_char_p]
+    lib.tllm_session_load_engine_keys.restype = c.c_void_p
     lib.tllm_session_setup.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32]
     lib.tllm_session_setup.restype = c.c_int32
     lib.tllm_session_setup_beam.argtypes = [c.c_void_p, c.c_int32, c.c_int32, c.c_int32, c.c_int32]
@@ -110,6 +112,9 @@ def _lib():
     lib.tllm_session_append_launches.restype = c.c_int32
     lib.tllm_attention_append.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p]
     lib.tllm_attention_append.restype = c.c_int32
+    lib.tllm_attention_append_paged.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p, c.c_int32, c.c_int32, c.c_void_p,
+                                                c.c_int32, c.c_void_p]
+    lib.tllm_attention_append_paged.restype = c.c_int32
     lib.tllm_attention_append_layout.argtypes = [c.POINTER(AttentionAppendParamsC), c.POINTER(c.c_int32)]
     lib.tllm_attention_append_layout.restype = c.c_int32
     lib.tllm_session_verify.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p]
@@ -285,6 +290,39 @@ def attention_append(qkv, kv_cache, out, sequence_length, input_lengths, *, num_
                'attention_append_ragged')
 
 
+def attention_append_paged(qkv, pool, block_pointers, out, sequence_length, input_lengths, *, tokens_per_block, max_seq_len,
+                           num_heads, num_kv_heads=0, head_size, max_input_len, max_past=None, masked_tokens=None, kv_cache_type=0,
+                           kv_scale_orig_quant=None, kv_scale_quant_orig=None, rotary_dim=None, neox=1, q_scaling=1.0,
+                           append_kernel=0, n_per_seq=None, max_end=None, stream: int = 0):
+    """tllm_attention_append_paged: attention_append on a paged cache.  pool is the memory the blocks [Hkv, tokens_per_block, Dh]
+    live in (any shape), block_pointers int64 [B, 2, max_blocks_per_seq] on the device (K row, V row per sequence; 0 = a block that
+    is not mapped), max_seq_len the capacity Smax the linear cache would have (masked_tokens is [B, Smax]).  Everything else, the
+    ragged form (n_per_seq with max_end) included, as attention_append takes it."""
+    B, n = qkv.shape[0], qkv.shape[1]
+    if (n_per_seq is None) != (max_end is None):
+        raise ValueError('n_per_seq and max_end go together')
+    if n_per_seq is None and max_past is None:
+        raise ValueError('max_past must be given (or n_per_seq with max_end)')
+    for t in (qkv, pool, block_pointers, out, sequence_length, input_lengths, masked_tokens, kv_scale_orig_quant,
+              kv_scale_quant_orig, n_per_seq):
+        assert t is None or (t.is_cuda and t.is_contiguous())
+    assert str(block_pointers.dtype) == 'torch.int64' and block_pointers.dim() == 3 and tuple(block_pointers.shape[:2]) == (B, 2), \
+        'block_pointers must be int64 [B, 2, max_blocks_per_seq]'
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    p = AttentionAppendParamsC(batch=B, n=n, num_heads=num_heads, num_kv_heads=num_kv_heads, head_size=head_size,
+                               rotary_dim=head_size if rotary_dim is None else rotary_dim, neox=neox, q_scaling=q_scaling,
+                               kv_cache_type=kv_cache_type, max_seq_len=int(max_seq_len), max_input_len=max_input_len,
+                               max_past=max_past or 0, append_kernel=append_kernel, qkv=ptr(qkv), kv_cache=ptr(pool),
+                               sequence_length=ptr(sequence_length), input_lengths=ptr(input_lengths),
+                               masked_tokens=ptr(masked_tokens), kv_scale_orig_quant=ptr(kv_scale_orig_quant),
+                               kv_scale_quant_orig=ptr(kv_scale_quant_orig), out=ptr(out))
+    if n_per_seq is not None:
+        assert str(n_per_seq.dtype) == 'torch.int32' and tuple(n_per_seq.shape) == (B, ), 'n_per_seq must be int32 [B]'
+    _check(_lib().tllm_attention_append_paged(ctypes.byref(p), block_pointers.data_ptr(), int(tokens_per_block),
+                                              int(block_pointers.shape[2]), ptr(n_per_seq), int(max_end or 0), stream),
+           'attention_append_paged')
+
+
 def _sampling_config(top_k=1, top_p=0.0, temperature=1.0, repetition_penalty=1.0, presence_penalty=0.0, min_length=1,
                      random_seed=0) -> SamplingConfigC:
     return SamplingConfigC(int(top_k), float(top_p), float(temperature), float(repetition_penalty), float(presence_penalty),
@@ -373,12 +411,18 @@ def _check(rc: int, what: str):
 class NativeSession:
     """Thin owner of a tllm_session_t."""
 
-    def __init__(self, config: Optional[Dict] = None, engine: Optional[bytes] = None):
+    def __init__(self, config: Optional[Dict] = None, engine: Optional[bytes] = None, runtime_keys: Optional[Dict] = None):
+        """config: the session keys; or engine: a serialized engine, whose header holds them - then runtime_keys adds the keys
+        that belong to the runtime and not to the engine (paged_append; tllm_session_load_engine_keys refuses every other)."""
         lib = _lib()
         self._keep = []  # torch tensors whose device memory the session references
         if engine is not None:
             buf = (ctypes.c_char * len(engine)).from_buffer_copy(engine)
-            self._h = lib.tllm_session_load_engine(buf, len(engine))
+            if runtime_keys:
+                text = '\n'.join(f'{k}={v}' for k, v in runtime_keys.items())
+                self._h = lib.tllm_session_load_engine_keys(buf, len(engine), text.encode())
+            else:
+                self._h = lib.tllm_session_load_engine(buf, len(engine))
         else:
             text = '\n'.join(f'{k}={v}' for k, v in config.items())
             self._h = lib.tllm_session_create(text.encode())
@@ -588,7 +632,8 @@ class NativeSession:
     def append(self, ids, lengths=None, stream: int = 0):
         """Append ids [batch, n] to the live cache in one prefill pass (tllm_session_append): the parallel form of n times
         force_tokens(ids[:, i]); step(1).  Token 0 replaces the pending token (pass it as ids[:, 0] to keep it).  Afterwards
-        logits() holds the last appended token's logits and a new pending token is chosen.  beam_width 1, linear cache, tp 1.
+        logits() holds the last appended token's logits and a new pending token is chosen.  beam_width 1, tp 1; a paged cache with
+        the session key paged_append = 1.
         lengths [batch] (tllm_session_append_ragged): sequence b appends ids[b, :lengths[b]] alone, 1 <= lengths[b] <= n; what
         stands behind them in the row is never read."""
         ids = self._i32(ids)
@@ -625,6 +670,7 @@ class NativeSession:
         return int(w.value), int(m.value)
 
     attention_append = staticmethod(attention_append)
+    attention_append_paged = staticmethod(attention_append_paged)
     spec_accept = staticmethod(spec_accept)
     prompt_lookup = staticmethod(prompt_lookup)
     spec_sample_rows = staticmethod(spec_sample_rows)
