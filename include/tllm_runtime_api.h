@@ -797,6 +797,60 @@ int32_t tllm_attention_append_paged(const tllm_attention_append_params_t* p, con
  * GPU needed): TLLM_APPEND_ATTN_WAVE or _MFMA in *kind.  Non-zero: a forced append_kernel the launch cannot run. */
 int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* p, int32_t* kind);
 
+/* ------------------------------------------------------------------------------------------------
+ * Kernel-level entries of the row-wise and element-wise kernels (kernels/pointwise.hip), so that tests reach every kernel without
+ * a plugin or a session.  tllm_rmsnorm_params_t restates kernels.h RmsnormParams field for field (every field not needed is
+ * 0 / NULL):
+ *   y = f16(f16(x' * rsqrt(mean(x'^2) + eps)) * gamma), x' = x or f16(x + residual) (then written to sum_out, which is required);
+ *   layernorm != 0: y = f16((x' - mean) * rstd * gamma + beta), variance as E[x^2] - mean^2 (use_diff_of_squares) or E[(x - mean)^2];
+ *   q, if set: sat(rni(y * static_scale[0])), or with dyn_scale_out sat(rni(y * (127 / amax))) and dyn_scale_out[m] = amax / 127,
+ *   amax = max(|y[m, :]|, f16(1e-6)).  y may be NULL when only q is wanted.
+ * kernel: 0 = the launcher's choice, 1 = the scalar LDS kernel (any N, any fp16 alignment), 2 = the 16-byte LDS kernel (N % 8 == 0,
+ * 16-byte aligned fp16 pointers, 8-byte aligned q), 3 = the register kernel (what 2 needs, RMSNorm only, 8 <= N <= 8192).  Both LDS
+ * kernels hold the row in 128 + 2 N <= 64 KiB.  A forced kernel whose precondition does not hold returns -1 with
+ * tllm_last_error() set and nothing launched - never a substitute.  0 on success (an empty problem included). */
+typedef struct
+{
+    int32_t M, N;
+    const void* x;
+    const void* residual;
+    void* sum_out;
+    const void* gamma;
+    float eps;
+    void* y;
+    int8_t* q;
+    const float* static_scale;
+    float* dyn_scale_out;
+    int32_t layernorm, use_diff_of_squares;
+    const void* beta;
+} tllm_rmsnorm_params_t;
+int32_t tllm_rmsnorm(const tllm_rmsnorm_params_t* p, int32_t kernel, tllm_stream_t stream);
+/* the kernel tllm_rmsnorm(p, 0, ..) would run (the launcher's own rule; no pointer is followed, no GPU needed): 1, 2, or
+ * 3 + 8 * NV for the register kernel with NV = 1 (N <= 2048), 2 (<= 4096) or 4 (<= 8192) vectors per thread; 0 for an empty problem
+ * (M <= 0 or N <= 0: nothing is launched); -1 with tllm_last_error() set where the launch is refused. */
+int32_t tllm_rmsnorm_kernel(const tllm_rmsnorm_params_t* p);
+/* The launchers of kernels.h as they are (fp16 operands; non-zero with tllm_last_error() set on failure):
+ *   swiglu y = f16(f16(silu(a)) * b); swiglu_quant q = sat(rni(swiglu * scale[0])); add y = f16(a + b) (y may be a);
+ *   quantize_tensor / quantize_per_token: src_dtype TLLM_HALF or TLLM_FLOAT;
+ *   embedding out[t] = table[ids[t]], an id outside [0, vocab) gives a zero row;
+ *   gather_last_token out[b] = hidden[b, clamp(last_token_ids[b] - 1, 0, seq - 1)]; gather_rows out[b] = hidden[rows[b]];
+ *   exclusive_scan_i32 cu[0] = 0, cu[i + 1] = cu[i] + lens[i] (cu holds n + 1);
+ *   fill_random: dtype TLLM_HALF / TLLM_FLOAT (U(-scale, scale)), TLLM_INT8 ([-127, 127]), TLLM_FP8 (finite E4M3 codes, |x| < 2). */
+int32_t tllm_swiglu(void* y, const void* a, const void* b, int64_t n, tllm_stream_t stream);
+int32_t tllm_swiglu_quant(int8_t* q, const void* a, const void* b, int64_t n, const float* scale, tllm_stream_t stream);
+int32_t tllm_add(void* y, const void* a, const void* b, int64_t n, tllm_stream_t stream);
+int32_t tllm_quantize_tensor(int8_t* dst, const void* src, int32_t src_dtype, int64_t size, const float* scale, tllm_stream_t stream);
+int32_t tllm_quantize_per_token(int8_t* dst, const void* src, int32_t src_dtype, int64_t rows, int64_t cols, float* scale_out,
+    tllm_stream_t stream);
+int32_t tllm_embedding(void* out, const int32_t* ids, const void* table, int64_t tokens, int32_t hidden, int32_t vocab,
+    tllm_stream_t stream);
+int32_t tllm_gather_last_token(void* out, const void* hidden, const int32_t* last_token_ids, int32_t batch, int32_t seq,
+    int32_t hidden_size, tllm_stream_t stream);
+int32_t tllm_gather_rows(void* out, const void* hidden, const int32_t* rows, int32_t batch, int32_t hidden_size, tllm_stream_t stream);
+int32_t tllm_exclusive_scan_i32(int32_t* cu, const int32_t* lens, int32_t n, tllm_stream_t stream);
+int32_t tllm_fill_i32(int32_t* dst, int32_t value, int64_t n, tllm_stream_t stream);
+int32_t tllm_fill_random(void* dst, int32_t dtype, int64_t n, uint32_t seed, float scale, tllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

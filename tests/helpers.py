@@ -88,3 +88,11 @@ class GemvParams(ctypes.Structure):
                 ('per_channel', ctypes.c_int32), ('per_token', ctypes.c_int32), ('gamma', ctypes.c_void_p), ('eps', ctypes.c_float),
                 ('act_scale', ctypes.c_void_p), ('dyn_scale_out', ctypes.c_void_p), ('x_pro_out', ctypes.c_void_p),
                 ('residual', ctypes.c_void_p), ('epi_scale', ctypes.c_void_p), ('y', ctypes.c_void_p), ('ldy', ctypes.c_int64)]
+
+
+class RmsnormParams(ctypes.Structure):
+    """tllm_rmsnorm_params_t (include/tllm_runtime_api.h): kernels.h RmsnormParams field for field"""
+    _fields_ = [('M', ctypes.c_int32), ('N', ctypes.c_int32), ('x', ctypes.c_void_p), ('residual', ctypes.c_void_p),
+                ('sum_out', ctypes.c_void_p), ('gamma', ctypes.c_void_p), ('eps', ctypes.c_float), ('y', ctypes.c_void_p),
+                ('q', ctypes.c_void_p), ('static_scale', ctypes.c_void_p), ('dyn_scale_out', ctypes.c_void_p),
+                ('layernorm', ctypes.c_int32), ('use_diff_of_squares', ctypes.c_int32), ('beta', ctypes.c_void_p)]

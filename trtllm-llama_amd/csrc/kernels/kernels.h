@@ -105,6 +105,8 @@ struct RmsnormParams
 {
     int32_t M = 0, N = 0;
     const void* x = nullptr;        // fp16 [M, N]
+    // residual / sum_out: nothing in the product sets them (neither the plugins nor the session) - both kernels implement them and
+    // tests/test_gpu_pointwise_instances.py (through tllm_rmsnorm) is what keeps them correct
     const void* residual = nullptr; // optional fp16 [M, N]: x <- x + residual first, sum written to sum_out
     void* sum_out = nullptr;        // fp16 [M, N] (required when residual != nullptr)
     const void* gamma = nullptr;    // fp16 [N]
@@ -118,6 +120,14 @@ struct RmsnormParams
     const void* beta = nullptr; // fp16 [N]
 };
 int launch_rmsnorm(const RmsnormParams& p, hipStream_t stream);
+// The one dispatch rule of launch_rmsnorm, host only (no pointer is followed): the kernel it runs for p as
+// 1 = rmsnorm_kernel<1>, 2 = rmsnorm_kernel<8>, 3 + 8 * NV = rmsnorm_reg_kernel<NV> (NV = 1, 2, 4); 0 for an empty problem
+// (M <= 0 or N <= 0: nothing to launch); -1 with set_error where it refuses.
+// kernel: 0 = the launcher's choice; 1 / 2 = that rmsnorm_kernel; 3 = rmsnorm_reg_kernel (NV by N) - a forced kernel whose
+// precondition does not hold is refused (-1), never replaced.
+int rmsnorm_kernel_for(const RmsnormParams& p, int kernel = 0);
+// launch_rmsnorm with the kernel forced as above (tests: both kernels on the same row)
+int launch_rmsnorm_kernel(const RmsnormParams& p, int kernel, hipStream_t stream);
 
 // A11: quantize_tensor (static per-tensor) and quantize_per_token.  K/quantization.cu:31-128.
 int launch_quantize_tensor(int8_t* dst, const void* src, int32_t src_dtype, int64_t size, const float* scale,

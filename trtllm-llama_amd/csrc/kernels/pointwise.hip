@@ -180,7 +180,8 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const RmsnormParams p)
 // The RMSNorm flavour of the kernel above for vector rows of at most 2048 NV elements (LLaMA-7B: NV = 2), the prefill's shape
 // ([tokens, hidden], one launch in front of the QKV GEMM and one in front of the MLP GEMMs of every layer).  Same arithmetic in
 // the same order - per-thread partial sums over ascending k, the same block reductions, the same rounding points - so the two
-// kernels are bit-identical; what differs is the data path: the row stays in registers instead of LDS, and gamma (and the
+// kernels are bit-identical (tests/test_gpu_pointwise_instances.py runs both on the same rows through tllm_rmsnorm's forced
+// kernel and compares y, q, the row scales and sum_out byte for byte); what differs is the data path: the row stays in registers instead of LDS, and gamma (and the
 // static scale) are requested together with the row, not after the reduction (there the gamma load was a second, dependent
 // round trip on every row: 7.6 us per launch at [1024, 4096] for 12 MB of traffic).
 template <int NV>
@@ -422,14 +423,14 @@ __global__ __launch_bounds__(256) void add_kernel(uint16_t* y, const uint16_t* a
 }
 
 __global__ __launch_bounds__(256) void embedding_kernel(
-    uint16_t* out, const int32_t* ids, const uint16_t* table, int32_t hidden, int32_t vocab)
+    uint16_t* out, const int32_t* ids, const uint16_t* table, int32_t hidden, int32_t vocab, int32_t vec8)
 {
     const int64_t t = blockIdx.x;
     const int32_t id = ids[t];
     const bool ok = id >= 0 && id < vocab;
     const uint16_t* src = table + (int64_t) (ok ? id : 0) * hidden;
     uint16_t* dst = out + t * hidden;
-    if ((hidden & 7) == 0)
+    if (vec8) // the launcher's choice: hidden % 8 == 0 and 16-byte aligned out and table
     {
         for (int k = threadIdx.x * 8; k < hidden; k += blockDim.x * 8)
         {
@@ -496,10 +497,15 @@ inline int grid_for(int64_t n)
 
 } // namespace
 
-int launch_rmsnorm(const RmsnormParams& p, hipStream_t stream)
+int rmsnorm_kernel_for(const RmsnormParams& p, int kernel)
 {
     if (p.M <= 0 || p.N <= 0)
         return 0;
+    if (kernel < 0 || kernel > 3)
+    {
+        set_error("rmsnorm: no such kernel %d", kernel);
+        return -1;
+    }
     if (p.residual && !p.sum_out)
     {
         set_error("rmsnorm: residual given without sum_out");
@@ -524,20 +530,48 @@ int launch_rmsnorm(const RmsnormParams& p, hipStream_t stream)
         set_error("layernorm: bias is required");
         return -1;
     }
-    if (vec && !p.layernorm && p.N >= 8 && p.N <= 2048 * 4)
+    const bool reg = vec && !p.layernorm && p.N >= 8 && p.N <= 2048 * 4;
+    if ((kernel == 2 || kernel == 3) && !vec)
     {
-        if (p.N <= 2048)
-            hipLaunchKernelGGL(rmsnorm_reg_kernel<1>, dim3(p.M), dim3(256), 0, stream, p);
-        else if (p.N <= 4096)
-            hipLaunchKernelGGL(rmsnorm_reg_kernel<2>, dim3(p.M), dim3(256), 0, stream, p);
-        else
-            hipLaunchKernelGGL(rmsnorm_reg_kernel<4>, dim3(p.M), dim3(256), 0, stream, p);
+        set_error("rmsnorm: kernel %d needs N %% 8 == 0 (N=%d), 16-byte aligned fp16 pointers and an 8-byte aligned q", kernel, p.N);
+        return -1;
     }
-    else if (vec)
+    if (kernel == 3 && !reg)
+    {
+        set_error("rmsnorm: the register kernel serves RMSNorm rows of 8 <= N <= 8192 only (N=%d, layernorm=%d)", p.N, p.layernorm);
+        return -1;
+    }
+    if (kernel == 1)
+        return 1;
+    if (kernel == 2 || (kernel == 0 && vec && !reg))
+        return 2;
+    if (!reg)
+        return 1;
+    return 3 + 8 * (p.N <= 2048 ? 1 : (p.N <= 4096 ? 2 : 4));
+}
+
+int launch_rmsnorm_kernel(const RmsnormParams& p, int kernel, hipStream_t stream)
+{
+    const int k = rmsnorm_kernel_for(p, kernel);
+    if (k <= 0)
+        return k;
+    const size_t smem = 128 + (size_t) p.N * 2;
+    if (k == 3 + 8 * 1)
+        hipLaunchKernelGGL(rmsnorm_reg_kernel<1>, dim3(p.M), dim3(256), 0, stream, p);
+    else if (k == 3 + 8 * 2)
+        hipLaunchKernelGGL(rmsnorm_reg_kernel<2>, dim3(p.M), dim3(256), 0, stream, p);
+    else if (k == 3 + 8 * 4)
+        hipLaunchKernelGGL(rmsnorm_reg_kernel<4>, dim3(p.M), dim3(256), 0, stream, p);
+    else if (k == 2)
         hipLaunchKernelGGL(rmsnorm_kernel<8>, dim3(p.M), dim3(256), smem, stream, p);
     else
         hipLaunchKernelGGL(rmsnorm_kernel<1>, dim3(p.M), dim3(256), smem, stream, p);
     return check_launch("rmsnorm");
+}
+
+int launch_rmsnorm(const RmsnormParams& p, hipStream_t stream)
+{
+    return launch_rmsnorm_kernel(p, 0, stream);
 }
 
 int launch_quantize_tensor(
@@ -627,8 +661,10 @@ int launch_embedding(void* out, const int32_t* ids, const void* table, int64_t t
 {
     if (tokens <= 0)
         return 0;
+    // 16-byte accesses only where every row of both sides starts on 16 bytes, as vec8_ok asks of the element-wise kernels
+    const int32_t vec8 = !(hidden & 7) && !((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(table)) & 15);
     hipLaunchKernelGGL(embedding_kernel, dim3((unsigned) tokens), dim3(256), 0, stream,
-        reinterpret_cast<uint16_t*>(out), ids, reinterpret_cast<const uint16_t*>(table), hidden, vocab);
+        reinterpret_cast<uint16_t*>(out), ids, reinterpret_cast<const uint16_t*>(table), hidden, vocab, vec8);
     return check_launch("embedding");
 }
 

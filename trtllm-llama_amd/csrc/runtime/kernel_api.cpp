@@ -1,4 +1,4 @@
-// The entry points of include/tllm_runtime_api.h that need no session: single GEMV / GEMM launches, the prefill GEMM tactic
+// The entry points of include/tllm_runtime_api.h that need no session: single GEMV / GEMM / row-wise launches, the prefill GEMM tactic
 // table, the kernels' tuning hooks and the stand-alone sampler (tests, microbenchmarks, the Python builder's profile).
 #include "../../../include/tllm_runtime_api.h"
 #include "../kernels/kernels.h"
@@ -788,6 +788,104 @@ int32_t tllm_token_logprobs(const float* logits, int32_t nparts, int32_t rows, i
     if (launch_token_logprob_partial(p, st))
         return 1;
     return launch_token_logprob_merge(partials, nparts, rows, vocab, targets, log_probs, lse, top1_ids, st) ? 1 : 0;
+}
+
+static RmsnormParams rmsnorm_params(const tllm_rmsnorm_params_t* q)
+{
+    RmsnormParams p;
+    p.M = q->M;
+    p.N = q->N;
+    p.x = q->x;
+    p.residual = q->residual;
+    p.sum_out = q->sum_out;
+    p.gamma = q->gamma;
+    p.eps = q->eps;
+    p.y = q->y;
+    p.q = q->q;
+    p.static_scale = q->static_scale;
+    p.dyn_scale_out = q->dyn_scale_out;
+    p.layernorm = q->layernorm;
+    p.use_diff_of_squares = q->use_diff_of_squares;
+    p.beta = q->beta;
+    return p;
+}
+
+int32_t tllm_rmsnorm(const tllm_rmsnorm_params_t* q, int32_t kernel, tllm_stream_t stream)
+{
+    if (!q || !q->x || !q->gamma || (!q->y && !q->q))
+    {
+        set_error("tllm_rmsnorm: bad arguments (x, gamma and one of y, q must be set)");
+        return -1;
+    }
+    return launch_rmsnorm_kernel(rmsnorm_params(q), kernel, reinterpret_cast<hipStream_t>(stream)) ? -1 : 0;
+}
+
+int32_t tllm_rmsnorm_kernel(const tllm_rmsnorm_params_t* q)
+{
+    if (!q)
+    {
+        set_error("tllm_rmsnorm_kernel: null argument");
+        return -1;
+    }
+    return rmsnorm_kernel_for(rmsnorm_params(q));
+}
+
+int32_t tllm_swiglu(void* y, const void* a, const void* b, int64_t n, tllm_stream_t stream)
+{
+    return launch_swiglu(y, a, b, n, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_swiglu_quant(int8_t* q, const void* a, const void* b, int64_t n, const float* scale, tllm_stream_t stream)
+{
+    return launch_swiglu_quant(q, a, b, n, scale, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_add(void* y, const void* a, const void* b, int64_t n, tllm_stream_t stream)
+{
+    return launch_add(y, a, b, n, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_quantize_tensor(int8_t* dst, const void* src, int32_t src_dtype, int64_t size, const float* scale, tllm_stream_t stream)
+{
+    return launch_quantize_tensor(dst, src, src_dtype, size, scale, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_quantize_per_token(int8_t* dst, const void* src, int32_t src_dtype, int64_t rows, int64_t cols, float* scale_out,
+    tllm_stream_t stream)
+{
+    return launch_quantize_per_token(dst, src, src_dtype, rows, cols, scale_out, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_embedding(void* out, const int32_t* ids, const void* table, int64_t tokens, int32_t hidden, int32_t vocab,
+    tllm_stream_t stream)
+{
+    return launch_embedding(out, ids, table, tokens, hidden, vocab, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gather_last_token(void* out, const void* hidden, const int32_t* last_token_ids, int32_t batch, int32_t seq,
+    int32_t hidden_size, tllm_stream_t stream)
+{
+    return launch_gather_last_token(out, hidden, last_token_ids, batch, seq, hidden_size, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_gather_rows(void* out, const void* hidden, const int32_t* rows, int32_t batch, int32_t hidden_size, tllm_stream_t stream)
+{
+    return launch_gather_rows(out, hidden, rows, batch, hidden_size, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_exclusive_scan_i32(int32_t* cu, const int32_t* lens, int32_t n, tllm_stream_t stream)
+{
+    return launch_exclusive_scan_i32(cu, lens, n, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_fill_i32(int32_t* dst, int32_t value, int64_t n, tllm_stream_t stream)
+{
+    return launch_fill_i32(dst, value, n, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
+}
+
+int32_t tllm_fill_random(void* dst, int32_t dtype, int64_t n, uint32_t seed, float scale, tllm_stream_t stream)
+{
+    return launch_fill_random(dst, dtype, n, seed, scale, reinterpret_cast<hipStream_t>(stream)) ? 1 : 0;
 }
 
 } // extern "C"
