@@ -44,6 +44,13 @@ typedef struct tllm_session* tllm_session_t;
  *   _generate forms, tllm_session_verify, _verify_sampled and both tllm_session_generate_lookup loops, LoRA included, serve the
  *   paged cache through its table, bit for bit what the linear session computes; without the key a paged session refuses them
  *   as before.  A key of the runtime, not of the engine header: tllm_session_load_engine_keys adds it to a loaded engine),
+ *   append_split (0; 1, with the linear cache only - together with paged_kv_cache = 1 it is refused by name: every pass through the
+ *   append attention - the entries listed under paged_append - runs the split-KV kernel (tllm_attention_append_split) whenever the
+ *   head size is 64 / 128 and the pass has N <= 32 rows per sequence, from a workspace allocated at setup - B * 32 * H * (R + 1) *
+ *   (Dh + 2) * 4 bytes, R = min(64, CUs / (Hkv * B), ceil(Smax / 128)): 4.8 MB for the 7B extents at batch 1 on 256 CUs; any other
+ *   pass follows
+ *   the rule as before, and a session without the key launches exactly what it launched before.  Same rule, another summation
+ *   order: results agree within the kernels' bound.  A key of the runtime: tllm_session_load_engine_keys takes it),
  *   debug_taps (0; 1: keep per-layer intermediates of the generation step for tllm_session_get_tap),
  *   gemm_tactics (optional; the table tllm_gemm_tactics_export wrote, as the builder stores it in the engine).
  * Returns NULL on error (tllm_last_error()). */
@@ -63,7 +70,7 @@ int32_t tllm_session_finalize(tllm_session_t s);
  * text, tensor table, data) = tllm_engine_verify + create + set_tensor(location 0) + finalize. */
 tllm_session_t tllm_session_load_engine(const void* engine, size_t nbytes);
 /* The same with session keys of the runtime behind the header's: runtime_keys is "key=value" lines (NULL or empty: none).  Only
- * the keys that are not the engine's to decide are taken - paged_append - and any other line is refused by name, so nothing the
+ * the keys that are not the engine's to decide are taken - paged_append, append_split - and any other line is refused by name, so nothing the
  * engine was built and verified with can be overridden here. */
 tllm_session_t tllm_session_load_engine_keys(const void* engine, size_t nbytes, const char* runtime_keys);
 
@@ -224,6 +231,9 @@ int32_t tllm_session_append_ragged_generate(tllm_session_t s, const int32_t* ids
 /* Attention launches tllm_session_append and tllm_session_append_ragged have enqueued since setup, by kernel (one per layer and
  * call): *wave, *mfma (either may be NULL).  For tests: which kernel served a chunk. */
 int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* mfma);
+/* The same for the launches the session key append_split sent to the split-KV kernel (one per layer and pass; they are counted
+ * here and not in *wave / *mfma).  0 for a session without the key. */
+int32_t tllm_session_append_split_launches(tllm_session_t s, int64_t* count);
 
 /* Speculative greedy decoding (the rules are stated in csrc/kernels/kernels.h, SpecAcceptParams and
  * PromptLookupParams, and restated in numpy in tensorrt_llm/runtime/spec_ref.py).  Opt-in: tllm_session_generate, the step graph
@@ -796,6 +806,29 @@ int32_t tllm_attention_append_paged(const tllm_attention_append_params_t* p, con
 /* the attention kernel tllm_attention_append would run for p (n, head_size and append_kernel are read; no pointer is followed; no
  * GPU needed): TLLM_APPEND_ATTN_WAVE or _MFMA in *kind.  Non-zero: a forced append_kernel the launch cannot run. */
 int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* p, int32_t* kind);
+/* The split-KV form of the append attention (kernels/append_attn_split.hip) for SHORT appends onto LONG pasts:
+ * tllm_attention_append (n_per_seq NULL; p->max_past holds, max_end ignored) or tllm_attention_append_ragged (n_per_seq set;
+ * max_end holds) with the attention launch replaced by two: one workgroup per (sequence, K/V head, range of split_chunk past slots)
+ * serves every query row that reads the K/V head - the cache rows of a range are fetched once, not once per query row - and writes
+ * fp32 partials (m, l, O) to the workspace; a merge launch sums them in range order.  The rule, the cache write and every
+ * refusal are the linear entries'; only the summation order differs, so results agree within the kernels' bound, not bit for bit,
+ * and two runs give the same bits.  p->append_kernel is ignored (this entry IS the choice; the value TLLM_APPEND_ATTN_SPLIT in
+ * the entries above is refused and names this one - they have no workspace).
+ *   split_chunk  0 = the plan's (tllm_attention_append_split_layout for the device's CU count), else a positive multiple of 64;
+ *   workspace    device, 16-byte aligned, >= the layout's workspace_bytes for the same p, split_chunk and max_keys = p->max_past
+ *                (uniform) or max_end (ragged); written before it is read, nothing to clear; free for reuse when the stream has
+ *                passed the call.
+ * Refused, with nothing launched: head size not 64 / 128; n < 1 or n > 32; workspace NULL, misaligned or too small; split_chunk
+ * negative or not a multiple of 64; and everything tllm_attention_append / _ragged refuse.  The paged cache is not served. */
+#define TLLM_APPEND_ATTN_SPLIT 3
+int32_t tllm_attention_append_split(const tllm_attention_append_params_t* p, const int32_t* n_per_seq /* NULL = uniform */,
+    int32_t max_end, int32_t split_chunk, void* workspace, int64_t workspace_bytes, tllm_stream_t stream);
+/* the plan tllm_attention_append_split follows for p (batch, n, num_heads, num_kv_heads, head_size are read; no pointer is followed;
+ * no GPU needed): past slots [r * chunk, (r + 1) * chunk) are range r < ranges = ceil(max_keys / chunk), max_keys >= every past
+ * length.  split_chunk 0: the smallest multiple of 64 that is >= 128, gives at most 64 ranges and fills `cus` CUs (<= 0: 256) about
+ * once.  workspace_bytes = batch * n * num_heads * (ranges + 1) * (head_size + 2) * 4.  Non-zero: a refusal of the list above. */
+int32_t tllm_attention_append_split_layout(const tllm_attention_append_params_t* p, int32_t max_keys, int32_t cus, int32_t split_chunk,
+    int32_t* chunk, int32_t* ranges, int64_t* workspace_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Kernel-level entries of the row-wise and element-wise kernels (kernels/pointwise.hip), so that tests reach every kernel without

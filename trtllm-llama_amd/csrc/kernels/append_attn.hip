@@ -9,6 +9,8 @@
 //                               blocks - first the past blocks from the cache, then the chunk's blocks from the QKV buffer;
 //   (c) append_attn_wave_kernel one wave per query: every n, head sizes 32 / 64 / 128 / 256;
 //   (d) append_advance_kernel   sequence_length[b] += n, finished[b] = 0 (the session's bookkeeping, a launch of its own).
+// In place of (b) / (c), by name only (APPEND_ATTN_SPLIT; append_attn_split.hip): the split-KV pair of launches for n <= 32 onto a
+// long past - same rule, another summation order.
 // A different number of tokens per sequence (n_per_seq, device [B]; null = n for all): sequence b appends n_b = n_per_seq[b]
 // clamped into [0, n], n stays the row stride of the QKV buffer and of `out`, and the rule above holds with n_b in place of n.  Rows
 // i >= n_b are padding: (a) leaves them alone (no RoPE, no cache store - their bits in the QKV buffer stay), (b) and (c) write
@@ -24,6 +26,7 @@
 // Every load index is clamped or predicated and every cache store is guarded by slot < Smax: a wrong length on the device can give
 // wrong numbers, never an access outside the cache, the QKV buffer or `out`.  Keys that are masked or beyond a length are never
 // multiplied in (their V rows enter as zero), so what such slots hold - NaN included - does not reach the result.
+#include "append_attn_common.h"
 #include "dev_utils.h"
 #include "kernels.h"
 #include "launch_util.h"
@@ -33,45 +36,10 @@ namespace tllm
 namespace kernels
 {
 using namespace dev;
+using namespace append_attn;
 
 namespace
 {
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi)
-{
-    return v < lo ? lo : (v > hi ? hi : v);
-}
-
-// cache element kinds of the instances: 0 fp16, 1 int8, 2 fp8 (E4M3)
-constexpr int kv_kind(int32_t kv_dtype)
-{
-    return kv_dtype == DT_INT8 ? 1 : (kv_dtype == DT_FP8 ? 2 : 0);
-}
-
-// 8 cache elements -> 8 fp16: the value of the byte itself for the one-byte types (exact; the scale is applied by the caller)
-template <int KV>
-__device__ __forceinline__ uint4 load_kv8(const char* ptr)
-{
-    if constexpr (KV == 0)
-        return *reinterpret_cast<const uint4*>(ptr);
-    else
-    {
-        const uint2 q = *reinterpret_cast<const uint2*>(ptr);
-        if constexpr (KV == 2)
-            return dequant8_fp8(q);
-        else
-        {
-            float f[8];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-            {
-                f[j] = (float) (int8_t) (q.x >> (8 * j));
-                f[4 + j] = (float) (int8_t) (q.y >> (8 * j));
-            }
-            return f_to_h8(f);
-        }
-    }
-}
 
 // ---- (a) grid (n, ceil(H / HG), B), 256 threads: DH / 8 lanes own the 8-element pieces of one head of one appended token
 template <int DH, bool PG>
@@ -629,13 +597,15 @@ __global__ __launch_bounds__(256) void append_advance_kernel(int32_t* sequence_l
 }
 
 template <int DH, bool PG>
-int launch_dh(const AppendAttnParams& p, int kind, hipStream_t stream)
+int launch_dh(const AppendAttnParams& p, int kind, hipStream_t stream, const AppendSplitPlan* split = nullptr)
 {
     constexpr int HG = 256 / (DH / 8);
     hipLaunchKernelGGL((append_rope_kv_kernel<DH, PG>), dim3(p.n, (p.num_heads + HG - 1) / HG, p.batch), dim3(256), 0, stream, p);
     if (launch_util::check_launch("append attention (RoPE, cache write)"))
         return -1;
     const int kv = kv_kind(p.kv_dtype);
+    if (kind == APPEND_ATTN_SPLIT) // (checked by the caller: head size 64 / 128, the linear cache, a plan and its workspace)
+        return launch_append_attn_split(p, *split, stream);
     if (kind == APPEND_ATTN_MFMA)
     {
         if constexpr (DH == 64 || DH == 128)
@@ -684,6 +654,15 @@ int append_attention_kernel(int32_t head_size, int32_t n, int32_t forced_kernel,
             kind = APPEND_ATTN_MFMA;
         else
             why = "the MFMA kernel needs head size 64 or 128 and n >= 16";
+    }
+    else if (forced_kernel == APPEND_ATTN_SPLIT)
+    {
+        if (head_size != 64 && head_size != 128)
+            why = "the split-KV kernel needs head size 64 or 128";
+        else if (n > 32)
+            why = "the split-KV kernel needs 1 <= n <= 32";
+        else
+            kind = APPEND_ATTN_SPLIT;
     }
     else
         why = "unknown kernel kind";
@@ -763,6 +742,29 @@ int launch_append_attention(const AppendAttnParams& pin, hipStream_t stream)
     {
         set_error("append attention: rotary_dim %d without a RoPE table", p.rotary_dim);
         return -1;
+    }
+    if (kind == APPEND_ATTN_SPLIT)
+    {
+        if (p.block_pointers)
+        {
+            set_error("append attention: the split-KV kernel does not serve the paged KV cache (a block table was given)");
+            return -1;
+        }
+        const AppendSplitPlan plan = append_split_plan(p.head_size, p.n, p.batch, p.num_heads, p.num_kv_heads,
+            p.n_per_seq ? p.max_end : p.max_past, launch_util::device_cus(), p.split_chunk);
+        if (plan.refused)
+        {
+            set_error("append attention: split-KV plan refused (split_chunk %d): %s", p.split_chunk, plan.refused);
+            return -1;
+        }
+        if (!p.workspace || ((uintptr_t) p.workspace & 15) || p.workspace_bytes < plan.workspace_bytes)
+        {
+            set_error("append attention: the split-KV kernel needs a 16-byte aligned workspace of >= %lld bytes (got %s, %lld bytes)",
+                (long long) plan.workspace_bytes, !p.workspace ? "null" : (((uintptr_t) p.workspace & 15) ? "a misaligned one" : "one too small"),
+                (long long) p.workspace_bytes);
+            return -1;
+        }
+        return p.head_size == 64 ? launch_dh<64, false>(p, kind, stream, &plan) : launch_dh<128, false>(p, kind, stream, &plan);
     }
     if (p.block_pointers) // the paged instances
     {

@@ -420,7 +420,11 @@ enum AppendAttnKernel
 {
     APPEND_ATTN_RULE = 0, // the MFMA kernel where it serves (head size 64 / 128, n >= 16), else one wave per query
     APPEND_ATTN_WAVE = 1, // one wave per query: every n, head sizes 32 / 64 / 128 / 256
-    APPEND_ATTN_MFMA = 2  // 64 queries per workgroup, online soft-max over 64-key blocks
+    APPEND_ATTN_MFMA = 2, // 64 queries per workgroup, online soft-max over 64-key blocks
+    // split-KV (kernels/append_attn_split.hip): one workgroup per (sequence, K/V head, key range) serves every query row that reads
+    // the K/V head, then a merge launch; head size 64 / 128, 1 <= n <= 32, the linear cache, a caller-owned workspace.  Only ever
+    // asked for by name: the rule does not choose it
+    APPEND_ATTN_SPLIT = 3
 };
 struct AppendAttnParams
 {
@@ -459,9 +463,34 @@ struct AppendAttnParams
     // paged instances, same arithmetic in the same order: every result is the linear launch's on the same logical cache, bit for bit
     const int64_t* block_pointers = nullptr;
     int32_t tokens_per_block = 0, max_blocks_per_seq = 0;
+    // APPEND_ATTN_SPLIT alone: the partials' workspace (device, 16-byte aligned, >= append_split_plan(...).workspace_bytes; the
+    // launch writes every word it later reads, nothing has to be cleared) and the chunk length (0 = the plan's, else a positive
+    // multiple of 64)
+    void* workspace = nullptr;
+    int64_t workspace_bytes = 0;
+    int32_t split_chunk = 0;
 };
-// the attention kernel a launch runs (APPEND_ATTN_WAVE / _MFMA), 0 = refused (*refused says why)
+// the attention kernel a launch runs (APPEND_ATTN_WAVE / _MFMA, _SPLIT when forced), 0 = refused (*refused says why)
 int append_attention_kernel(int32_t head_size, int32_t n, int32_t forced_kernel, const char** refused = nullptr);
+// The plan of APPEND_ATTN_SPLIT (pure host code): past slots [r * chunk, (r + 1) * chunk) are range r < ranges = ceil(max_keys /
+// chunk) (max_keys >= every past length: max_past, or max_end of a ragged launch), range `ranges` is the appended tokens themselves;
+// the n * (H / Hkv) query rows of a K/V head are served 32 to a tile group.  Grid (ranges + 1, Hkv * tile_groups, batch).
+// chunk, unless forced: the smallest multiple of 64 that is >= 128, gives at most 64 ranges, and leaves ranges * Hkv * tile_groups *
+// batch at about the CU count (cus; <= 0: 256) - more ranges than that only add partials to merge.
+// workspace_bytes = batch * n * H * (ranges + 1) * (head_size + 2) * 4: per (row, range) fp32 O[head_size], m, l.
+struct AppendSplitPlan
+{
+    int32_t chunk = 0, ranges = 0, tile_groups = 0;
+    int64_t workspace_bytes = 0;
+    const char* refused = nullptr; // set: nothing else is
+};
+AppendSplitPlan append_split_plan(int32_t head_size, int32_t n, int32_t batch, int32_t num_heads, int32_t num_kv_heads,
+    int32_t max_keys, int32_t cus, int32_t forced_chunk);
+// the most workspace_bytes the plan's own chunk (split_chunk 0) asks for on a device of `cus` CUs, over every n <= max_n and every
+// max_keys <= max_seq_len: what a session allocates once.  The rule gives at most min(64, cus / (Hkv * batch), ceil(max_keys / 128))
+// ranges
+int64_t append_split_workspace_max(int32_t head_size, int32_t max_n, int32_t batch, int32_t num_heads, int32_t num_kv_heads,
+    int32_t max_seq_len, int32_t cus);
 int launch_append_attention(const AppendAttnParams& p, hipStream_t stream);
 // sequence_length[b] += n; finished[b] = 0 (finished may be null): one workgroup, a launch of its own
 int launch_append_advance(int32_t* sequence_length, int32_t* finished, int32_t batch, int32_t n, hipStream_t stream);

@@ -271,9 +271,18 @@ int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* q, in
 
 // n_per_seq null: tllm_attention_append (q->max_past holds); else tllm_attention_append_ragged (max_end in its place).
 // block_pointers set: tllm_attention_append_paged (q->kv_cache is the pool)
-static int32_t attention_append(const char* who, const tllm_attention_append_params_t* q, const int32_t* n_per_seq, int32_t max_end,
-    tllm_stream_t stream, const int64_t* block_pointers = nullptr, int32_t tokens_per_block = 0, int32_t max_blocks_per_seq = 0)
+// split: tllm_attention_append_split (its workspace and chunk; the kernel is APPEND_ATTN_SPLIT whatever q->append_kernel says)
+struct AppendSplitArgs
 {
+    int32_t split_chunk;
+    void* workspace;
+    int64_t workspace_bytes;
+};
+static int32_t attention_append(const char* who, const tllm_attention_append_params_t* q, const int32_t* n_per_seq, int32_t max_end,
+    tllm_stream_t stream, const int64_t* block_pointers = nullptr, int32_t tokens_per_block = 0, int32_t max_blocks_per_seq = 0,
+    const AppendSplitArgs* split = nullptr)
+{
+    static_assert(TLLM_APPEND_ATTN_SPLIT == APPEND_ATTN_SPLIT, "the header's kinds are the launcher's");
     if (!q || q->batch < 1 || q->n < 1 || q->num_heads < 1 || q->head_size < 1 || q->max_seq_len < 1)
     {
         set_error("%s: bad arguments (batch, n, num_heads, head_size, max_seq_len)", who);
@@ -282,6 +291,12 @@ static int32_t attention_append(const char* who, const tllm_attention_append_par
     if (q->kv_cache_type != 0 && q->kv_cache_type != TLLM_HALF && q->kv_cache_type != TLLM_INT8 && q->kv_cache_type != TLLM_FP8)
     {
         set_error("%s: kv_cache_type %d is not TLLM_HALF, TLLM_INT8 or TLLM_FP8", who, q->kv_cache_type);
+        return 1;
+    }
+    if (!split && q->append_kernel == APPEND_ATTN_SPLIT)
+    {
+        set_error("%s: append_kernel %d (split-KV) needs a workspace this entry does not take: call tllm_attention_append_split", who,
+            q->append_kernel);
         return 1;
     }
     AppendAttnParams p;
@@ -311,6 +326,13 @@ static int32_t attention_append(const char* who, const tllm_attention_append_par
     p.block_pointers = block_pointers;
     p.tokens_per_block = tokens_per_block;
     p.max_blocks_per_seq = max_blocks_per_seq;
+    if (split)
+    {
+        p.kernel = APPEND_ATTN_SPLIT;
+        p.split_chunk = split->split_chunk;
+        p.workspace = split->workspace;
+        p.workspace_bytes = split->workspace_bytes;
+    }
     if (p.rotary_dim > 0)
     {
         p.rope_table = tllm::plugins::rope_table(p.rotary_dim, p.max_seq_len, &p.rope_table_len);
@@ -346,6 +368,37 @@ int32_t tllm_attention_append_paged(const tllm_attention_append_params_t* q, con
     }
     return attention_append("tllm_attention_append_paged", q, n_per_seq, max_end, stream, block_pointers, tokens_per_block,
         max_blocks_per_seq);
+}
+
+int32_t tllm_attention_append_split(const tllm_attention_append_params_t* q, const int32_t* n_per_seq, int32_t max_end,
+    int32_t split_chunk, void* workspace, int64_t workspace_bytes, tllm_stream_t stream)
+{
+    const AppendSplitArgs split{split_chunk, workspace, workspace_bytes};
+    return attention_append("tllm_attention_append_split", q, n_per_seq, max_end, stream, nullptr, 0, 0, &split);
+}
+
+int32_t tllm_attention_append_split_layout(const tllm_attention_append_params_t* q, int32_t max_keys, int32_t cus, int32_t split_chunk,
+    int32_t* chunk, int32_t* ranges, int64_t* workspace_bytes)
+{
+    if (!q)
+    {
+        set_error("tllm_attention_append_split_layout: bad arguments");
+        return 1;
+    }
+    const AppendSplitPlan plan = append_split_plan(q->head_size, q->n, q->batch, q->num_heads, q->num_kv_heads, max_keys, cus, split_chunk);
+    if (plan.refused)
+    {
+        set_error("tllm_attention_append_split_layout: refused (head size %d, n %d, split_chunk %d): %s", q->head_size, q->n,
+            split_chunk, plan.refused);
+        return 1;
+    }
+    if (chunk)
+        *chunk = plan.chunk;
+    if (ranges)
+        *ranges = plan.ranges;
+    if (workspace_bytes)
+        *workspace_bytes = plan.workspace_bytes;
+    return 0;
 }
 
 static GemvParams gemv_params(const tllm_gemv_params_t* q)

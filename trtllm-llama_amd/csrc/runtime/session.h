@@ -145,6 +145,9 @@ struct tllm_session
     // loops - serve the paged cache through the table (the paged instances of kernels/append_attn.hip).  Without it a paged
     // session refuses them as it always did
     bool paged_append = false;
+    // session key append_split (a key of the runtime too): every pass through append_attention() runs the split-KV kernel
+    // (kernels/append_attn_split.hip) whenever Dh is 64 / 128 and the pass's N <= 32, else the rule as before.  The linear cache only
+    bool append_split = false;
     size_t kv_elems = 0; // elements of one layer's cache / pool
     bool force_comm = false; // tests: run the TP collectives on a 1-rank communicator too (RCCL inside the captured graph)
     // session key no_comm = 1: a rank's launches WITHOUT its collectives (all-reduces and the logits all-gather are skipped, nothing
@@ -190,6 +193,9 @@ struct tllm_session
                                     // sequence, or the lengths of a ragged append - then the attention's n_per_seq too
     int append_max_end = 0;         // > 0 during a ragged append pass: max_b (past[b] + n_b), and append_last holds the lengths
     int64_t append_wave_launches = 0, append_mfma_launches = 0; // attention launches of tllm_session_append since setup, by kernel
+    int64_t append_split_launches = 0; // and those the key append_split sent to the split-KV kernel (counted here alone)
+    void* append_split_ws = nullptr;   // its partials: sized at setup for N = 32 and the finest plan of Smax
+    int64_t append_split_ws_bytes = 0;
     const float* rope = nullptr;
     int rope_len = 0;
     float* rope_row = nullptr; // [B, Dh/2, 2]: cos/sin row of the next generation step (written by the sampler)

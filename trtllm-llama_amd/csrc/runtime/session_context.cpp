@@ -301,6 +301,15 @@ int tllm_session::append_attention(const Layer& L, int n, int max_past, hipStrea
     a.rope_table = rope;
     a.rope_table_len = rope_len;
     a.out = ctx;
+    if (append_split_ws && n <= 32) // session key append_split (Dh 64 / 128: the workspace exists), a pass the kernel serves
+    {
+        a.kernel = APPEND_ATTN_SPLIT;
+        a.workspace = append_split_ws;
+        a.workspace_bytes = append_split_ws_bytes;
+        RUN(launch_append_attention(a, st) ? 1 : 0);
+        ++append_split_launches;
+        return 0;
+    }
     const int kind = append_attention_kernel(Dh, n, APPEND_ATTN_RULE);
     RUN(launch_append_attention(a, st) ? 1 : 0);
     ++(kind == APPEND_ATTN_MFMA ? append_mfma_launches : append_wave_launches);

@@ -108,7 +108,18 @@ int tllm_session::alloc_buffers()
     RUN(dalloc(&last_tok, (size_t) Bc * 4));
     RUN(dalloc(&in_len_ctx, (size_t) Bc * 4));
     RUN(dalloc(&append_last, (size_t) B * 4));
-    append_wave_launches = append_mfma_launches = 0;
+    append_wave_launches = append_mfma_launches = append_split_launches = 0;
+    append_split_ws = nullptr;
+    append_split_ws_bytes = 0;
+    if (append_split && (Dh == 64 || Dh == 128))
+    {
+        // the most a pass of N <= kVerifyMaxTokens (= 32, the kernel's own limit) rows asks for on this device behind any past <= Smax
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            cus = 0; // (the launcher's own fallback: 256)
+        append_split_ws_bytes = append_split_workspace_max(Dh, kVerifyMaxTokens, B, Hr, Hkvr, Smax, cus);
+        RUN(dalloc(&append_split_ws, (size_t) append_split_ws_bytes));
+    }
     has_context = false;
     cum_log_probs = nullptr;
     parent_ids = cache_ind = nullptr;

@@ -189,6 +189,13 @@ tllm_session_t tllm_session_create(const char* config_text)
         set_error("tllm_session_create: paged_append = 1 needs paged_kv_cache = 1 (the append passes of a linear cache need no key)");
         return nullptr;
     }
+    s->append_split = geti("append_split", 0) != 0;
+    if (s->append_split && s->paged_kv)
+    {
+        set_error("tllm_session_create: append_split = 1 does not go with paged_kv_cache = 1 (the split-KV append attention serves "
+                  "the linear cache only)");
+        return nullptr;
+    }
     if (kv.count("rms_norm_eps"))
         s->eps = (float) atof(kv["rms_norm_eps"].c_str());
     if (kv.count("weight_only_precision"))
@@ -562,9 +569,9 @@ tllm_session_t tllm_session_load_engine_keys(const void* engine, size_t nbytes, 
                 continue;
             const size_t e = eq == std::string::npos ? std::string::npos : line.find_last_not_of(" \t\r", eq - 1);
             const std::string key = eq == std::string::npos || eq == a ? std::string() : line.substr(a, e - a + 1);
-            if (key != "paged_append")
+            if (key != "paged_append" && key != "append_split")
             {
-                set_error("tllm_session_load_engine_keys: '%s' is not a runtime key (paged_append); the engine header holds the rest",
+                set_error("tllm_session_load_engine_keys: '%s' is not a runtime key (paged_append, append_split); the engine header holds the rest",
                     line.c_str());
                 return nullptr;
             }

@@ -117,6 +117,14 @@ def _lib():
     lib.tllm_attention_append_paged.restype = c.c_int32
     lib.tllm_attention_append_layout.argtypes = [c.POINTER(AttentionAppendParamsC), c.POINTER(c.c_int32)]
     lib.tllm_attention_append_layout.restype = c.c_int32
+    lib.tllm_attention_append_split.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p, c.c_int32, c.c_int32, c.c_void_p,
+                                                c.c_int64, c.c_void_p]
+    lib.tllm_attention_append_split.restype = c.c_int32
+    lib.tllm_attention_append_split_layout.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_int32, c.c_int32, c.c_int32,
+                                                       c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(c.c_int64)]
+    lib.tllm_attention_append_split_layout.restype = c.c_int32
+    lib.tllm_session_append_split_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
+    lib.tllm_session_append_split_launches.restype = c.c_int32
     lib.tllm_session_verify.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.tllm_session_verify.restype = c.c_int32
     lib.tllm_session_verify_top1.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
@@ -246,7 +254,7 @@ class AttentionAppendParamsC(ctypes.Structure):
                 ('kv_scale_quant_orig', ctypes.c_void_p), ('out', ctypes.c_void_p)]
 
 
-APPEND_ATTN_WAVE, APPEND_ATTN_MFMA = 1, 2
+APPEND_ATTN_WAVE, APPEND_ATTN_MFMA, APPEND_ATTN_SPLIT = 1, 2, 3
 
 
 def attention_append_kernel(n: int, head_size: int, append_kernel: int = 0) -> int:
@@ -288,6 +296,56 @@ def attention_append(qkv, kv_cache, out, sequence_length, input_lengths, *, num_
         assert str(n_per_seq.dtype) == 'torch.int32' and tuple(n_per_seq.shape) == (B, ), 'n_per_seq must be int32 [B]'
         _check(_lib().tllm_attention_append_ragged(ctypes.byref(p), n_per_seq.data_ptr(), int(max_end), stream),
                'attention_append_ragged')
+
+
+def attention_append_split_layout(n: int, head_size: int, *, batch: int, num_heads: int, num_kv_heads: int = 0, max_keys: int,
+                                  cus: int = 0, split_chunk: int = 0):
+    """tllm_attention_append_split_layout: (chunk, ranges, workspace_bytes) of the split-KV append attention for max_keys >= every
+    past length on a device of `cus` CUs (0: 256); split_chunk 0 = the plan's own.  Raises on a refusal.  Needs no GPU."""
+    p = AttentionAppendParamsC(batch=int(batch), n=int(n), num_heads=int(num_heads), num_kv_heads=int(num_kv_heads),
+                               head_size=int(head_size))
+    chunk, ranges, nbytes = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    _check(_lib().tllm_attention_append_split_layout(ctypes.byref(p), int(max_keys), int(cus), int(split_chunk), ctypes.byref(chunk),
+                                                     ctypes.byref(ranges), ctypes.byref(nbytes)), 'attention_append_split_layout')
+    return int(chunk.value), int(ranges.value), int(nbytes.value)
+
+
+def attention_append_split(qkv, kv_cache, out, sequence_length, input_lengths, *, num_heads, num_kv_heads=0, head_size, max_input_len,
+                           max_past=None, masked_tokens=None, kv_cache_type=0, kv_scale_orig_quant=None, kv_scale_quant_orig=None,
+                           rotary_dim=None, neox=1, q_scaling=1.0, n_per_seq=None, max_end=None, split_chunk=0, workspace=None,
+                           stream: int = 0):
+    """tllm_attention_append_split: attention_append (or its ragged form, n_per_seq with max_end) with the split-KV attention kernel -
+    head sizes 64 / 128, 1 <= n <= 32, the linear cache.  split_chunk: past slots per workgroup, 0 = the plan's.  workspace: a
+    contiguous cuda tensor of at least attention_append_split_layout(...)'s bytes (its whole extent is offered), or None - then one
+    is allocated for the current device's plan.  Asynchronous; the workspace must live until the stream has passed the call."""
+    import torch
+    B, n = qkv.shape[0], qkv.shape[1]
+    if (n_per_seq is None) != (max_end is None):
+        raise ValueError('n_per_seq and max_end go together')
+    if n_per_seq is None and max_past is None:
+        raise ValueError('max_past must be given (or n_per_seq with max_end)')
+    for t in (qkv, kv_cache, out, sequence_length, input_lengths, masked_tokens, kv_scale_orig_quant, kv_scale_quant_orig,
+              n_per_seq, workspace):
+        assert t is None or (t.is_cuda and t.is_contiguous())
+    if workspace is None:
+        cus = torch.cuda.get_device_properties(qkv.device).multi_processor_count
+        nbytes = attention_append_split_layout(n, head_size, batch=B, num_heads=num_heads, num_kv_heads=num_kv_heads,
+                                               max_keys=int(max_past if n_per_seq is None else max_end), cus=cus,
+                                               split_chunk=split_chunk)[2]
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    p = AttentionAppendParamsC(batch=B, n=n, num_heads=num_heads, num_kv_heads=num_kv_heads, head_size=head_size,
+                               rotary_dim=head_size if rotary_dim is None else rotary_dim, neox=neox, q_scaling=q_scaling,
+                               kv_cache_type=kv_cache_type, max_seq_len=kv_cache.shape[3], max_input_len=max_input_len,
+                               max_past=max_past or 0, qkv=ptr(qkv), kv_cache=ptr(kv_cache),
+                               sequence_length=ptr(sequence_length), input_lengths=ptr(input_lengths),
+                               masked_tokens=ptr(masked_tokens), kv_scale_orig_quant=ptr(kv_scale_orig_quant),
+                               kv_scale_quant_orig=ptr(kv_scale_quant_orig), out=ptr(out))
+    if n_per_seq is not None:
+        assert str(n_per_seq.dtype) == 'torch.int32' and tuple(n_per_seq.shape) == (B, ), 'n_per_seq must be int32 [B]'
+    _check(_lib().tllm_attention_append_split(ctypes.byref(p), ptr(n_per_seq), int(max_end or 0), int(split_chunk),
+                                              workspace.data_ptr() or None, workspace.numel() * workspace.element_size(), stream),
+           'attention_append_split')
 
 
 def attention_append_paged(qkv, pool, block_pointers, out, sequence_length, input_lengths, *, tokens_per_block, max_seq_len,
@@ -413,7 +471,8 @@ class NativeSession:
 
     def __init__(self, config: Optional[Dict] = None, engine: Optional[bytes] = None, runtime_keys: Optional[Dict] = None):
         """config: the session keys; or engine: a serialized engine, whose header holds them - then runtime_keys adds the keys
-        that belong to the runtime and not to the engine (paged_append; tllm_session_load_engine_keys refuses every other)."""
+        that belong to the runtime and not to the engine (paged_append, append_split; tllm_session_load_engine_keys refuses every
+        other)."""
         lib = _lib()
         self._keep = []  # torch tensors whose device memory the session references
         if engine is not None:
@@ -669,7 +728,14 @@ class NativeSession:
         _check(_lib().tllm_session_append_launches(self._h, ctypes.byref(w), ctypes.byref(m)), 'append_launches')
         return int(w.value), int(m.value)
 
+    def append_split_launches(self):
+        """attention launches the session key append_split has sent to the split-KV kernel since setup (one per layer and pass)"""
+        n = ctypes.c_int64()
+        _check(_lib().tllm_session_append_split_launches(self._h, ctypes.byref(n)), 'append_split_launches')
+        return int(n.value)
+
     attention_append = staticmethod(attention_append)
+    attention_append_split = staticmethod(attention_append_split)
     attention_append_paged = staticmethod(attention_append_paged)
     spec_accept = staticmethod(spec_accept)
     prompt_lookup = staticmethod(prompt_lookup)
