@@ -51,6 +51,12 @@ typedef struct tllm_session* tllm_session_t;
  *   pass follows
  *   the rule as before, and a session without the key launches exactly what it launched before.  Same rule, another summation
  *   order: results agree within the kernels' bound.  A key of the runtime: tllm_session_load_engine_keys takes it),
+ *   stream_gemm (0; 1, SmoothQuant engines only - any other quant_mode refuses it by name: every layer projection of 9 <= M <= 64
+ *   rows - the passes listed under paged_append at B * N rows in that range, and prompts that short - runs the weight-streaming
+ *   GEMM (tllm_gemm_stream) from a workspace allocated at setup for M = 64 and the layer's shapes; a shape that kernel refuses,
+ *   the dual SwiGLU GEMM of static scales at M >= 32 and every other M run what they ran before.  Integer sums, the same scaling
+ *   and rounding: results are bit for bit those of a session without the key, which launches exactly what it launched before.
+ *   A key of the runtime: tllm_session_load_engine_keys takes it),
  *   debug_taps (0; 1: keep per-layer intermediates of the generation step for tllm_session_get_tap),
  *   gemm_tactics (optional; the table tllm_gemm_tactics_export wrote, as the builder stores it in the engine).
  * Returns NULL on error (tllm_last_error()). */
@@ -70,7 +76,7 @@ int32_t tllm_session_finalize(tllm_session_t s);
  * text, tensor table, data) = tllm_engine_verify + create + set_tensor(location 0) + finalize. */
 tllm_session_t tllm_session_load_engine(const void* engine, size_t nbytes);
 /* The same with session keys of the runtime behind the header's: runtime_keys is "key=value" lines (NULL or empty: none).  Only
- * the keys that are not the engine's to decide are taken - paged_append, append_split - and any other line is refused by name, so nothing the
+ * the keys that are not the engine's to decide are taken - paged_append, append_split, stream_gemm - and any other line is refused by name, so nothing the
  * engine was built and verified with can be overridden here. */
 tllm_session_t tllm_session_load_engine_keys(const void* engine, size_t nbytes, const char* runtime_keys);
 
@@ -234,6 +240,9 @@ int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* m
 /* The same for the launches the session key append_split sent to the split-KV kernel (one per layer and pass; they are counted
  * here and not in *wave / *mfma).  0 for a session without the key. */
 int32_t tllm_session_append_split_launches(tllm_session_t s, int64_t* count);
+/* GEMM calls the session key stream_gemm has sent to the weight-streaming kernel (tllm_gemm_stream) since setup.  0 for a session
+ * without the key. */
+int32_t tllm_session_stream_gemm_launches(tllm_session_t s, int64_t* count);
 
 /* Speculative greedy decoding (the rules are stated in csrc/kernels/kernels.h, SpecAcceptParams and
  * PromptLookupParams, and restated in numpy in tensorrt_llm/runtime/spec_ref.py).  Opt-in: tllm_session_generate, the step graph
@@ -628,6 +637,27 @@ int32_t tllm_gemm_residual(const tllm_gemm_params_t* p, const void* residual, tl
  * c = fp16(fp16(silu(gate)) * fp16(epi(A W^T))), the gate half of SwiGLU that the fp16 / weight-only prefill runs inside its
  * up-projection GEMM.  Whatever kernel the dispatch picks, including the passes behind the kernels that fuse neither. */
 int32_t tllm_gemm_epi(const tllm_gemm_params_t* p, const void* residual, const void* silu_gate, tllm_stream_t stream);
+/* The SmoothQuant GEMM of 9 <= M <= 64 rows as a weight stream on the matrix pipe (kernels/gemm_stream_sq.hip; DESIGN.md section
+ * 7c): wtype 3, int8 A as given, fp16 or fp32 output, optionally the residual epilogue of tllm_gemm_residual (residual NULL = none;
+ * it may be p->c).  Every weight byte is read from HBM once whatever M is; K is split across workgroups and the exact int32
+ * partial sums meet in `workspace` (device, 16-byte aligned, >= tllm_gemm_stream_layout's workspace_bytes for the device's CU
+ * count; written before it is read, nothing to clear; free for reuse when the stream has passed the call).  The result is bit
+ * for bit tllm_gemm's, and two runs give the same bits.  Returns 0 launched, 1 refused with the reason in tllm_last_error() and
+ * nothing enqueued: a weight type other than SmoothQuant; M < 9 or M > 64; K not a multiple of 64; an output type other than fp16 /
+ * fp32 (a residual: fp16); A or W not 16-byte aligned, lda / ldw below K or not a multiple of 16; C not aligned to four outputs, ldc
+ * below N or not a multiple of 4; a workspace that is NULL, misaligned or too small.  Negative: a launch error. */
+int32_t tllm_gemm_stream(const tllm_gemm_params_t* p, const void* residual, void* workspace, int64_t workspace_bytes,
+    tllm_stream_t stream);
+/* The plan tllm_gemm_stream follows for p on a device of `cus` CUs (<= 0: 256; M, N, K are read, no pointer is followed, no GPU
+ * needed): the row bucket (M rounded up to 16); K-slice s = k-bytes [s * k_slice, min(K, (s + 1) * k_slice)), k_slices of them;
+ * row group g = weight rows [16 g, min(N, 16 g + 16)), row_groups of them; workgroup (x, s) of the grid (grid_x, k_slices) walks
+ * the quads x, x + grid_x, .. of four consecutive groups, at most groups_per_workgroup groups, against the activation panel of
+ * its slice; lds_bytes = the four waves' weight rings + that panel; workspace_bytes = k_slices * row_groups * (bucket / 16) * 1024.
+ * Any output pointer may be NULL.  Non-zero: M or K refused as above. */
+int32_t tllm_gemm_stream_layout(const tllm_gemm_params_t* p, int32_t cus, int64_t* workspace_bytes, int32_t* k_slices,
+    int32_t* k_slice, int32_t* row_groups, int32_t* groups_per_workgroup, int32_t* grid_x, int32_t* lds_bytes);
+/* Tests and sweeps: tllm_gemm_stream plans for `cus` CUs instead of the device's (0 = the device's again). */
+void tllm_gemm_stream_set_cus(int32_t cus);
 /* EXACTLY this kernel or nothing (parity tests: a forced id that refuses the problem must not fall back silently).  Returns 0
  * when the kernel was launched, 1 when it does not serve the problem (reason in the last-error string, c not written), a
  * negative value on a launch error.  kernel_id: 1..65 as tllm_gemm_set_tile_cfg takes them (the ablations 21..27 / 31..33 are

@@ -535,6 +535,25 @@ int launch_gemm(const GemmParams& p, hipStream_t stream);
 // fc and gate projections of the SmoothQuant MLP in one kernel with SwiGLU + static int8 quantisation in its epilogue
 // (gemm_sqp.hip); returns 1 when the problem is not served (caller runs the two GEMMs + launch_swiglu_quant instead)
 int launch_gemm_swiglu(const GemmParams& p, hipStream_t stream);
+// SmoothQuant GEMM for 9 <= M <= 64 rows as a weight stream on the matrix pipe (kernels/gemm_stream_sq.hip):
+// every weight byte from HBM once, an activation panel A[bucket, K-slice] resident in LDS, K split across workgroups, the exact
+// int32 partial sums combined through the caller's workspace by a second launch.  Bit for bit the rule of the other SmoothQuant
+// GEMMs: float(sum) * (s_col * s_row), one rounding, then the residual add in fp16.
+// The plan (pure host code): bucket = M rounded up to 16; slice s covers k-bytes [s * k_slice, min(K, (s + 1) * k_slice)); row
+// group g covers weight rows [16 g, min(N, 16 g + 16)); workgroup (x, s) walks the quads x, x + grid_x, .. of four groups each,
+// at most groups_per_workgroup groups.  cus <= 0: 256.  refused set: nothing else is.
+struct GemmStreamPlan
+{
+    int32_t bucket = 0, k_slice = 0, k_slices = 0, row_groups = 0, groups_per_workgroup = 0, grid_x = 0, lds_bytes = 0;
+    int64_t workspace_bytes = 0; // k_slices * row_groups * (bucket / 16) fragments of 1 KB
+    const char* refused = nullptr;
+};
+GemmStreamPlan gemm_stream_plan(int32_t M, int32_t N, int32_t K, int32_t cus);
+// p: W_INT8_SQ, int8 A as given, fp16 or fp32 output, optional fp16 residual (may alias c); workspace: device, 16-byte aligned,
+// >= the plan's workspace_bytes for the current device's CU count, written before it is read.  0 launched, -1 launch error,
+// 1 refused with the reason as the error string and nothing enqueued.
+int launch_gemm_stream(const GemmParams& p, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+void gemm_stream_set_cus(int cus); // tests and sweeps: plan for this CU count instead of the device's (0 = the device's)
 // On-device tactic selection for the prefill GEMMs (gemm_tactics.hip; reference: int8_gemm_template.h:372-457 profileGemm +
 // smoothQuantGemmPlugin.cpp:253-282 mMNKProfileMap).  lookup: kernel id for the shape, 0 = nothing profiled (static rule).
 int gemm_tactic_lookup(int wtype, int M, int N, int K);

@@ -563,6 +563,17 @@ int32_t tllm_session_append_split_launches(tllm_session_t s, int64_t* count)
     return 0;
 }
 
+int32_t tllm_session_stream_gemm_launches(tllm_session_t s, int64_t* count)
+{
+    if (!s || !s->B || !count)
+    {
+        set_error("tllm_session_stream_gemm_launches: setup not called, or count is null");
+        return 1;
+    }
+    *count = s->stream_gemm_launches;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ speculative decoding
 // What a session must be for a verify pass.  The greedy entries refuse a sampling configuration that is not plain arg-max (their
 // accept rule compares with the arg-max); the *_sampled entries take it.

@@ -148,6 +148,10 @@ struct tllm_session
     // session key append_split (a key of the runtime too): every pass through append_attention() runs the split-KV kernel
     // (kernels/append_attn_split.hip) whenever Dh is 64 / 128 and the pass's N <= 32, else the rule as before.  The linear cache only
     bool append_split = false;
+    // session key stream_gemm (a key of the runtime; SmoothQuant engines only): gemm() sends the projections of 9 <= M <= 64 rows
+    // to the weight-streaming kernel (kernels/gemm_stream_sq.hip) - every pass through context_layer with that many rows.  The dual
+    // SwiGLU GEMM of context_gate_up (static scales, M >= 32) is not a gemm() call and stays
+    bool stream_gemm = false;
     size_t kv_elems = 0; // elements of one layer's cache / pool
     bool force_comm = false; // tests: run the TP collectives on a 1-rank communicator too (RCCL inside the captured graph)
     // session key no_comm = 1: a rank's launches WITHOUT its collectives (all-reduces and the logits all-gather are skipped, nothing
@@ -196,6 +200,9 @@ struct tllm_session
     int64_t append_split_launches = 0; // and those the key append_split sent to the split-KV kernel (counted here alone)
     void* append_split_ws = nullptr;   // its partials: sized at setup for N = 32 and the finest plan of Smax
     int64_t append_split_ws_bytes = 0;
+    int64_t stream_gemm_launches = 0; // gemm() calls the key stream_gemm sent to the weight-streaming kernel since setup
+    void* stream_gemm_ws = nullptr;   // its partial sums: sized at setup for M = 64 and the layer's four shapes
+    int64_t stream_gemm_ws_bytes = 0;
     const float* rope = nullptr;
     int rope_len = 0;
     float* rope_row = nullptr; // [B, Dh/2, 2]: cos/sin row of the next generation step (written by the sampler)

@@ -36,6 +36,21 @@ int tllm_session::gemm(const Linear& L, int M, const void* a, void* c, int out_d
     g.per_token = dyn;
     g.c = c;
     g.ldc = L.N;
+    if (stream_gemm_ws && L.wtype == W_INT8_SQ && M >= 9 && M <= 64 && !silu_gate && (M <= 32 || L.N < 2 * L.K))
+    {
+        // session key stream_gemm: the weight-streaming kernel where it serves the shape (same bits), else as before.  Beyond 32
+        // rows a projection with N >= 2 K stays on the prefill GEMM: measured equal within the spread there (12288 x 4096 and
+        // 11008 x 4096 at M = 48 / 64: 19.8 - 22.1 against 20.7 - 22.0 us, profiles/stream_gemm.txt)
+        const int rc = launch_gemm_stream(g, stream_gemm_ws, stream_gemm_ws_bytes, st);
+        if (rc < 0)
+            return 1;
+        if (rc == 0)
+        {
+            ++stream_gemm_launches;
+            return 0;
+        }
+        set_error("%s", ""); // not served: its reason must not stay behind for a later, unrelated failure
+    }
     return launch_gemm(g, st) ? 1 : 0;
 }
 

@@ -120,6 +120,27 @@ int tllm_session::alloc_buffers()
         append_split_ws_bytes = append_split_workspace_max(Dh, kVerifyMaxTokens, B, Hr, Hkvr, Smax, cus);
         RUN(dalloc(&append_split_ws, (size_t) append_split_ws_bytes));
     }
+    stream_gemm_launches = 0;
+    stream_gemm_ws = nullptr;
+    stream_gemm_ws_bytes = 0;
+    if (stream_gemm && !layers.empty())
+    {
+        // the most any row bucket asks for on this device over the layer's shapes (a shape the kernel refuses asks for nothing:
+        // gemm() sends it on as before)
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            cus = 0; // (the launcher's own fallback: 256)
+        const Layer& L0 = layers[0];
+        for (const Linear* l : {&L0.qkv, &L0.dense, &L0.fc, &L0.gate, &L0.proj})
+            for (int m = 16; m <= 64; m += 16)
+            {
+                const GemmStreamPlan plan = gemm_stream_plan(m, l->N, l->K, cus);
+                if (!plan.refused)
+                    stream_gemm_ws_bytes = std::max(stream_gemm_ws_bytes, plan.workspace_bytes);
+            }
+        if (stream_gemm_ws_bytes > 0)
+            RUN(dalloc(&stream_gemm_ws, (size_t) stream_gemm_ws_bytes));
+    }
     has_context = false;
     cum_log_probs = nullptr;
     parent_ids = cache_ind = nullptr;

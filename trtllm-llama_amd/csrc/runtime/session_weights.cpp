@@ -196,6 +196,14 @@ tllm_session_t tllm_session_create(const char* config_text)
                   "the linear cache only)");
         return nullptr;
     }
+    s->stream_gemm = geti("stream_gemm", 0) != 0;
+    if (s->stream_gemm && !((s->quant_mode & QM_ACTIVATIONS) && (s->quant_mode & QM_INT8_WEIGHTS)))
+    {
+        set_error("tllm_session_create: stream_gemm = 1 needs a SmoothQuant engine (quant_mode %d has no int8 activations x int8 "
+                  "weights): the weight-streaming GEMM serves int8 x int8 only",
+            s->quant_mode);
+        return nullptr;
+    }
     if (kv.count("rms_norm_eps"))
         s->eps = (float) atof(kv["rms_norm_eps"].c_str());
     if (kv.count("weight_only_precision"))
@@ -569,9 +577,9 @@ tllm_session_t tllm_session_load_engine_keys(const void* engine, size_t nbytes, 
                 continue;
             const size_t e = eq == std::string::npos ? std::string::npos : line.find_last_not_of(" \t\r", eq - 1);
             const std::string key = eq == std::string::npos || eq == a ? std::string() : line.substr(a, e - a + 1);
-            if (key != "paged_append" && key != "append_split")
+            if (key != "paged_append" && key != "append_split" && key != "stream_gemm")
             {
-                set_error("tllm_session_load_engine_keys: '%s' is not a runtime key (paged_append, append_split); the engine header holds the rest",
+                set_error("tllm_session_load_engine_keys: '%s' is not a runtime key (paged_append, append_split, stream_gemm); the engine header holds the rest",
                     line.c_str());
                 return nullptr;
             }

@@ -52,6 +52,9 @@ def parse_arguments(args=None):
     p.add_argument('--append_split_kv', action='store_true',
                    help='run the append / verify passes of N <= 32 ids on the split-KV attention kernel (session key append_split; '
                    'head sizes 64 / 128, the linear cache)')
+    p.add_argument('--stream_gemm', action='store_true',
+                   help='SmoothQuant engines: run the projections of 9 to 64 rows (append / verify passes, short prompts) on the '
+                   'weight-streaming GEMM (session key stream_gemm; the same tokens)')
     # LoRA adapters (an engine built with --lora_max_rank): HF PEFT directories go into slots 0, 1, ... in the order given
     p.add_argument('--lora_dir', type=str, nargs='+', default=None, help='HF PEFT adapter directories (adapter_config.json + '
                    'adapter_model.safetensors)')
@@ -60,7 +63,7 @@ def parse_arguments(args=None):
     return p.parse_args(args)
 
 
-def load_session(engine_dir, append_split=False):
+def load_session(engine_dir, append_split=False, stream_gemm=False):
     with open(Path(engine_dir) / 'config.json') as f:
         config = json.load(f)
     bc = config['builder_config']
@@ -87,15 +90,15 @@ def load_session(engine_dir, append_split=False):
     path = Path(engine_dir) / get_engine_name('llama', dtype, world_size, runtime_rank)
     with open(path, 'rb') as f:
         engine_buffer = f.read()
-    return GenerationSession(model_config, engine_buffer, mapping, append_split=append_split), runtime_rank
+    return GenerationSession(model_config, engine_buffer, mapping, append_split=append_split, stream_gemm=stream_gemm), runtime_rank
 
 
 def generate(max_output_len, log_level='error', engine_dir='llama_outputs', input_text=None, input_file=None,
              output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55, top_k=1, top_p=0.0,
              temperature=1.0, repetition_penalty=1.0, random_seed=None, prompt_lookup_tokens=0, prompt_lookup_ngram=3,
-             prompt_lookup_sampling=False, lora_dir=None, lora_slots=None, append_split_kv=False):
+             prompt_lookup_sampling=False, lora_dir=None, lora_slots=None, append_split_kv=False, stream_gemm=False):
     tensorrt_llm.logger.set_level(log_level)
-    decoder, runtime_rank = load_session(engine_dir, append_split=append_split_kv)
+    decoder, runtime_rank = load_session(engine_dir, append_split=append_split_kv, stream_gemm=stream_gemm)
     for slot, d in enumerate(lora_dir or []):
         decoder.load_lora(d, slot)
     if isinstance(lora_slots, str):

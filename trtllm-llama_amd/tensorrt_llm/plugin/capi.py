@@ -85,6 +85,14 @@ class AttentionParams(ctypes.Structure):
                 ('workspace', ctypes.c_void_p)]
 
 
+class GemmParams(ctypes.Structure):
+    """tllm_gemm_params_t (include/tllm_runtime_api.h): the argument of tllm_gemm, tllm_gemm_stream and their kin."""
+    _fields_ = [('wtype', ctypes.c_int32), ('out_dtype', ctypes.c_int32), ('M', ctypes.c_int32), ('N', ctypes.c_int32),
+                ('K', ctypes.c_int32), ('a', ctypes.c_void_p), ('lda', ctypes.c_int64), ('w', ctypes.c_void_p),
+                ('ldw', ctypes.c_int64), ('scale_col', ctypes.c_void_p), ('scale_row', ctypes.c_void_p),
+                ('per_channel', ctypes.c_int32), ('per_token', ctypes.c_int32), ('c', ctypes.c_void_p), ('ldc', ctypes.c_int64)]
+
+
 _lib = None
 
 
@@ -161,6 +169,12 @@ def load_library():
     lib.tllm_symmetric_quantize_last_axis.restype = c.c_int32
     lib.tllm_preprocess_weights_for_mixed_gemm.argtypes = [c.c_void_p, c.c_int64, c.c_int64, c.c_int32, c.c_void_p]
     lib.tllm_preprocess_weights_for_mixed_gemm.restype = c.c_int32
+    lib.tllm_gemm_stream.argtypes = [c.POINTER(GemmParams), c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
+    lib.tllm_gemm_stream.restype = c.c_int32
+    lib.tllm_gemm_stream_layout.argtypes = [c.POINTER(GemmParams), c.c_int32, c.POINTER(c.c_int64)] + [c.POINTER(c.c_int32)] * 6
+    lib.tllm_gemm_stream_layout.restype = c.c_int32
+    lib.tllm_gemm_stream_set_cus.argtypes = [c.c_int32]
+    lib.tllm_gemm_stream_set_cus.restype = None
     if not lib.initLibNvInferPlugins(None, TRT_LLM_PLUGIN_NAMESPACE.encode('utf-8')):
         raise RuntimeError('initLibNvInferPlugins failed')
     _lib = lib

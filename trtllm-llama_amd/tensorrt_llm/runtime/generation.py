@@ -55,7 +55,8 @@ class SamplingConfig:
 
 class GenerationSession(object):
 
-    def __init__(self, model_config: ModelConfig, engine_buffer, mapping: Mapping, debug_mode=False, append_split=False):
+    def __init__(self, model_config: ModelConfig, engine_buffer, mapping: Mapping, debug_mode=False, append_split=False,
+                 stream_gemm=False):
         assert isinstance(model_config, ModelConfig)
         if not model_config.gpt_attention_plugin:
             raise ValueError('the MI355X LLaMA path needs the gpt_attention plugin (RoPE lives in it)')
@@ -67,19 +68,22 @@ class GenerationSession(object):
         if mapping.tp_size > 1:
             from ..parallel import ensure_tp_communicator
             ensure_tp_communicator(mapping)
-        self.runtime = NativeSession(engine=bytes(engine_buffer), runtime_keys=self._runtime_keys(model_config, append_split))
+        self.runtime = NativeSession(engine=bytes(engine_buffer), runtime_keys=self._runtime_keys(model_config, append_split, stream_gemm))
         self.runtime.vocab = model_config.vocab_size
         self.batch_size = self.max_input_length = self.max_new_tokens = 0
 
     @staticmethod
-    def _runtime_keys(model_config: ModelConfig, append_split=False) -> dict:
+    def _runtime_keys(model_config: ModelConfig, append_split=False, stream_gemm=False) -> dict:
         """Session keys that belong to the runtime and not to the engine header.  paged_append: a paged engine serves append(),
         verify() and decode_lookup() on its block table (the key is refused on a linear cache, so only a paged engine gets it).
         append_split: those passes run the split-KV attention kernel at N <= 32 ids (the linear cache only: the session refuses
-        the key on a paged engine by name)."""
+        the key on a paged engine by name).  stream_gemm: the projections of 9 .. 64 rows - the same passes, and short prompts -
+        run the weight-streaming SmoothQuant GEMM, same bits (the session refuses the key on any other engine by name)."""
         keys = dict(paged_append=1) if model_config.paged_kv_cache else {}
         if append_split:
             keys['append_split'] = 1
+        if stream_gemm:
+            keys['stream_gemm'] = 1
         return keys
 
     @property

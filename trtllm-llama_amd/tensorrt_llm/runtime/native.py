@@ -125,6 +125,8 @@ def _lib():
     lib.tllm_attention_append_split_layout.restype = c.c_int32
     lib.tllm_session_append_split_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
     lib.tllm_session_append_split_launches.restype = c.c_int32
+    lib.tllm_session_stream_gemm_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
+    lib.tllm_session_stream_gemm_launches.restype = c.c_int32
     lib.tllm_session_verify.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.tllm_session_verify.restype = c.c_int32
     lib.tllm_session_verify_top1.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
@@ -471,8 +473,8 @@ class NativeSession:
 
     def __init__(self, config: Optional[Dict] = None, engine: Optional[bytes] = None, runtime_keys: Optional[Dict] = None):
         """config: the session keys; or engine: a serialized engine, whose header holds them - then runtime_keys adds the keys
-        that belong to the runtime and not to the engine (paged_append, append_split; tllm_session_load_engine_keys refuses every
-        other)."""
+        that belong to the runtime and not to the engine (paged_append, append_split, stream_gemm; tllm_session_load_engine_keys
+        refuses every other)."""
         lib = _lib()
         self._keep = []  # torch tensors whose device memory the session references
         if engine is not None:
@@ -732,6 +734,12 @@ class NativeSession:
         """attention launches the session key append_split has sent to the split-KV kernel since setup (one per layer and pass)"""
         n = ctypes.c_int64()
         _check(_lib().tllm_session_append_split_launches(self._h, ctypes.byref(n)), 'append_split_launches')
+        return int(n.value)
+
+    def stream_gemm_launches(self):
+        """GEMM calls the session key stream_gemm has sent to the weight-streaming kernel since setup (9 .. 64 rows, SmoothQuant)"""
+        n = ctypes.c_int64()
+        _check(_lib().tllm_session_stream_gemm_launches(self._h, ctypes.byref(n)), 'stream_gemm_launches')
         return int(n.value)
 
     attention_append = staticmethod(attention_append)
