@@ -51,11 +51,13 @@ typedef struct tllm_session* tllm_session_t;
  *   pass follows
  *   the rule as before, and a session without the key launches exactly what it launched before.  Same rule, another summation
  *   order: results agree within the kernels' bound.  A key of the runtime: tllm_session_load_engine_keys takes it),
- *   stream_gemm (0; 1, SmoothQuant engines only - any other quant_mode refuses it by name: every layer projection of 9 <= M <= 64
+ *   stream_gemm (0; 1, SmoothQuant and weight-only int8 / int4 engines - fp16 refuses it by name: every layer projection of 9 <= M <= 64
  *   rows - the passes listed under paged_append at B * N rows in that range, and prompts that short - runs the weight-streaming
  *   GEMM (tllm_gemm_stream) from a workspace allocated at setup for M = 64 and the layer's shapes; a shape that kernel refuses,
  *   the dual SwiGLU GEMM of static scales at M >= 32 and every other M run what they ran before.  Integer sums, the same scaling
  *   and rounding: results are bit for bit those of a session without the key, which launches exactly what it launched before.
+ *   Weight-only engines send the M ranges and shapes where the stream measured faster (session_context.cpp gemm()), the calls
+ *   with a residual or a SwiGLU gate included; fp32 partial sums in another order: results agree within the kernels' bound.
  *   A key of the runtime: tllm_session_load_engine_keys takes it),
  *   debug_taps (0; 1: keep per-layer intermediates of the generation step for tllm_session_get_tap),
  *   gemm_tactics (optional; the table tllm_gemm_tactics_export wrote, as the builder stores it in the engine).
@@ -648,11 +650,22 @@ int32_t tllm_gemm_epi(const tllm_gemm_params_t* p, const void* residual, const v
  * below N or not a multiple of 4; a workspace that is NULL, misaligned or too small.  Negative: a launch error. */
 int32_t tllm_gemm_stream(const tllm_gemm_params_t* p, const void* residual, void* workspace, int64_t workspace_bytes,
     tllm_stream_t stream);
+/* The weight-only types, wtype 1 (int8) and 2 (int4), take the same stream (kernels/gemm_stream_woq.hip) through both entry
+ * points: fp16 A (lda in elements, a multiple of 8), the weights in the engine's own layout (no fp16 image, no re-laying), fp16
+ * per-channel scales; u8 / nibbles are dequantised in registers between the LDS ring and the fp16 MFMA, products exact, fp32
+ * accumulation, the scale once in the epilogue.  The fp32 partial sums of the K-slices are added in slice order: two runs give the
+ * same bits, and the result is tllm_gemm's within the weight-only kernels' bound (another summation order), not bit for bit.
+ * tllm_gemm_stream_epi adds the gate operand of tllm_gemm_epi: c = silu_mul_fp16(silu_gate, v), fp16 output, silu_gate [M, ldc]
+ * fp16 (it may be p->c), not together with a residual; wtype 3 with a gate is refused. */
+int32_t tllm_gemm_stream_epi(const tllm_gemm_params_t* p, const void* residual, const void* silu_gate, void* workspace,
+    int64_t workspace_bytes, tllm_stream_t stream);
 /* The plan tllm_gemm_stream follows for p on a device of `cus` CUs (<= 0: 256; M, N, K are read, no pointer is followed, no GPU
  * needed): the row bucket (M rounded up to 16); K-slice s = k-bytes [s * k_slice, min(K, (s + 1) * k_slice)), k_slices of them;
  * row group g = weight rows [16 g, min(N, 16 g + 16)), row_groups of them; workgroup (x, s) of the grid (grid_x, k_slices) walks
  * the quads x, x + grid_x, .. of four consecutive groups, at most groups_per_workgroup groups, against the activation panel of
  * its slice; lds_bytes = the four waves' weight rings + that panel; workspace_bytes = k_slices * row_groups * (bucket / 16) * 1024.
+ * wtype 1 / 2: the plan of the weight-only stream - k_slice in k-elements, lds_bytes = 65536 + bucket * 2 * (k_slice rounded up
+ * to 256), the same workspace formula; any other wtype: the SmoothQuant plan.
  * Any output pointer may be NULL.  Non-zero: M or K refused as above. */
 int32_t tllm_gemm_stream_layout(const tllm_gemm_params_t* p, int32_t cus, int64_t* workspace_bytes, int32_t* k_slices,
     int32_t* k_slice, int32_t* row_groups, int32_t* groups_per_workgroup, int32_t* grid_x, int32_t* lds_bytes);

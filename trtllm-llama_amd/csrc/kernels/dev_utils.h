@@ -104,6 +104,27 @@ __device__ __forceinline__ uint32_t h2_as_u32(h2_t h)
     return r;
 }
 
+// Weight-only dequantisation in registers (gemm_woq.hip, gemm_stream_woq.hip): exact integers in fp16.
+// 4 bytes u = q + 128 -> 4 fp16 q (two words), exactly: 0x6400 | u = 1024 + u, minus 1152
+__device__ __forceinline__ void deq_u8x4(uint32_t w, uint32_t& lo, uint32_t& hi)
+{
+    const uint32_t magic = 0x64646464u;
+    const h2_t bias = {(_Float16) 1152.f, (_Float16) 1152.f};
+    lo = h2_as_u32(u32_as_h2(__builtin_amdgcn_perm(magic, w, 0x04010400u)) - bias);
+    hi = h2_as_u32(u32_as_h2(__builtin_amdgcn_perm(magic, w, 0x04030402u)) - bias);
+}
+
+// 8 nibbles n = q + 8 of one word (order e0 e2 e4 e6 | e1 e3 e5 e7, weight_layout.h) -> 8 fp16 q in element order
+__device__ __forceinline__ uint4 deq_u4x8(uint32_t w)
+{
+    const uint32_t m = 0x64006400u, w8 = w >> 8;
+    const h2_t b0 = {(_Float16) 1032.f, (_Float16) 1032.f};
+    const h2_t s1 = {(_Float16) 0.0625f, (_Float16) 0.0625f};
+    const h2_t b1 = {(_Float16) -72.f, (_Float16) -72.f};
+    return make_uint4(h2_as_u32(u32_as_h2((w & 0x000f000fu) | m) - b0), h2_as_u32(u32_as_h2((w & 0x00f000f0u) | m) * s1 + b1),
+        h2_as_u32(u32_as_h2((w8 & 0x000f000fu) | m) - b0), h2_as_u32(u32_as_h2((w8 & 0x00f000f0u) | m) * s1 + b1));
+}
+
 __device__ __forceinline__ uint32_t pack_h2(float lo, float hi)
 {
     h2_t r;

@@ -267,6 +267,11 @@ void gemm_stream_set_cus(int cus)
     stream_cus_override = cus > 0 ? cus : 0;
 }
 
+int gemm_stream_cus()
+{
+    return stream_cus_override ? stream_cus_override : launch_util::device_cus();
+}
+
 GemmStreamPlan gemm_stream_plan(int32_t M, int32_t N, int32_t K, int32_t cus)
 {
     GemmStreamPlan plan;
@@ -324,7 +329,7 @@ int launch_gemm_stream(const GemmParams& p, void* workspace, int64_t workspace_b
     auto misaligned = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
     if (p.wtype != W_INT8_SQ)
         return refuse("the weight type is not SmoothQuant int8 (W_INT8_SQ)");
-    const int cus = stream_cus_override ? stream_cus_override : launch_util::device_cus();
+    const int cus = gemm_stream_cus();
     const GemmStreamPlan plan = gemm_stream_plan(p.M, p.N, p.K, cus);
     if (plan.refused)
         return refuse(plan.refused);

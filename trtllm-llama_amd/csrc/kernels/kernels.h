@@ -554,6 +554,18 @@ GemmStreamPlan gemm_stream_plan(int32_t M, int32_t N, int32_t K, int32_t cus);
 // 1 refused with the reason as the error string and nothing enqueued.
 int launch_gemm_stream(const GemmParams& p, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 void gemm_stream_set_cus(int cus); // tests and sweeps: plan for this CU count instead of the device's (0 = the device's)
+int gemm_stream_cus();              // the CU count the stream launchers plan for
+// The same stream for the weight-only types (kernels/gemm_stream_woq.hip): W_INT8_WOQ / W_INT4_WOQ in the layouts of
+// weight_layout.h, fp16 A, launch_gemm's rule for these types - v = (sum_k A16 * q) * s16[n] with exact products and fp32
+// accumulation, then fp16(v) | fp32 v | fp16(fp16(v) + residual16) | silu_mul_fp16(silu_gate16, v).  u8 / nibbles go HBM -> LDS
+// ring -> registers, where deq_u8x4 / deq_u4x8 turn them into fp16 MFMA fragments; the fp32 partial sums of the K-slices meet in
+// the workspace and are added in slice order (deterministic; within the bound of the other weight-only GEMMs, not their bits).
+// The plan has gemm_stream_plan's fields, k_slice in k-elements: lds_bytes = 65536 + bucket * 2 * (k_slice rounded up to 256),
+// workspace_bytes = k_slices * row_groups * (bucket / 16) * 1024.
+GemmStreamPlan gemm_stream_woq_plan(int32_t M, int32_t N, int32_t K, int32_t wtype, int32_t cus);
+// p: W_INT8_WOQ / W_INT4_WOQ, fp16 A (lda in elements, a multiple of 8), fp16 scale_col [N], fp16 or fp32 output, optional fp16
+// residual (may alias c) or silu_gate (fp16 [M, ldc]; may alias c); the workspace as launch_gemm_stream's.  Same return values.
+int launch_gemm_stream_woq(const GemmParams& p, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 // On-device tactic selection for the prefill GEMMs (gemm_tactics.hip; reference: int8_gemm_template.h:372-457 profileGemm +
 // smoothQuantGemmPlugin.cpp:253-282 mMNKProfileMap).  lookup: kernel id for the shape, 0 = nothing profiled (static rule).
 int gemm_tactic_lookup(int wtype, int M, int N, int K);

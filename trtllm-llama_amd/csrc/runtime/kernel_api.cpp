@@ -625,9 +625,27 @@ int32_t tllm_gemm_stream(const tllm_gemm_params_t* q, const void* residual, void
         set_error("tllm_gemm_stream: null argument");
         return 1;
     }
+    if (q->wtype == W_INT8_WOQ || q->wtype == W_INT4_WOQ)
+        return tllm_gemm_stream_epi(q, residual, nullptr, workspace, workspace_bytes, stream);
     GemmParams g = gemm_params(q);
     g.residual = residual;
     return launch_gemm_stream(g, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+int32_t tllm_gemm_stream_epi(const tllm_gemm_params_t* q, const void* residual, const void* silu_gate, void* workspace,
+    int64_t workspace_bytes, tllm_stream_t stream)
+{
+    if (!q)
+    {
+        set_error("tllm_gemm_stream_epi: null argument");
+        return 1;
+    }
+    GemmParams g = gemm_params(q);
+    g.residual = residual;
+    g.silu_gate = silu_gate;
+    if (g.wtype == W_INT8_WOQ || g.wtype == W_INT4_WOQ)
+        return launch_gemm_stream_woq(g, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+    return launch_gemm_stream(g, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream)); // W_INT8_SQ, or its refusal
 }
 
 int32_t tllm_gemm_stream_layout(const tllm_gemm_params_t* q, int32_t cus, int64_t* workspace_bytes, int32_t* k_slices,
@@ -638,7 +656,8 @@ int32_t tllm_gemm_stream_layout(const tllm_gemm_params_t* q, int32_t cus, int64_
         set_error("tllm_gemm_stream_layout: null argument");
         return 1;
     }
-    const GemmStreamPlan plan = gemm_stream_plan(q->M, q->N, q->K, cus);
+    const bool woq = q->wtype == W_INT8_WOQ || q->wtype == W_INT4_WOQ;
+    const GemmStreamPlan plan = woq ? gemm_stream_woq_plan(q->M, q->N, q->K, q->wtype, cus) : gemm_stream_plan(q->M, q->N, q->K, cus);
     if (plan.refused)
     {
         set_error("tllm_gemm_stream_layout: %d x %d x %d refused: %s", q->M, q->N, q->K, plan.refused);

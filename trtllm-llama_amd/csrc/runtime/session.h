@@ -148,8 +148,8 @@ struct tllm_session
     // session key append_split (a key of the runtime too): every pass through append_attention() runs the split-KV kernel
     // (kernels/append_attn_split.hip) whenever Dh is 64 / 128 and the pass's N <= 32, else the rule as before.  The linear cache only
     bool append_split = false;
-    // session key stream_gemm (a key of the runtime; SmoothQuant engines only): gemm() sends the projections of 9 <= M <= 64 rows
-    // to the weight-streaming kernel (kernels/gemm_stream_sq.hip) - every pass through context_layer with that many rows.  The dual
+    // session key stream_gemm (a key of the runtime; SmoothQuant and weight-only int8 / int4 engines): gemm() sends the projections of 9 <= M <= 64 rows
+    // to the weight-streaming kernel (kernels/gemm_stream_sq.hip, gemm_stream_woq.hip) - every pass through context_layer with that many rows.  The dual
     // SwiGLU GEMM of context_gate_up (static scales, M >= 32) is not a gemm() call and stays
     bool stream_gemm = false;
     size_t kv_elems = 0; // elements of one layer's cache / pool

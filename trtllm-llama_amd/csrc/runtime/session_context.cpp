@@ -51,6 +51,24 @@ int tllm_session::gemm(const Linear& L, int M, const void* a, void* c, int out_d
         }
         set_error("%s", ""); // not served: its reason must not stay behind for a later, unrelated failure
     }
+    const bool woq = L.wtype == W_INT8_WOQ || L.wtype == W_INT4_WOQ;
+    if (stream_gemm_ws && woq && M >= 9 && M <= 64)
+    {
+        // the same key on a weight-only engine (kernels/gemm_stream_woq.hip), the calls with a residual or a SwiGLU gate included:
+        // within the weight-only kernels' bound of launch_gemm's result (fp32 partial sums in another order), not its bits.  The
+        // whole range and every shape class: the stream measured faster than launch_gemm by 7 spreads and more at M = 16 / 32 /
+        // 48 / 64 on all four 7B shapes of both types (least at 64 rows and N >= 2 K: 31 against 37 - 39 us; profiles/
+        // stream_gemm_woq.txt), so unlike the SmoothQuant rule above there is no M or shape condition
+        const int rc = launch_gemm_stream_woq(g, stream_gemm_ws, stream_gemm_ws_bytes, st);
+        if (rc < 0)
+            return 1;
+        if (rc == 0)
+        {
+            ++stream_gemm_launches;
+            return 0;
+        }
+        set_error("%s", "");
+    }
     return launch_gemm(g, st) ? 1 : 0;
 }
 

@@ -134,7 +134,8 @@ int tllm_session::alloc_buffers()
         for (const Linear* l : {&L0.qkv, &L0.dense, &L0.fc, &L0.gate, &L0.proj})
             for (int m = 16; m <= 64; m += 16)
             {
-                const GemmStreamPlan plan = gemm_stream_plan(m, l->N, l->K, cus);
+                const bool woq = l->wtype == W_INT8_WOQ || l->wtype == W_INT4_WOQ;
+                const GemmStreamPlan plan = woq ? gemm_stream_woq_plan(m, l->N, l->K, l->wtype, cus) : gemm_stream_plan(m, l->N, l->K, cus);
                 if (!plan.refused)
                     stream_gemm_ws_bytes = std::max(stream_gemm_ws_bytes, plan.workspace_bytes);
             }

@@ -197,10 +197,10 @@ tllm_session_t tllm_session_create(const char* config_text)
         return nullptr;
     }
     s->stream_gemm = geti("stream_gemm", 0) != 0;
-    if (s->stream_gemm && !((s->quant_mode & QM_ACTIVATIONS) && (s->quant_mode & QM_INT8_WEIGHTS)))
+    if (s->stream_gemm && !(s->quant_mode & (QM_INT8_WEIGHTS | QM_INT4_WEIGHTS)))
     {
-        set_error("tllm_session_create: stream_gemm = 1 needs a SmoothQuant engine (quant_mode %d has no int8 activations x int8 "
-                  "weights): the weight-streaming GEMM serves int8 x int8 only",
+        set_error("tllm_session_create: stream_gemm = 1 needs a SmoothQuant or weight-only int8 / int4 engine (quant_mode %d has "
+                  "fp16 weights): the weight-streaming GEMMs serve quantised weights only",
             s->quant_mode);
         return nullptr;
     }

@@ -53,8 +53,8 @@ def parse_arguments(args=None):
                    help='run the append / verify passes of N <= 32 ids on the split-KV attention kernel (session key append_split; '
                    'head sizes 64 / 128, the linear cache)')
     p.add_argument('--stream_gemm', action='store_true',
-                   help='SmoothQuant engines: run the projections of 9 to 64 rows (append / verify passes, short prompts) on the '
-                   'weight-streaming GEMM (session key stream_gemm; the same tokens)')
+                   help='SmoothQuant and weight-only int8 / int4 engines: run the projections of 9 to 64 rows (append / verify passes, '
+                   'short prompts) on the weight-streaming GEMM (session key stream_gemm)')
     # LoRA adapters (an engine built with --lora_max_rank): HF PEFT directories go into slots 0, 1, ... in the order given
     p.add_argument('--lora_dir', type=str, nargs='+', default=None, help='HF PEFT adapter directories (adapter_config.json + '
                    'adapter_model.safetensors)')

@@ -171,6 +171,8 @@ def load_library():
     lib.tllm_preprocess_weights_for_mixed_gemm.restype = c.c_int32
     lib.tllm_gemm_stream.argtypes = [c.POINTER(GemmParams), c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
     lib.tllm_gemm_stream.restype = c.c_int32
+    lib.tllm_gemm_stream_epi.argtypes = [c.POINTER(GemmParams), c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
+    lib.tllm_gemm_stream_epi.restype = c.c_int32
     lib.tllm_gemm_stream_layout.argtypes = [c.POINTER(GemmParams), c.c_int32, c.POINTER(c.c_int64)] + [c.POINTER(c.c_int32)] * 6
     lib.tllm_gemm_stream_layout.restype = c.c_int32
     lib.tllm_gemm_stream_set_cus.argtypes = [c.c_int32]

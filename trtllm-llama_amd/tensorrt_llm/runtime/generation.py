@@ -78,7 +78,8 @@ class GenerationSession(object):
         verify() and decode_lookup() on its block table (the key is refused on a linear cache, so only a paged engine gets it).
         append_split: those passes run the split-KV attention kernel at N <= 32 ids (the linear cache only: the session refuses
         the key on a paged engine by name).  stream_gemm: the projections of 9 .. 64 rows - the same passes, and short prompts -
-        run the weight-streaming SmoothQuant GEMM, same bits (the session refuses the key on any other engine by name)."""
+        run the weight-streaming GEMM: SmoothQuant engines with the same bits, weight-only int8 / int4 engines (LoRA sessions
+        included) within the weight-only kernels' bound (the session refuses the key on an fp16 engine by name)."""
         keys = dict(paged_append=1) if model_config.paged_kv_cache else {}
         if append_split:
             keys['append_split'] = 1

@@ -737,7 +737,7 @@ class NativeSession:
         return int(n.value)
 
     def stream_gemm_launches(self):
-        """GEMM calls the session key stream_gemm has sent to the weight-streaming kernel since setup (9 .. 64 rows, SmoothQuant)"""
+        """GEMM calls the session key stream_gemm has sent to the weight-streaming kernel since setup (9 .. 64 rows; SmoothQuant and weight-only engines)"""
         n = ctypes.c_int64()
         _check(_lib().tllm_session_stream_gemm_launches(self._h, ctypes.byref(n)), 'stream_gemm_launches')
         return int(n.value)
