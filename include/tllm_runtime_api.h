@@ -58,6 +58,14 @@ typedef struct tllm_session* tllm_session_t;
  *   and rounding: results are bit for bit those of a session without the key, which launches exactly what it launched before.
  *   Weight-only engines send the M ranges and shapes where the stream measured faster (session_context.cpp gemm()), the calls
  *   with a residual or a SwiGLU gate included; fp32 partial sums in another order: results agree within the kernels' bound.
+ *   2, every engine: what 1 does on a SmoothQuant / weight-only engine - the same kernels, routing and bits for the layer
+ *   projections - and in addition fp16 WEIGHTS on the fp16 stream (tllm_gemm_stream_f16): the projections of an fp16 engine at the
+ *   M ranges and shapes where it measured faster (session_context.cpp gemm(), residual and gate calls included), and at tp = 1 the
+ *   lm_head of every engine - fp16 in all of them - wherever 9 .. 64 rows go through it outside the generation step: the B * N
+ *   rows of tllm_session_verify / _verify_sampled and the lookup loops, a chunk of that many rows in tllm_session_score, and the B
+ *   rows behind a prompt, an append or a ragged append at batch 9 .. 64 (ln_f as a launch of its own, then one pass over the
+ *   head with fp32 logits).  The generation step keeps its GEMV slabs.  The workspace then covers the head's shape too (7B: 49 MB).
+ *   fp32 partial sums in another order: within the fp16 kernels' bound.  Any other value is refused with the key's name.
  *   A key of the runtime: tllm_session_load_engine_keys takes it),
  *   debug_taps (0; 1: keep per-layer intermediates of the generation step for tllm_session_get_tap),
  *   gemm_tactics (optional; the table tllm_gemm_tactics_export wrote, as the builder stores it in the engine).
@@ -242,8 +250,8 @@ int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* m
 /* The same for the launches the session key append_split sent to the split-KV kernel (one per layer and pass; they are counted
  * here and not in *wave / *mfma).  0 for a session without the key. */
 int32_t tllm_session_append_split_launches(tllm_session_t s, int64_t* count);
-/* GEMM calls the session key stream_gemm has sent to the weight-streaming kernel (tllm_gemm_stream) since setup.  0 for a session
- * without the key. */
+/* GEMM calls the session key stream_gemm has sent to a weight-streaming kernel (tllm_gemm_stream; under value 2 tllm_gemm_stream_f16
+ * too, one per fp16 projection and one per lm_head call it served) since setup.  0 for a session without the key. */
 int32_t tllm_session_stream_gemm_launches(tllm_session_t s, int64_t* count);
 
 /* Speculative greedy decoding (the rules are stated in csrc/kernels/kernels.h, SpecAcceptParams and
@@ -669,7 +677,26 @@ int32_t tllm_gemm_stream_epi(const tllm_gemm_params_t* p, const void* residual, 
  * Any output pointer may be NULL.  Non-zero: M or K refused as above. */
 int32_t tllm_gemm_stream_layout(const tllm_gemm_params_t* p, int32_t cus, int64_t* workspace_bytes, int32_t* k_slices,
     int32_t* k_slice, int32_t* row_groups, int32_t* groups_per_workgroup, int32_t* grid_x, int32_t* lds_bytes);
-/* Tests and sweeps: tllm_gemm_stream plans for `cus` CUs instead of the device's (0 = the device's again). */
+/* The stream for fp16 weights, wtype 0 (kernels/gemm_stream_f16.hip), through entry points of its own - tllm_gemm_stream, _epi and
+ * _layout keep refusing / ignoring wtype 0.  c [M, ldc] = fp16(v) | fp32 v | fp16(fp16(v) + residual) | silu_mul_fp16(silu_gate, v)
+ * with v = sum_k a[m, k] * w[n, k], exact products, fp32 accumulation: fp16 a [M, lda] (lda in elements), fp16 w [N, ldw] as the
+ * engine holds it (ldw in BYTES as in tllm_gemm: 2 per element), no scale.  Every weight byte crosses HBM once; the 16-byte pieces
+ * of the LDS ring are the MFMA operands.  The fp32 partial sums of the K-slices are added in slice order: two runs give the same
+ * bits, and the result is tllm_gemm's within the fp16 kernels' bound, not bit for bit.  residual and silu_gate: fp16 [M, ldc], NULL
+ * or one of them, fp16 output only, either may be p->c.  0: launched.  Positive with nothing enqueued and C untouched, the reason
+ * in tllm_last_error(): a wtype other than 0; M outside 9 .. 64; K not a multiple of 64; an output type other than fp16 / fp32; a
+ * residual or gate with fp32 output; both together; a or w not 16-byte aligned; lda below K or not a multiple of 8 elements, ldw
+ * below 2 K or not a multiple of 16 bytes (8 elements); ldc below N or not a multiple of 4; a workspace that is NULL, misaligned or
+ * smaller than tllm_gemm_stream_f16_layout's workspace_bytes for the device's CU count.  Negative: a launch error. */
+int32_t tllm_gemm_stream_f16(const tllm_gemm_params_t* p, const void* residual, const void* silu_gate, void* workspace,
+    int64_t workspace_bytes, tllm_stream_t stream);
+/* Its plan, fields as tllm_gemm_stream_layout's (no pointer of p is followed, its wtype is not read, no GPU needed): k_slice in
+ * k-elements, a multiple of the ring block of 128 (K itself when K is 64); lds_bytes = 65536 + bucket * 2 * (k_slice rounded up to
+ * 128); workspace_bytes = k_slices * row_groups * (bucket / 16) * 1024 - 49,152,000 for the 7B lm_head (32000 x 4096) at 64 rows.
+ * Any output pointer may be NULL.  Non-zero: M or K refused as above. */
+int32_t tllm_gemm_stream_f16_layout(const tllm_gemm_params_t* p, int32_t cus, int64_t* workspace_bytes, int32_t* k_slices,
+    int32_t* k_slice, int32_t* row_groups, int32_t* groups_per_workgroup, int32_t* grid_x, int32_t* lds_bytes);
+/* Tests and sweeps: tllm_gemm_stream and tllm_gemm_stream_f16 plan for `cus` CUs instead of the device's (0 = the device's again). */
 void tllm_gemm_stream_set_cus(int32_t cus);
 /* EXACTLY this kernel or nothing (parity tests: a forced id that refuses the problem must not fall back silently).  Returns 0
  * when the kernel was launched, 1 when it does not serve the problem (reason in the last-error string, c not written), a

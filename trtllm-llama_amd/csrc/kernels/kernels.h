@@ -566,6 +566,19 @@ GemmStreamPlan gemm_stream_woq_plan(int32_t M, int32_t N, int32_t K, int32_t wty
 // p: W_INT8_WOQ / W_INT4_WOQ, fp16 A (lda in elements, a multiple of 8), fp16 scale_col [N], fp16 or fp32 output, optional fp16
 // residual (may alias c) or silu_gate (fp16 [M, ldc]; may alias c); the workspace as launch_gemm_stream's.  Same return values.
 int launch_gemm_stream_woq(const GemmParams& p, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+// The same stream for fp16 weights (kernels/gemm_stream_f16.hip): W_FP16 [N, ldw] as the engine holds it, fp16 A, launch_gemm's rule
+// for the type on another summation order - v = sum_k A16 * W16 with exact products and fp32 accumulation, no scale, then
+// fp16(v) | fp32 v | fp16(fp16(v) + residual16) | silu_mul_fp16(silu_gate16, v).  The ring's 16-byte pieces are the MFMA operands:
+// HBM -> LDS ring -> ds_read_b128 -> v_mfma_f32_16x16x32_f16; the fp32 partial sums of the K-slices meet in the workspace and are
+// added in slice order (deterministic; within the bound of the other fp16 GEMMs, not their bits).
+// The plan has gemm_stream_plan's fields, k_slice in k-elements and a multiple of 128 (K itself below 128): lds_bytes = 65536 +
+// bucket * 2 * (k_slice rounded up to 128), workspace_bytes = k_slices * row_groups * (bucket / 16) * 1024 - for the 7B lm_head
+// (32000 x 4096) at most 49,152,000 bytes (M = 64: 6 slices).
+GemmStreamPlan gemm_stream_f16_plan(int32_t M, int32_t N, int32_t K, int32_t cus);
+// p: W_FP16 (ldw in bytes, >= 2 K, a multiple of 16), fp16 A (lda in elements, a multiple of 8), fp16 or fp32 output, optional
+// fp16 residual (may alias c) or silu_gate (fp16 [M, ldc]; may alias c), K a multiple of 64; the workspace as launch_gemm_stream's.
+// Same return values: 0 launched, 1 refused with the reason as the error string and nothing enqueued, -1 launch error.
+int launch_gemm_stream_f16(const GemmParams& p, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 // On-device tactic selection for the prefill GEMMs (gemm_tactics.hip; reference: int8_gemm_template.h:372-457 profileGemm +
 // smoothQuantGemmPlugin.cpp:253-282 mMNKProfileMap).  lookup: kernel id for the shape, 0 = nothing profiled (static rule).
 int gemm_tactic_lookup(int wtype, int M, int N, int K);

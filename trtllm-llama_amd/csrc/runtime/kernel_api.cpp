@@ -680,6 +680,51 @@ int32_t tllm_gemm_stream_layout(const tllm_gemm_params_t* q, int32_t cus, int64_
     return 0;
 }
 
+int32_t tllm_gemm_stream_f16(const tllm_gemm_params_t* q, const void* residual, const void* silu_gate, void* workspace,
+    int64_t workspace_bytes, tllm_stream_t stream)
+{
+    if (!q)
+    {
+        set_error("tllm_gemm_stream_f16: null argument");
+        return 1;
+    }
+    GemmParams g = gemm_params(q);
+    g.residual = residual;
+    g.silu_gate = silu_gate;
+    return launch_gemm_stream_f16(g, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+int32_t tllm_gemm_stream_f16_layout(const tllm_gemm_params_t* q, int32_t cus, int64_t* workspace_bytes, int32_t* k_slices,
+    int32_t* k_slice, int32_t* row_groups, int32_t* groups_per_workgroup, int32_t* grid_x, int32_t* lds_bytes)
+{
+    if (!q)
+    {
+        set_error("tllm_gemm_stream_f16_layout: null argument");
+        return 1;
+    }
+    const GemmStreamPlan plan = gemm_stream_f16_plan(q->M, q->N, q->K, cus);
+    if (plan.refused)
+    {
+        set_error("tllm_gemm_stream_f16_layout: %d x %d x %d refused: %s", q->M, q->N, q->K, plan.refused);
+        return 1;
+    }
+    if (workspace_bytes)
+        *workspace_bytes = plan.workspace_bytes;
+    if (k_slices)
+        *k_slices = plan.k_slices;
+    if (k_slice)
+        *k_slice = plan.k_slice;
+    if (row_groups)
+        *row_groups = plan.row_groups;
+    if (groups_per_workgroup)
+        *groups_per_workgroup = plan.groups_per_workgroup;
+    if (grid_x)
+        *grid_x = plan.grid_x;
+    if (lds_bytes)
+        *lds_bytes = plan.lds_bytes;
+    return 0;
+}
+
 void tllm_gemm_stream_set_cus(int32_t cus)
 {
     gemm_stream_set_cus(cus);

@@ -148,10 +148,13 @@ struct tllm_session
     // session key append_split (a key of the runtime too): every pass through append_attention() runs the split-KV kernel
     // (kernels/append_attn_split.hip) whenever Dh is 64 / 128 and the pass's N <= 32, else the rule as before.  The linear cache only
     bool append_split = false;
-    // session key stream_gemm (a key of the runtime; SmoothQuant and weight-only int8 / int4 engines): gemm() sends the projections of 9 <= M <= 64 rows
-    // to the weight-streaming kernel (kernels/gemm_stream_sq.hip, gemm_stream_woq.hip) - every pass through context_layer with that many rows.  The dual
-    // SwiGLU GEMM of context_gate_up (static scales, M >= 32) is not a gemm() call and stays
-    bool stream_gemm = false;
+    // session key stream_gemm (a key of the runtime), 0 / 1 / 2.  1 (SmoothQuant and weight-only int8 / int4 engines): gemm() sends the
+    // projections of 9 <= M <= 64 rows to the weight-streaming kernel (kernels/gemm_stream_sq.hip, gemm_stream_woq.hip) - every pass
+    // through context_layer with that many rows.  The dual SwiGLU GEMM of context_gate_up (static scales, M >= 32) is not a gemm()
+    // call and stays.  2 (every engine): the same, and fp16 weights go to kernels/gemm_stream_f16.hip - the projections of an fp16
+    // engine in gemm(), and at tp = 1 the fp16 lm_head at 9 .. 64 rows in head_gemm_f32 (verify, scoring) and in run_head where the
+    // rows come from a pass through context_layer (prompt, append, ragged append); the generation step keeps its GEMV slabs
+    int stream_gemm = 0;
     size_t kv_elems = 0; // elements of one layer's cache / pool
     bool force_comm = false; // tests: run the TP collectives on a 1-rank communicator too (RCCL inside the captured graph)
     // session key no_comm = 1: a rank's launches WITHOUT its collectives (all-reduces and the logits all-gather are skipped, nothing
@@ -200,8 +203,8 @@ struct tllm_session
     int64_t append_split_launches = 0; // and those the key append_split sent to the split-KV kernel (counted here alone)
     void* append_split_ws = nullptr;   // its partials: sized at setup for N = 32 and the finest plan of Smax
     int64_t append_split_ws_bytes = 0;
-    int64_t stream_gemm_launches = 0; // gemm() calls the key stream_gemm sent to the weight-streaming kernel since setup
-    void* stream_gemm_ws = nullptr;   // its partial sums: sized at setup for M = 64 and the layer's four shapes
+    int64_t stream_gemm_launches = 0; // gemm() and head calls the key stream_gemm sent to a weight-streaming kernel since setup
+    void* stream_gemm_ws = nullptr;   // its partial sums: sized at setup for M = 64 and the layer's four shapes (value 2: the head's too)
     int64_t stream_gemm_ws_bytes = 0;
     const float* rope = nullptr;
     int rope_len = 0;
@@ -433,7 +436,8 @@ struct tllm_session
         const void* residual, const float* epi_scale, void* y, int64_t ldy, int out_dtype, const Linear* up, hipStream_t st,
         const float* row_scales = nullptr, void* tap = nullptr);
     int allreduce(void* buf, int64_t n, hipStream_t st);
-    int run_head(const void* h, int rows, hipStream_t st, bool normalised = false);
+    // pass_rows: the rows come from a pass through context_layer (not a generation step): stream_gemm = 2 may stream the head
+    int run_head(const void* h, int rows, hipStream_t st, bool normalised = false, bool pass_rows = false);
     tllm::kernels::GreedyParams greedy_params();
     int run_sampler(int advance, hipStream_t st);
     struct DecodeStep; // what is fixed for one generation step (session_decode.cpp)

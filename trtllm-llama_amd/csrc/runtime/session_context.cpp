@@ -69,6 +69,24 @@ int tllm_session::gemm(const Linear& L, int M, const void* a, void* c, int out_d
         }
         set_error("%s", "");
     }
+    if (stream_gemm == 2 && stream_gemm_ws && L.wtype == W_FP16 && M >= 9 && M <= 64)
+    {
+        // value 2 of the key: fp16 weights on kernels/gemm_stream_f16.hip, the calls with a residual or a SwiGLU gate included;
+        // within the fp16 kernels' bound of launch_gemm's result (fp32 partial sums in another order), not its bits.  The whole
+        // range and every shape class: on the four 7B shapes the stream measured 12 - 23 us against launch_gemm's 107 - 264 at
+        // M = 16, 14 - 25 against 31 - 77 at 32, 18 - 31 against 33 - 89 at 64; the least gain is 12288 x 4096 at M = 64, 31.2
+        // against 37.0 us = 20 spreads of launch_gemm's runs, the fewest spreads 4.1 (the same shape at M = 32: 25.4 against 35.1;
+        // profiles/stream_gemm_f16.txt) - above the 3 spreads DESIGN.md section 6 asks for, so there is no M or shape condition
+        const int rc = launch_gemm_stream_f16(g, stream_gemm_ws, stream_gemm_ws_bytes, st);
+        if (rc < 0)
+            return 1;
+        if (rc == 0)
+        {
+            ++stream_gemm_launches;
+            return 0;
+        }
+        set_error("%s", "");
+    }
     return launch_gemm(g, st) ? 1 : 0;
 }
 
@@ -296,7 +314,7 @@ int tllm_session::run_context(hipStream_t st)
         RUN(launch_gather_rows(last_hidden, x, last_rows, Bc, D, st));
     else
         RUN(launch_gather_last_token(last_hidden, x, last_tok, Bc, S, D, st));
-    RUN(run_head(last_hidden, Bc, st));
+    RUN(run_head(last_hidden, Bc, st, false, true));
     return 0;
 }
 
@@ -368,7 +386,7 @@ int tllm_session::run_append(int n, int max_past, hipStream_t st)
     // row n - 1 of every sequence (append_last holds n for every sequence: the padded-layout gather takes row last - 1)
     RUN(launch_fill_i32(append_last, n, B, st));
     RUN(launch_gather_last_token(last_hidden, x, append_last, B, n, hidden, st));
-    RUN(run_head(last_hidden, B, st));
+    RUN(run_head(last_hidden, B, st, false, true));
     return 0;
 }
 
@@ -381,7 +399,7 @@ int tllm_session::run_append_ragged(int n, int max_end, hipStream_t st)
     append_max_end = 0;
     RUN(rc);
     RUN(launch_gather_last_token(last_hidden, x, append_last, B, n, hidden, st));
-    RUN(run_head(last_hidden, B, st));
+    RUN(run_head(last_hidden, B, st, false, true));
     return 0;
 }
 
@@ -493,6 +511,23 @@ int tllm_session::head_gemm_f32(const void* a, int rows, float* out, hipStream_t
     g.per_channel = head.per_channel;
     g.c = out;
     g.ldc = Vr;
+    if (stream_gemm == 2 && stream_gemm_ws && head.wtype == W_FP16 && tp == 1 && rows >= 9 && rows <= 32)
+    {
+        // value 2 of the key: the head - fp16 in every engine - on kernels/gemm_stream_f16.hip, fp32 logits.  Up to 32 rows: the
+        // 7B head (32000 x 4096) measured 56.5 against launch_gemm's 127.6 us at 16 rows (6 spreads) and 57.7 against 63.9 at 32
+        // (7 spreads), but 61.8 against 64.7 at 48 (2.4 spreads: under the 3 of DESIGN.md section 6) and 70.3 against 66.6 at 64,
+        // where the stream's 6 K-slices cost 98 MB of partial-sum traffic beside 262 MB of weights - those rows stay on the
+        // prefill GEMM (profiles/stream_gemm_f16.txt)
+        const int rc = launch_gemm_stream_f16(g, stream_gemm_ws, stream_gemm_ws_bytes, st);
+        if (rc < 0)
+            return 1;
+        if (rc == 0)
+        {
+            ++stream_gemm_launches;
+            return 0;
+        }
+        set_error("%s", ""); // not served: the prefill GEMM on the same operands
+    }
     return launch_gemm(g, st) ? 1 : 0;
 }
 

@@ -134,9 +134,22 @@ int tllm_session::allreduce(void* buf, int64_t n, hipStream_t st)
 }
 
 // ln_f -> lm_head -> fp32 logits of this rank's vocabulary shard (-> all-gather)
-int tllm_session::run_head(const void* h, int rows, hipStream_t st, bool normalised)
+int tllm_session::run_head(const void* h, int rows, hipStream_t st, bool normalised, bool pass_rows)
 {
     logit_rows = rows;
+    if (pass_rows && stream_gemm == 2 && stream_gemm_ws && head.wtype == W_FP16 && tp == 1 && !force_comm && rows >= 9 && rows <= 64
+        && !gemm_stream_f16_plan(rows, head.N, head.K, 0).refused)
+    {
+        // value 2 of the session key stream_gemm, the rows of a prompt, an append or a ragged append at batch 9 .. 64: the GEMV
+        // below would stream the head once per slab of 8 rows (7B head: 107 / 216 / 330 / 435 us at 16 / 32 / 48 / 64 rows).  ln_f
+        // as a launch of its own (fp16 in tmp, free behind the last layer), then ONE pass over the head in head_gemm_f32: the fp16
+        // stream up to 32 rows (57 / 58 us), the prefill GEMM beyond (65 / 67 us, where the stream measured equal or slower;
+        // profiles/stream_gemm_f16.txt).  A head whose K the stream's plan refuses keeps the slabs
+        head_partials_live = false;
+        if (!normalised)
+            RUN(head_norm(h, rows, st));
+        return head_gemm_f32(normalised ? h : tmp, rows, logits_local, st);
+    }
     gemv_cls = PC_GEMV_HEAD;
     // one row: the launch of a batch-1 step (and of a single prompt) - the instance that takes the two lm_head options
     const bool one_row = rows == 1 && head.wtype == W_FP16;

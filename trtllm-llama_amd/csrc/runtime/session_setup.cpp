@@ -135,7 +135,19 @@ int tllm_session::alloc_buffers()
             for (int m = 16; m <= 64; m += 16)
             {
                 const bool woq = l->wtype == W_INT8_WOQ || l->wtype == W_INT4_WOQ;
-                const GemmStreamPlan plan = woq ? gemm_stream_woq_plan(m, l->N, l->K, l->wtype, cus) : gemm_stream_plan(m, l->N, l->K, cus);
+                if (l->wtype == W_FP16 && stream_gemm != 2)
+                    continue; // fp16 weights stream under value 2 alone
+                const GemmStreamPlan plan = l->wtype == W_FP16 ? gemm_stream_f16_plan(m, l->N, l->K, cus)
+                    : woq                                      ? gemm_stream_woq_plan(m, l->N, l->K, l->wtype, cus)
+                                                               : gemm_stream_plan(m, l->N, l->K, cus);
+                if (!plan.refused)
+                    stream_gemm_ws_bytes = std::max(stream_gemm_ws_bytes, plan.workspace_bytes);
+            }
+        // value 2: the fp16 lm_head streams too, up to 32 rows (head_gemm_f32; one rank only)
+        if (stream_gemm == 2 && head.wtype == W_FP16 && tp == 1)
+            for (int m = 16; m <= 32; m += 16)
+            {
+                const GemmStreamPlan plan = gemm_stream_f16_plan(m, head.N, head.K, cus);
                 if (!plan.refused)
                     stream_gemm_ws_bytes = std::max(stream_gemm_ws_bytes, plan.workspace_bytes);
             }

@@ -196,8 +196,15 @@ tllm_session_t tllm_session_create(const char* config_text)
                   "the linear cache only)");
         return nullptr;
     }
-    s->stream_gemm = geti("stream_gemm", 0) != 0;
-    if (s->stream_gemm && !(s->quant_mode & (QM_INT8_WEIGHTS | QM_INT4_WEIGHTS)))
+    s->stream_gemm = geti("stream_gemm", 0);
+    if (s->stream_gemm < 0 || s->stream_gemm > 2)
+    {
+        set_error("tllm_session_create: stream_gemm = %d is not 0, 1 (the streams of quantised weights) or 2 (those and the fp16 "
+                  "stream: fp16 projections and the lm_head)",
+            s->stream_gemm);
+        return nullptr;
+    }
+    if (s->stream_gemm == 1 && !(s->quant_mode & (QM_INT8_WEIGHTS | QM_INT4_WEIGHTS)))
     {
         set_error("tllm_session_create: stream_gemm = 1 needs a SmoothQuant or weight-only int8 / int4 engine (quant_mode %d has "
                   "fp16 weights): the weight-streaming GEMMs serve quantised weights only",

@@ -54,7 +54,10 @@ def parse_arguments(args=None):
                    'head sizes 64 / 128, the linear cache)')
     p.add_argument('--stream_gemm', action='store_true',
                    help='SmoothQuant and weight-only int8 / int4 engines: run the projections of 9 to 64 rows (append / verify passes, '
-                   'short prompts) on the weight-streaming GEMM (session key stream_gemm)')
+                   'short prompts) on the weight-streaming GEMM (session key stream_gemm = 1)')
+    p.add_argument('--stream_gemm_fp16', action='store_true',
+                   help='every engine: what --stream_gemm does, and fp16 weights on the fp16 weight stream - the projections of an '
+                   'fp16 engine at 9 to 64 rows and the lm_head of the verify passes (session key stream_gemm = 2)')
     # LoRA adapters (an engine built with --lora_max_rank): HF PEFT directories go into slots 0, 1, ... in the order given
     p.add_argument('--lora_dir', type=str, nargs='+', default=None, help='HF PEFT adapter directories (adapter_config.json + '
                    'adapter_model.safetensors)')
@@ -96,9 +99,10 @@ def load_session(engine_dir, append_split=False, stream_gemm=False):
 def generate(max_output_len, log_level='error', engine_dir='llama_outputs', input_text=None, input_file=None,
              output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55, top_k=1, top_p=0.0,
              temperature=1.0, repetition_penalty=1.0, random_seed=None, prompt_lookup_tokens=0, prompt_lookup_ngram=3,
-             prompt_lookup_sampling=False, lora_dir=None, lora_slots=None, append_split_kv=False, stream_gemm=False):
+             prompt_lookup_sampling=False, lora_dir=None, lora_slots=None, append_split_kv=False, stream_gemm=False,
+             stream_gemm_fp16=False):
     tensorrt_llm.logger.set_level(log_level)
-    decoder, runtime_rank = load_session(engine_dir, append_split=append_split_kv, stream_gemm=stream_gemm)
+    decoder, runtime_rank = load_session(engine_dir, append_split=append_split_kv, stream_gemm=2 if stream_gemm_fp16 else stream_gemm)
     for slot, d in enumerate(lora_dir or []):
         decoder.load_lora(d, slot)
     if isinstance(lora_slots, str):

@@ -175,6 +175,10 @@ def load_library():
     lib.tllm_gemm_stream_epi.restype = c.c_int32
     lib.tllm_gemm_stream_layout.argtypes = [c.POINTER(GemmParams), c.c_int32, c.POINTER(c.c_int64)] + [c.POINTER(c.c_int32)] * 6
     lib.tllm_gemm_stream_layout.restype = c.c_int32
+    lib.tllm_gemm_stream_f16.argtypes = [c.POINTER(GemmParams), c.c_void_p, c.c_void_p, c.c_void_p, c.c_int64, c.c_void_p]
+    lib.tllm_gemm_stream_f16.restype = c.c_int32
+    lib.tllm_gemm_stream_f16_layout.argtypes = [c.POINTER(GemmParams), c.c_int32, c.POINTER(c.c_int64)] + [c.POINTER(c.c_int32)] * 6
+    lib.tllm_gemm_stream_f16_layout.restype = c.c_int32
     lib.tllm_gemm_stream_set_cus.argtypes = [c.c_int32]
     lib.tllm_gemm_stream_set_cus.restype = None
     if not lib.initLibNvInferPlugins(None, TRT_LLM_PLUGIN_NAMESPACE.encode('utf-8')):

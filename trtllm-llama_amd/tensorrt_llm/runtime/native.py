@@ -737,7 +737,8 @@ class NativeSession:
         return int(n.value)
 
     def stream_gemm_launches(self):
-        """GEMM calls the session key stream_gemm has sent to the weight-streaming kernel since setup (9 .. 64 rows; SmoothQuant and weight-only engines)"""
+        """GEMM calls the session key stream_gemm has sent to a weight-streaming kernel since setup (9 .. 64 rows; SmoothQuant and
+        weight-only projections, and under value 2 fp16 projections and every lm_head call the fp16 stream served)"""
         n = ctypes.c_int64()
         _check(_lib().tllm_session_stream_gemm_launches(self._h, ctypes.byref(n)), 'stream_gemm_launches')
         return int(n.value)
