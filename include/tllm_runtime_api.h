@@ -44,7 +44,10 @@ typedef struct tllm_session* tllm_session_t;
  *   _generate forms, tllm_session_verify, _verify_sampled and both tllm_session_generate_lookup loops, LoRA included, serve the
  *   paged cache through its table, bit for bit what the linear session computes; without the key a paged session refuses them
  *   as before.  A key of the runtime, not of the engine header: tllm_session_load_engine_keys adds it to a loaded engine),
- *   append_split (0; 1, with the linear cache only - together with paged_kv_cache = 1 it is refused by name: every pass through the
+ *   append_split (0; 1, with the linear cache only - together with paged_kv_cache = 1 it is refused by name; 2: what 1 does on a
+ *   linear cache, and on paged_kv_cache = 1 with paged_append = 1 - refused by name without it - the same through pool and table
+ *   (tllm_attention_append_split_paged), bit for bit the linear session's with the key; any other non-zero value acts as 1: every
+ *   pass through the
  *   append attention - the entries listed under paged_append - runs the split-KV kernel (tllm_attention_append_split) whenever the
  *   head size is 64 / 128 and the pass has N <= 32 rows per sequence, from a workspace allocated at setup - B * 32 * H * (R + 1) *
  *   (Dh + 2) * 4 bytes, R = min(64, CUs / (Hkv * B), ceil(Smax / 128)): 4.8 MB for the 7B extents at batch 1 on 256 CUs; any other
@@ -889,10 +892,20 @@ int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* p, in
  *                (uniform) or max_end (ragged); written before it is read, nothing to clear; free for reuse when the stream has
  *                passed the call.
  * Refused, with nothing launched: head size not 64 / 128; n < 1 or n > 32; workspace NULL, misaligned or too small; split_chunk
- * negative or not a multiple of 64; and everything tllm_attention_append / _ragged refuse.  The paged cache is not served. */
+ * negative or not a multiple of 64; and everything tllm_attention_append / _ragged refuse.  The paged cache has the entry below. */
 #define TLLM_APPEND_ATTN_SPLIT 3
 int32_t tllm_attention_append_split(const tllm_attention_append_params_t* p, const int32_t* n_per_seq /* NULL = uniform */,
     int32_t max_end, int32_t split_chunk, void* workspace, int64_t workspace_bytes, tllm_stream_t stream);
+/* tllm_attention_append_paged with the attention launch replaced by the split-KV pair: pool, table and the zero-entry contract as
+ * tllm_attention_append_paged takes them, split_chunk and workspace as tllm_attention_append_split takes them (plan and workspace
+ * do not depend on the layout: the same tllm_attention_append_split_layout).  The partial launch is a paged instance of the same
+ * kernel - a past row is found through the table, whose entries travel one 64-key block ahead of the rows in an LDS ring - and
+ * its results are, bit for bit, those of tllm_attention_append_split on the same logical cache with the same split_chunk: out, the
+ * rewritten qkv and the rows stored behind the table.
+ * Refused, with nothing launched: block_pointers NULL, and everything either of the two entries refuses. */
+int32_t tllm_attention_append_split_paged(const tllm_attention_append_params_t* p, const int64_t* block_pointers,
+    int32_t tokens_per_block, int32_t max_blocks_per_seq, const int32_t* n_per_seq /* NULL = uniform */, int32_t max_end,
+    int32_t split_chunk, void* workspace, int64_t workspace_bytes, tllm_stream_t stream);
 /* the plan tllm_attention_append_split follows for p (batch, n, num_heads, num_kv_heads, head_size are read; no pointer is followed;
  * no GPU needed): past slots [r * chunk, (r + 1) * chunk) are range r < ranges = ceil(max_keys / chunk), max_keys >= every past
  * length.  split_chunk 0: the smallest multiple of 64 that is >= 128, gives at most 64 ranges and fills `cus` CUs (<= 0: 256) about

@@ -8,6 +8,7 @@ verify pass - device events, medians with the spread, the two routes alternating
 Part 1 calls each entry 20 times on ONE cache, which then sits in the chip's caches; a pass walks 32 layers, each with a cache of its
 own.  Part 1b repeats four rows with the calls rotating over 32 caches, as the layers of a pass do.
 GPU only.    python tools/append_split_timing.py [--out profiles/append_split.txt] [--no_pass]
+--paged [--tokens_per_block T]: the same three things on the paged cache (paged_report below) -> profiles/append_split_paged.txt
 --trace_pass: nothing is timed - 8 verify passes of n = 2 on the keyless session, then 8 on the keyed one, for a kernel trace:
              rocprofv3 --kernel-trace --stats -d <dir> -- python tools/append_split_timing.py --trace_pass"""
 import argparse, os, sys
@@ -16,11 +17,14 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'trtllm-llama_am
 import torch, numpy as np
 import bench
 from tensorrt_llm.plugin import capi
-from tensorrt_llm.runtime.native import (APPEND_ATTN_MFMA, APPEND_ATTN_WAVE, NativeSession, attention_append, attention_append_split,
-                                         attention_append_split_layout)
+from tensorrt_llm.runtime.native import (APPEND_ATTN_MFMA, APPEND_ATTN_WAVE, NativeSession, attention_append, attention_append_paged,
+                                         attention_append_split, attention_append_split_layout, attention_append_split_paged)
 ap = argparse.ArgumentParser()
-ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'append_split.txt'))
+ap.add_argument('--out', default=None, help='profiles/append_split.txt, with --paged profiles/append_split_paged.txt')
 ap.add_argument('--no_pass', action='store_true', help='part 1 alone')
+ap.add_argument('--paged', action='store_true', help='the paged cache: attention call and verify pass of the paged session without '
+                'the key, the paged session with append_split = 2 and the linear session with append_split = 1')
+ap.add_argument('--tokens_per_block', type=int, default=64, help='with --paged: tokens per page')
 ap.add_argument('--trace_pass', action='store_true', help='run verify passes for a kernel trace, time nothing')
 args = ap.parse_args()
 assert torch.cuda.is_available(), 'append_split_timing.py needs a GPU'
@@ -82,6 +86,108 @@ def attention_case(kv, past, n, H=32, Hkv=32, Dh=128, chunks=(0, ), layers=1):
             t[c].append(event_us(lambda: attention_append_split(qkv, next_cache(), out, seq, seq, split_chunk=c, workspace=ws, **kw)))
     return {k: v[1:] for k, v in t.items()}, ('MFMA' if n >= 16 else 'WAVE')
 
+
+def paged_report(T):
+    """--paged: the attention call and the verify pass on the paged cache, three routes alternating in one run - the paged session
+    without append_split (what a paged session ran before the paged split instance: the WAVE kernel at n < 16), the paged session
+    with append_split = 2, the linear session with append_split = 1 - at pasts 1024 and 4000, n = 2 / 4 / 8"""
+    H, Dh, NS = 32, 128, (2, 4, 8)
+    sc = torch.tensor([32.0], device=dev), torch.tensor([1 / 32.0], device=dev)
+    say(f'Part 1: the attention call alone (RoPE + cache write launch, attention launch, SPLIT: + merge launch), int8 cache, batch 1, '
+        f'H {H}, Dh {Dh}, T = {T}, {CUS} CUs; microseconds per call, median (min - max) of {RUNS} runs of {REPS} calls between device '
+        'events, the routes alternating, one warm-up run of each dropped; the pages of the sequence scattered over the pool, and the same '
+        'pool with its pages in ascending order')
+    for past in (1024, 4000):
+        smax = (past + 64 + T - 1) // T * T
+        M = smax // T
+        cache = torch.randint(-127, 128, (1, 2, H, smax, Dh), device=dev, dtype=torch.int8)
+        pool = torch.randint(-127, 128, (2 * M, H, T, Dh), device=dev, dtype=torch.int8)
+        order, nbytes = torch.randperm(M), H * T * Dh
+        table = torch.stack([pool.data_ptr() + order * nbytes, pool.data_ptr() + (M + order) * nbytes]).view(1, 2, M).to(dev)
+        order = torch.arange(M)  # the same pool with its pages in ascending order: what the scatter costs, apart from the table
+        table_asc = torch.stack([pool.data_ptr() + order * nbytes, pool.data_ptr() + (M + order) * nbytes]).view(1, 2, M).to(dev)
+        seq = torch.tensor([past], dtype=torch.int32, device=dev)
+        for n in NS:
+            qkv = (torch.randn((1, n, 3 * H * Dh), device=dev) * 0.5).half()
+            out = torch.empty((1, n, H * Dh), device=dev, dtype=torch.float16)
+            kw = dict(num_heads=H, head_size=Dh, max_input_len=past, max_past=past, kv_cache_type=capi.INT8, kv_scale_orig_quant=sc[0],
+                      kv_scale_quant_orig=sc[1])
+            ws = torch.empty(attention_append_split_layout(n, Dh, batch=1, num_heads=H, max_keys=past, cus=CUS)[2], dtype=torch.uint8,
+                             device=dev)
+            pg = dict(tokens_per_block=T, max_seq_len=smax, **kw)
+            routes = dict(wave=lambda: attention_append_paged(qkv, pool, table, out, seq, seq, append_kernel=APPEND_ATTN_WAVE, **pg),
+                          split=lambda: attention_append_split_paged(qkv, pool, table, out, seq, seq, workspace=ws, **pg),
+                          asc=lambda: attention_append_split_paged(qkv, pool, table_asc, out, seq, seq, workspace=ws, **pg),
+                          linear=lambda: attention_append_split(qkv, cache, out, seq, seq, workspace=ws, **kw))
+            t = {k: [] for k in routes}
+            for i in range(RUNS + 1):
+                for k, fn in routes.items():
+                    t[k].append(event_us(fn))
+            t = {k: v[1:] for k, v in t.items()}
+            say(f'int8 past {past:4d} n {n}: paged WAVE {med(t["wave"])} | paged SPLIT {med(t["split"])} | pages in order '
+                f'{med(t["asc"])} | linear SPLIT {med(t["linear"])} | '
+                f'WAVE / paged SPLIT {np.median(t["wave"]) / np.median(t["split"]):.2f} x, paged / linear SPLIT '
+                f'{np.median(t["split"]) / np.median(t["linear"]):.3f}')
+    if args.no_pass:
+        return
+    cfg = dict(bench.LLAMA_7B, num_layers=32)
+    V = cfg['vocab_size']
+    torch.cuda.set_stream(torch.cuda.Stream(device=dev))
+    stream = torch.cuda.current_stream().cuda_stream
+    w = bench.synth_weights(torch, cfg, 'sq', True, 1, 0, dev)
+    STEPS, PRUNS = 8, 7
+    paged = dict(paged_kv_cache=1, tokens_per_block=T, paged_append=1)
+    sess = {}
+    for name, keys in (('paged', paged), ('paged2', dict(paged, append_split=2)), ('linear1', dict(append_split=1))):
+        s = NativeSession(dict(cfg, quant_mode=bench.QM['sq'] | bench.INT8_KV, tp_size=1, tp_rank=0, **keys))
+        for k, t in w.items():
+            s.set_tensor(k, t)
+        s.finalize()
+        sess[name] = s
+
+    def event_ms(fn):
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    say(f'Part 2: the verify pass, 7B SmoothQuant int8 + int8 KV, batch 1, synthetic weights, T = {T}; ms, median (min - max) of {PRUNS} '
+        'runs between device events, one warm-up run dropped; the paged session without append_split, the paged session with '
+        'append_split = 2, the linear session with append_split = 1 and graph steps of the paged session alternating')
+    r = np.random.default_rng(1)
+    fm = lambda v: f'{np.median(v):.3f} ({min(v):.3f} - {max(v):.3f})'
+    for past in (1024, 4000):
+        for s in sess.values():
+            s.setup(1, past, 512)
+        for n in NS:
+            for s in sess.values():
+                s.fake_context(past, seed=3, stream=stream)
+                s.step(2, use_graph=True, stream=stream)
+            tv, ts = {k: [] for k in sess}, []
+            for i in range(PRUNS + 1):
+                ids = r.integers(3, V, (1, n)).astype(np.int32)
+                for name, s in sess.items():
+                    tv[name].append(event_ms(lambda: s.verify(ids, stream=stream)))
+                ts.append(event_ms(lambda: sess['paged'].step(STEPS, use_graph=True, stream=stream)) / STEPS)
+            tv, st = {k: v[1:] for k, v in tv.items()}, np.median(ts[1:])
+            say(f'past {past:4d} verify pass of n = {n}: paged {fm(tv["paged"])} | paged append_split = 2 {fm(tv["paged2"])} | linear '
+                f'append_split = 1 {fm(tv["linear1"])} | one paged step from the graph {st:.3f} | break-even '
+                + ' -> '.join(f'{np.median(tv[k]) / st - 1:.2f}' for k in ('paged', 'paged2')) + ' drafts kept per round')
+    say('split launches: ' + ', '.join(f'{k} {s.append_split_launches()}' for k, s in sess.items())
+        + '; append launches (wave, mfma): ' + ', '.join(f'{k} {s.append_launches()}' for k, s in sess.items()))
+    for s in sess.values():
+        s.close()
+
+
+if args.paged:
+    paged_report(args.tokens_per_block)
+    with open(args.out or os.path.join(ROOT, 'profiles', 'append_split_paged.txt'), 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
+args.out = args.out or os.path.join(ROOT, 'profiles', 'append_split.txt')
 
 if not args.trace_pass:
     say(f'Part 1: the attention call alone (RoPE + cache write launch, attention launch, SPLIT: + merge launch), batch 1, H 32, Dh 128, '

@@ -10,7 +10,7 @@
 //   (c) append_attn_wave_kernel one wave per query: every n, head sizes 32 / 64 / 128 / 256;
 //   (d) append_advance_kernel   sequence_length[b] += n, finished[b] = 0 (the session's bookkeeping, a launch of its own).
 // In place of (b) / (c), by name only (APPEND_ATTN_SPLIT; append_attn_split.hip): the split-KV pair of launches for n <= 32 onto a
-// long past - same rule, another summation order.
+// long past - same rule, another summation order; its partial launch has a paged instance too.
 // A different number of tokens per sequence (n_per_seq, device [B]; null = n for all): sequence b appends n_b = n_per_seq[b]
 // clamped into [0, n], n stays the row stride of the QKV buffer and of `out`, and the rule above holds with n_b in place of n.  Rows
 // i >= n_b are padding: (a) leaves them alone (no RoPE, no cache store - their bits in the QKV buffer stay), (b) and (c) write
@@ -604,7 +604,7 @@ int launch_dh(const AppendAttnParams& p, int kind, hipStream_t stream, const App
     if (launch_util::check_launch("append attention (RoPE, cache write)"))
         return -1;
     const int kv = kv_kind(p.kv_dtype);
-    if (kind == APPEND_ATTN_SPLIT) // (checked by the caller: head size 64 / 128, the linear cache, a plan and its workspace)
+    if (kind == APPEND_ATTN_SPLIT) // (checked by the caller: head size 64 / 128, a plan and its workspace; PG from the table)
         return launch_append_attn_split(p, *split, stream);
     if (kind == APPEND_ATTN_MFMA)
     {
@@ -745,11 +745,6 @@ int launch_append_attention(const AppendAttnParams& pin, hipStream_t stream)
     }
     if (kind == APPEND_ATTN_SPLIT)
     {
-        if (p.block_pointers)
-        {
-            set_error("append attention: the split-KV kernel does not serve the paged KV cache (a block table was given)");
-            return -1;
-        }
         const AppendSplitPlan plan = append_split_plan(p.head_size, p.n, p.batch, p.num_heads, p.num_kv_heads,
             p.n_per_seq ? p.max_end : p.max_past, launch_util::device_cus(), p.split_chunk);
         if (plan.refused)
@@ -764,6 +759,8 @@ int launch_append_attention(const AppendAttnParams& pin, hipStream_t stream)
                 (long long) p.workspace_bytes);
             return -1;
         }
+        if (p.block_pointers) // launch (a) and the partial launch as paged instances; plan, workspace and merge know no layout
+            return p.head_size == 64 ? launch_dh<64, true>(p, kind, stream, &plan) : launch_dh<128, true>(p, kind, stream, &plan);
         return p.head_size == 64 ? launch_dh<64, false>(p, kind, stream, &plan) : launch_dh<128, false>(p, kind, stream, &plan);
     }
     if (p.block_pointers) // the paged instances

@@ -1,5 +1,5 @@
 // Split-KV append attention (APPEND_ATTN_SPLIT): the attention launch of an append of 1 <= n <= 32 tokens
-// per sequence onto a long live cache, head sizes 64 / 128, the linear cache.  The rule is append_attn.hip's, unchanged - visibility,
+// per sequence onto a long live cache, head sizes 64 / 128, the linear or the paged cache.  The rule is append_attn.hip's, unchanged - visibility,
 // cache elements as the exact fp16 value of their byte, kv_scale_quant_orig once on the score and once on the sum of p.v, fp32
 // soft-max, probabilities rounded to fp16, normaliser 1 / (l + 1e-6), one rounding of the result - only the summation order differs.
 // Two launches behind launch (a), ordered by the kernel boundary alone (no tickets, flags or waits inside a launch):
@@ -30,6 +30,20 @@
 //    behind p_b writes the empty partial (m = -inf, l = 0, O = 0), decided before the first barrier.  A workgroup whose every
 //    column is padding (tile group at or behind n_b * G) writes NOTHING: the merge takes rows i >= n_b as zeros without reading
 //    a partial, and every (row i < n_b, range) has exactly one workgroup that writes it - the merge never reads an unwritten word.
+//    The paged cache (template parameter PG; block_pointers set): only where a past row comes from differs - slot t is row t & (T - 1)
+//    of the page block_pointers[(b * 2 + {K 0, V 1}) * max_blocks_per_seq + (t >> lg T)], pages [Hkv, T, Dh] - so every result is the
+//    linear instance's bit for bit.  A 64-key block starts at a multiple of 64: it lies inside one page (T >= 64) or spans 64 / T
+//    pages, at most 64 K and 64 V entries.  Scheme: the table entries travel ONE STAGE AHEAD of the rows.  Entry threads (tid <
+//    128: 64 K, 64 V, NE = max(64 / T, 1) of each live) request the entries of the block AFTER NEXT into a register right behind the
+//    row requests of an iteration (the memory counter is in order, so the wait for the rows in front of the LDS writes never
+//    includes a table load), so the request flies under compute(); an iteration later they publish the register into an LDS
+//    ring of 2 slots x 128 x 8 bytes ahead of the top barrier, and the fetch() behind that barrier forms each row address from an
+//    LDS read.  So no row load of block k0 + 64 waits on a table load issued in the same iteration, and the register stage of the
+//    rows is exactly the linear instance's.  Only the prologue has a dependent pair (the first block's entries, then its rows); the
+//    second block's entries are requested next to the first's.  Two slots, not one: a publication never touches the slot the
+//    previous fetch() read, so its place in the iteration is free.  Every page index is clamped to the page of slot
+//    min(range end, p_b) - 1, an entry of 0 is replaced by the pool's address before it is published (no address is formed from
+//    0), the slots read in that way are >= kend and become zeros on the way into LDS as before, and the chunk range reads no entry.
 // 2. append_split_merge_kernel, one wave per row of `out`: M = max_r m_r, l = sum_r l_r e^(m_r - M), O likewise, in range order
 //    (deterministic), out = fp16(O / (l + 1e-6)); rows i >= n_b are zeros.
 #include "append_attn_common.h"
@@ -53,8 +67,28 @@ typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
 constexpr int kSplitCols = 32; // columns of a tile group
 
+// 8 cache elements at an address made from a block-table entry.  The address is cast to the global address space: through a
+// generic pointer the row loads would be flat loads, which count as LDS traffic too - every wait for a fragment read in compute()
+// would then wait for the prefetch
+template <int KV>
+__device__ __forceinline__ typename kv_raw8<KV>::type load_page_raw8(int64_t addr)
+{
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+    if constexpr (KV == 0)
+    {
+        const u32x4_t g = *(const __attribute__((address_space(1))) u32x4_t*) (uintptr_t) addr;
+        return make_uint4(g.x, g.y, g.z, g.w);
+    }
+    else
+    {
+        const u32x2_t g = *(const __attribute__((address_space(1))) u32x2_t*) (uintptr_t) addr;
+        return make_uint2(g.x, g.y);
+    }
+}
+
 // workspace: O [rows][R][DH] fp32, then (m, l) [rows][R][2]; rows = B * n * H in the order of `out`, R = ranges + 1
-template <int DH, int KV>
+template <int DH, int KV, bool PG>
 __global__ __launch_bounds__(256) void append_attn_split_kernel(const AppendAttnParams p, const int chunk, const int ranges)
 {
     constexpr int ESZ = KV == 0 ? 2 : 1;
@@ -68,6 +102,12 @@ __global__ __launch_bounds__(256) void append_attn_split_kernel(const AppendAttn
     typedef typename kv_raw8<KV>::type raw_t;
     __shared__ __attribute__((aligned(16))) char smem[64 * KP + DH * VP];
     __shared__ int sOk[64];
+    int64_t* sEnt = nullptr; // paged: the ring of table entries, 2 slots x (64 K + 64 V)
+    if constexpr (PG)
+    {
+        __shared__ int64_t ent_lds[2 * 128];
+        sEnt = ent_lds;
+    }
     char* const sK = smem;
     char* const sV = smem + 64 * KP;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, c16 = lane & 15, kb = lane >> 4;
@@ -202,6 +242,15 @@ __global__ __launch_bounds__(256) void append_attn_split_kernel(const AppendAttn
         }
     };
 
+    // paged: entry thread tid < 128 owns entry e = tid & 63 < NE = max(64 / T, 1) of the K (tid < 64) or V row of the table for
+    // the 64-key block at slot k0 - the page of slot k0 + e * T, clamped to the page of slot kend - 1 (kend <= p_b <= Smax <=
+    // max_blocks_per_seq * T: inside the sequence's row).  An entry of 0 becomes the pool's own address: a select, never 0 + offset
+    const int pg_T = PG ? p.tokens_per_block : 1, pg_lg = PG ? 31 - __builtin_clz(pg_T) : 0;
+    const bool is_ent = PG && tid < 128 && (tid & 63) < max(64 >> pg_lg, 1);
+    auto pg_entry = [&](int k0) -> int64_t {
+        const int j = min((k0 >> pg_lg) + (tid & 63), (kend - 1) >> pg_lg);
+        return p.block_pointers[((int64_t) b * 2 + (tid >> 6)) * p.max_blocks_per_seq + j]; // (as loaded: the select waits for it)
+    };
     // the loop over a past range; HM: the launch has a slot mask (a compile-time copy each, so that the prefetch has no branch)
     auto past_range = [&](auto has_mask) {
         constexpr bool HM = decltype(has_mask)::value;
@@ -211,12 +260,19 @@ __global__ __launch_bounds__(256) void append_attn_split_kernel(const AppendAttn
         // a loaded value here - what a row means is decided when the block is written to LDS - so nothing waits for a load before
         // the block in LDS has been computed.  A slot >= kend reads slot kend - 1 instead (kend <= p_b <= Smax) and a masked slot
         // reads its own bytes (they are the cache's); both become zeros on the way into LDS
-        auto fetch = [&](int k0) {
+        // paged: `ents` is the ring slot that holds the block's table entries (K 0 .. 63, V 64 .. 127), entry e for the page of slot
+        // k0 + e * T; a row's address is an LDS read away, never a table load away
+        auto fetch = [&](int k0, const int64_t* ents) {
+            const int pg0 = k0 >> pg_lg;
 #pragma unroll
             for (int ps = 0; ps < KPASS; ++ps)
             {
                 const int slot = min(k0 + ps * KPP + krow, kend - 1); // (a non-empty range: kend - 1 >= kbeg >= 0)
-                kr[ps] = *reinterpret_cast<const raw_t*>(kc + ((int64_t) slot * DH + kc8 * 8) * ESZ);
+                if constexpr (PG)
+                    kr[ps] = load_page_raw8<KV>(ents[(slot >> pg_lg) - pg0]
+                        + (((int64_t) kvh * pg_T + (slot & (pg_T - 1))) * DH + kc8 * 8) * ESZ);
+                else
+                    kr[ps] = *reinterpret_cast<const raw_t*>(kc + ((int64_t) slot * DH + kc8 * 8) * ESZ);
                 kmask[ps] = 0;
                 if constexpr (HM)
                     kmask[ps] = mask[slot];
@@ -225,13 +281,44 @@ __global__ __launch_bounds__(256) void append_attn_split_kernel(const AppendAttn
             vmask = 0;
             if constexpr (HM)
                 vmask = mask[slot];
+            if constexpr (PG)
+            {
+                const int64_t vrow = ents[64 + (slot >> pg_lg) - pg0] + ((int64_t) kvh * pg_T + (slot & (pg_T - 1))) * DH * ESZ;
 #pragma unroll
-            for (int ps = 0; ps < VPASS; ++ps)
-                vr[ps] = *reinterpret_cast<const raw_t*>(vc + ((int64_t) slot * DH + ((tid >> 6) + 4 * ps) * 8) * ESZ);
+                for (int ps = 0; ps < VPASS; ++ps)
+                    vr[ps] = load_page_raw8<KV>(vrow + (((tid >> 6) + 4 * ps) * 8) * ESZ);
+            }
+            else
+            {
+#pragma unroll
+                for (int ps = 0; ps < VPASS; ++ps)
+                    vr[ps] = *reinterpret_cast<const raw_t*>(vc + ((int64_t) slot * DH + ((tid >> 6) + 4 * ps) * 8) * ESZ);
+            }
         };
-        fetch(kbeg);
+        int64_t pg_next = 0;
+        if constexpr (PG)
+        {
+            // the first block's entries directly, and the second block's behind them: the one dependent load of a workgroup
+            if (is_ent)
+            {
+                const int64_t e0 = pg_entry(kbeg);
+                if (kbeg + 64 < kend)
+                    pg_next = pg_entry(kbeg + 64);
+                sEnt[tid] = e0 ? e0 : reinterpret_cast<int64_t>(p.kv_cache);
+            }
+            __syncthreads();
+        }
+        fetch(kbeg, sEnt);
         for (int k0 = kbeg; k0 < kend; k0 += 64)
         {
+            int64_t* const ents_next = PG ? sEnt + ((((k0 - kbeg) >> 6) + 1) & 1) * 128 : nullptr;
+            if constexpr (PG)
+            {
+                // the entries of block k0 + 64, requested an iteration ago, ahead of the barrier that precedes their fetch; the slot
+                // was last read by the fetch of block k0 - 64, two barriers back
+                if (is_ent && k0 + 64 < kend)
+                    ents_next[tid] = pg_next ? pg_next : reinterpret_cast<int64_t>(p.kv_cache);
+            }
             __syncthreads(); // the previous block's fragment reads are done
 #pragma unroll
             for (int ps = 0; ps < KPASS; ++ps)
@@ -243,7 +330,14 @@ __global__ __launch_bounds__(256) void append_attn_split_kernel(const AppendAttn
             for (int ps = 0; ps < VPASS; ++ps)
                 store_v((tid >> 6) + 4 * ps, keep8(kv8_to_h8<KV>(vr[ps]), vlive));
             if (k0 + 64 < kend) // uniform: the next block's loads fly while this one computes
-                fetch(k0 + 64);
+                fetch(k0 + 64, ents_next);
+            if constexpr (PG)
+            {
+                // the entries of the block after next, BEHIND the row requests (the memory counter is in order: a wait for the
+                // rows never includes this load) and unused until the publication above: in flight under compute()
+                if (is_ent && k0 + 128 < kend)
+                    pg_next = pg_entry(k0 + 128);
+            }
             __syncthreads();
             if (active)
                 compute();
@@ -369,17 +463,17 @@ __global__ __launch_bounds__(256) void append_split_merge_kernel(const AppendAtt
         *out = f2h(o[0] * inv);
 }
 
-template <int DH>
+template <int DH, bool PG>
 int launch_split_dh(const AppendAttnParams& p, const AppendSplitPlan& plan, hipStream_t stream)
 {
     const dim3 grid(plan.ranges + 1, p.num_kv_heads * plan.tile_groups, p.batch);
     const int kv = kv_kind(p.kv_dtype);
     if (kv == 0)
-        hipLaunchKernelGGL((append_attn_split_kernel<DH, 0>), grid, dim3(256), 0, stream, p, plan.chunk, plan.ranges);
+        hipLaunchKernelGGL((append_attn_split_kernel<DH, 0, PG>), grid, dim3(256), 0, stream, p, plan.chunk, plan.ranges);
     else if (kv == 1)
-        hipLaunchKernelGGL((append_attn_split_kernel<DH, 1>), grid, dim3(256), 0, stream, p, plan.chunk, plan.ranges);
+        hipLaunchKernelGGL((append_attn_split_kernel<DH, 1, PG>), grid, dim3(256), 0, stream, p, plan.chunk, plan.ranges);
     else
-        hipLaunchKernelGGL((append_attn_split_kernel<DH, 2>), grid, dim3(256), 0, stream, p, plan.chunk, plan.ranges);
+        hipLaunchKernelGGL((append_attn_split_kernel<DH, 2, PG>), grid, dim3(256), 0, stream, p, plan.chunk, plan.ranges);
     if (launch_util::check_launch("append attention (split-KV partials)"))
         return -1;
     const int64_t rows = (int64_t) p.batch * p.n * p.num_heads;
@@ -447,7 +541,9 @@ namespace append_attn
 {
 int launch_append_attn_split(const AppendAttnParams& p, const AppendSplitPlan& plan, hipStream_t stream)
 {
-    return p.head_size == 64 ? launch_split_dh<64>(p, plan, stream) : launch_split_dh<128>(p, plan, stream);
+    if (p.block_pointers) // the paged instances (the table has been checked by launch_append_attention)
+        return p.head_size == 64 ? launch_split_dh<64, true>(p, plan, stream) : launch_split_dh<128, true>(p, plan, stream);
+    return p.head_size == 64 ? launch_split_dh<64, false>(p, plan, stream) : launch_split_dh<128, false>(p, plan, stream);
 }
 } // namespace append_attn
 

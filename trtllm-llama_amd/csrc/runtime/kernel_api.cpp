@@ -272,6 +272,7 @@ int32_t tllm_attention_append_layout(const tllm_attention_append_params_t* q, in
 // n_per_seq null: tllm_attention_append (q->max_past holds); else tllm_attention_append_ragged (max_end in its place).
 // block_pointers set: tllm_attention_append_paged (q->kv_cache is the pool)
 // split: tllm_attention_append_split (its workspace and chunk; the kernel is APPEND_ATTN_SPLIT whatever q->append_kernel says)
+// both: tllm_attention_append_split_paged
 struct AppendSplitArgs
 {
     int32_t split_chunk;
@@ -375,6 +376,20 @@ int32_t tllm_attention_append_split(const tllm_attention_append_params_t* q, con
 {
     const AppendSplitArgs split{split_chunk, workspace, workspace_bytes};
     return attention_append("tllm_attention_append_split", q, n_per_seq, max_end, stream, nullptr, 0, 0, &split);
+}
+
+int32_t tllm_attention_append_split_paged(const tllm_attention_append_params_t* q, const int64_t* block_pointers,
+    int32_t tokens_per_block, int32_t max_blocks_per_seq, const int32_t* n_per_seq, int32_t max_end, int32_t split_chunk,
+    void* workspace, int64_t workspace_bytes, tllm_stream_t stream)
+{
+    if (!block_pointers)
+    {
+        set_error("tllm_attention_append_split_paged: block_pointers is null");
+        return 1;
+    }
+    const AppendSplitArgs split{split_chunk, workspace, workspace_bytes};
+    return attention_append("tllm_attention_append_split_paged", q, n_per_seq, max_end, stream, block_pointers, tokens_per_block,
+        max_blocks_per_seq, &split);
 }
 
 int32_t tllm_attention_append_split_layout(const tllm_attention_append_params_t* q, int32_t max_keys, int32_t cus, int32_t split_chunk,

@@ -146,7 +146,8 @@ struct tllm_session
     // session refuses them as it always did
     bool paged_append = false;
     // session key append_split (a key of the runtime too): every pass through append_attention() runs the split-KV kernel
-    // (kernels/append_attn_split.hip) whenever Dh is 64 / 128 and the pass's N <= 32, else the rule as before.  The linear cache only
+    // (kernels/append_attn_split.hip) whenever Dh is 64 / 128 and the pass's N <= 32, else the rule as before.  Value 1: the linear cache only;
+    // value 2: the paged cache too (with paged_append), through the kernel's paged instance - tllm_session_create holds the pairing
     bool append_split = false;
     // session key stream_gemm (a key of the runtime), 0 / 1 / 2.  1 (SmoothQuant and weight-only int8 / int4 engines): gemm() sends the
     // projections of 9 <= M <= 64 rows to the weight-streaming kernel (kernels/gemm_stream_sq.hip, gemm_stream_woq.hip) - every pass

@@ -354,6 +354,7 @@ int tllm_session::append_attention(const Layer& L, int n, int max_past, hipStrea
     a.out = ctx;
     if (append_split_ws && n <= 32) // session key append_split (Dh 64 / 128: the workspace exists), a pass the kernel serves
     {
+        // (a paged session - append_split = 2 - hands pool and table on as set above: the launcher picks the paged instance)
         a.kernel = APPEND_ATTN_SPLIT;
         a.workspace = append_split_ws;
         a.workspace_bytes = append_split_ws_bytes;

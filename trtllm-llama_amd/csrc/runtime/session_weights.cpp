@@ -189,11 +189,18 @@ tllm_session_t tllm_session_create(const char* config_text)
         set_error("tllm_session_create: paged_append = 1 needs paged_kv_cache = 1 (the append passes of a linear cache need no key)");
         return nullptr;
     }
-    s->append_split = geti("append_split", 0) != 0;
-    if (s->append_split && s->paged_kv)
+    const int append_split_cfg = geti("append_split", 0);
+    s->append_split = append_split_cfg != 0;
+    if (s->append_split && s->paged_kv && append_split_cfg != 2)
     {
-        set_error("tllm_session_create: append_split = 1 does not go with paged_kv_cache = 1 (the split-KV append attention serves "
-                  "the linear cache only)");
+        set_error("tllm_session_create: append_split = 1 does not go with paged_kv_cache = 1 (it is the key of the linear cache; "
+                  "append_split = 2, together with paged_append = 1, serves the paged cache)");
+        return nullptr;
+    }
+    if (append_split_cfg == 2 && s->paged_kv && !s->paged_append)
+    {
+        set_error("tllm_session_create: append_split = 2 on paged_kv_cache = 1 needs paged_append = 1 (the split-KV kernel serves "
+                  "the append passes, which a paged session runs with that key only)");
         return nullptr;
     }
     s->stream_gemm = geti("stream_gemm", 0);

@@ -51,7 +51,8 @@ def parse_arguments(args=None):
                    '--random_seed: a draft is kept where it equals the token the sampler draws (the same tokens as without lookup).')
     p.add_argument('--append_split_kv', action='store_true',
                    help='run the append / verify passes of N <= 32 ids on the split-KV attention kernel (session key append_split; '
-                   'head sizes 64 / 128, the linear cache)')
+                   'head sizes 64 / 128; value 1 on a linear engine, value 2 - the kernel\'s paged instance - on an engine built '
+                   'with --paged_kv_cache)')
     p.add_argument('--stream_gemm', action='store_true',
                    help='SmoothQuant and weight-only int8 / int4 engines: run the projections of 9 to 64 rows (append / verify passes, '
                    'short prompts) on the weight-streaming GEMM (session key stream_gemm = 1)')

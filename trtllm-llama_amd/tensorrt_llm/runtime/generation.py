@@ -76,15 +76,15 @@ class GenerationSession(object):
     def _runtime_keys(model_config: ModelConfig, append_split=False, stream_gemm=False) -> dict:
         """Session keys that belong to the runtime and not to the engine header.  paged_append: a paged engine serves append(),
         verify() and decode_lookup() on its block table (the key is refused on a linear cache, so only a paged engine gets it).
-        append_split: those passes run the split-KV attention kernel at N <= 32 ids (the linear cache only: the session refuses
-        the key on a paged engine by name).  stream_gemm: the projections of 9 .. 64 rows - the same passes, and short prompts -
+        append_split: those passes run the split-KV attention kernel at N <= 32 ids - value 1 on a linear engine, value 2 (the
+        kernel's paged instance, next to paged_append) on a paged engine.  stream_gemm: the projections of 9 .. 64 rows - the same passes, and short prompts -
         run the weight-streaming GEMM: SmoothQuant engines with the same bits, weight-only int8 / int4 engines (LoRA sessions
         included) within the weight-only kernels' bound (the session refuses value 1 on an fp16 engine by name).  stream_gemm=2
         (True means 1): every engine - the same, and fp16 weights on the fp16 stream: an fp16 engine's projections and the
         lm_head of verify passes, within the fp16 kernels' bound."""
         keys = dict(paged_append=1) if model_config.paged_kv_cache else {}
         if append_split:
-            keys['append_split'] = 1
+            keys['append_split'] = 2 if model_config.paged_kv_cache else 1
         if stream_gemm:
             keys['stream_gemm'] = int(stream_gemm)
         return keys

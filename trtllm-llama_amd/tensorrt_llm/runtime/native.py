@@ -120,6 +120,9 @@ def _lib():
     lib.tllm_attention_append_split.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p, c.c_int32, c.c_int32, c.c_void_p,
                                                 c.c_int64, c.c_void_p]
     lib.tllm_attention_append_split.restype = c.c_int32
+    lib.tllm_attention_append_split_paged.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_void_p, c.c_int32, c.c_int32, c.c_void_p,
+                                                      c.c_int32, c.c_int32, c.c_void_p, c.c_int64, c.c_void_p]
+    lib.tllm_attention_append_split_paged.restype = c.c_int32
     lib.tllm_attention_append_split_layout.argtypes = [c.POINTER(AttentionAppendParamsC), c.c_int32, c.c_int32, c.c_int32,
                                                        c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(c.c_int64)]
     lib.tllm_attention_append_split_layout.restype = c.c_int32
@@ -381,6 +384,48 @@ def attention_append_paged(qkv, pool, block_pointers, out, sequence_length, inpu
     _check(_lib().tllm_attention_append_paged(ctypes.byref(p), block_pointers.data_ptr(), int(tokens_per_block),
                                               int(block_pointers.shape[2]), ptr(n_per_seq), int(max_end or 0), stream),
            'attention_append_paged')
+
+
+def attention_append_split_paged(qkv, pool, block_pointers, out, sequence_length, input_lengths, *, tokens_per_block, max_seq_len,
+                                 num_heads, num_kv_heads=0, head_size, max_input_len, max_past=None, masked_tokens=None,
+                                 kv_cache_type=0, kv_scale_orig_quant=None, kv_scale_quant_orig=None, rotary_dim=None, neox=1,
+                                 q_scaling=1.0, n_per_seq=None, max_end=None, split_chunk=0, workspace=None, stream: int = 0):
+    """tllm_attention_append_split_paged: attention_append_paged with the split-KV attention kernel - pool, block_pointers (None:
+    the entry's refusal) and max_seq_len as attention_append_paged takes them, split_chunk and workspace as attention_append_split
+    takes them (None: allocated for the current device's plan).  Bit for bit attention_append_split on the same logical cache."""
+    import torch
+    B, n = qkv.shape[0], qkv.shape[1]
+    if (n_per_seq is None) != (max_end is None):
+        raise ValueError('n_per_seq and max_end go together')
+    if n_per_seq is None and max_past is None:
+        raise ValueError('max_past must be given (or n_per_seq with max_end)')
+    for t in (qkv, pool, block_pointers, out, sequence_length, input_lengths, masked_tokens, kv_scale_orig_quant,
+              kv_scale_quant_orig, n_per_seq, workspace):
+        assert t is None or (t.is_cuda and t.is_contiguous())
+    assert block_pointers is None or (str(block_pointers.dtype) == 'torch.int64' and block_pointers.dim() == 3
+                                      and tuple(block_pointers.shape[:2]) == (B, 2)), \
+        'block_pointers must be int64 [B, 2, max_blocks_per_seq]'
+    if workspace is None:
+        cus = torch.cuda.get_device_properties(qkv.device).multi_processor_count
+        nbytes = attention_append_split_layout(n, head_size, batch=B, num_heads=num_heads, num_kv_heads=num_kv_heads,
+                                               max_keys=int(max_past if n_per_seq is None else max_end), cus=cus,
+                                               split_chunk=split_chunk)[2]
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    p = AttentionAppendParamsC(batch=B, n=n, num_heads=num_heads, num_kv_heads=num_kv_heads, head_size=head_size,
+                               rotary_dim=head_size if rotary_dim is None else rotary_dim, neox=neox, q_scaling=q_scaling,
+                               kv_cache_type=kv_cache_type, max_seq_len=int(max_seq_len), max_input_len=max_input_len,
+                               max_past=max_past or 0, qkv=ptr(qkv), kv_cache=ptr(pool),
+                               sequence_length=ptr(sequence_length), input_lengths=ptr(input_lengths),
+                               masked_tokens=ptr(masked_tokens), kv_scale_orig_quant=ptr(kv_scale_orig_quant),
+                               kv_scale_quant_orig=ptr(kv_scale_quant_orig), out=ptr(out))
+    if n_per_seq is not None:
+        assert str(n_per_seq.dtype) == 'torch.int32' and tuple(n_per_seq.shape) == (B, ), 'n_per_seq must be int32 [B]'
+    _check(_lib().tllm_attention_append_split_paged(ctypes.byref(p), ptr(block_pointers), int(tokens_per_block),
+                                                    0 if block_pointers is None else int(block_pointers.shape[2]), ptr(n_per_seq),
+                                                    int(max_end or 0), int(split_chunk), workspace.data_ptr() or None,
+                                                    workspace.numel() * workspace.element_size(), stream),
+           'attention_append_split_paged')
 
 
 def _sampling_config(top_k=1, top_p=0.0, temperature=1.0, repetition_penalty=1.0, presence_penalty=0.0, min_length=1,
@@ -746,6 +791,7 @@ class NativeSession:
     attention_append = staticmethod(attention_append)
     attention_append_split = staticmethod(attention_append_split)
     attention_append_paged = staticmethod(attention_append_paged)
+    attention_append_split_paged = staticmethod(attention_append_split_paged)
     spec_accept = staticmethod(spec_accept)
     prompt_lookup = staticmethod(prompt_lookup)
     spec_sample_rows = staticmethod(spec_sample_rows)
