@@ -256,6 +256,10 @@ int32_t tllm_session_append_split_launches(tllm_session_t s, int64_t* count);
 /* GEMM calls the session key stream_gemm has sent to a weight-streaming kernel (tllm_gemm_stream; under value 2 tllm_gemm_stream_f16
  * too, one per fp16 projection and one per lm_head call it served) since setup.  0 for a session without the key. */
 int32_t tllm_session_stream_gemm_launches(tllm_session_t s, int64_t* count);
+/* Decode attention launches the session key gqa_mfma_decode (a key of the runtime: grouped K/V heads, head size 64 / 128, linear
+ * cache, beam width 1) has sent to the grouped MFMA kernel in place of the head-mapped one since setup: one per layer and
+ * generation step, eager or captured (a replayed graph counts the launches it holds).  0 for a session without the key. */
+int32_t tllm_session_grouped_decode_launches(tllm_session_t s, int64_t* count);
 
 /* Speculative greedy decoding (the rules are stated in csrc/kernels/kernels.h, SpecAcceptParams and
  * PromptLookupParams, and restated in numpy in tensorrt_llm/runtime/spec_ref.py).  Opt-in: tllm_session_generate, the step graph
@@ -803,6 +807,13 @@ int32_t tllm_attention_context(const tllm_attention_params_t* p, tllm_stream_t s
  * query tile, and whether the splits are merged inside the launch (1) or by the combine launch (0).  Non-zero: p is refused. */
 int32_t tllm_attention_decode_layout(const tllm_attention_params_t* p, int32_t* tchunk, int32_t* nsplit, int32_t* q_tile,
     int32_t* in_launch_merge);
+/* tllm_attention_decode for grouped K/V heads on the matrix pipe (csrc/kernels/mmha_gqa_mfma.hip): the query heads of a K/V head
+ * are the columns of an MFMA tile, so a cache row is requested once per K/V head (once per 16 query heads) instead of once per
+ * query head.  Same struct, same workspace, same split geometry (rows_per_group, combine_launch, tllm_attention_decode_layout),
+ * same rule - only the order of the fp32 sums differs; q_heads_per_workgroup is not read.  Refused by name, nothing launched and
+ * nothing written: num_kv_heads == num_heads, more than 16 query heads per K/V head unless a multiple of 16, a head_size other
+ * than 64 / 128, beam_width > 1, block_pointers (the paged cache). */
+int32_t tllm_attention_decode_grouped(const tllm_attention_params_t* p, tllm_stream_t stream);
 /* the attention kernel tllm_attention_context would run for p (batch, seq, num_heads, head_size, q_scaling, context_kernel and
  * whether workspace is NULL are read; no pointer is followed) on a device of `cus` compute units: its kind (TLLM_CTX_ATTN_*), the
  * queries per workgroup, the operand stages in LDS (0 for the wave-per-query kernel) and the workgroups of the launch.  cus 0 = the

@@ -231,6 +231,19 @@ MmhaPlan mmha_plan(int32_t head_size, int32_t max_seq_len, int32_t batch, int32_
 // session zeroes its workspace at setup and with every prompt instead.
 int mmha_bind_workspace(MmhaParams& p, const MmhaPlan& plan, void* workspace, bool reset_tickets, hipStream_t stream);
 int launch_mmha(const MmhaParams& p, hipStream_t stream);
+// What launch_mmha checks before it picks an instance, for the launchers that share its rule: the RoPE table, the cache element
+// type, the time step and the paged / beam arguments of p (grouping resolved), and p against the plan of its rows_per_group.
+// Non-zero: refused, error set.
+int mmha_check_launch(const MmhaParams& p);
+int mmha_check_plan(const MmhaParams& p, const MmhaPlan& plan);
+// the combine launch behind a partial launch without tickets (head sizes 64 / 128 outside launch_mmha)
+int launch_mmha_combine(const MmhaParams& p, const MmhaPlan& plan, hipStream_t stream);
+// Decode attention for grouped K/V heads with the query heads of a K/V head as MFMA columns (kernels/mmha_gqa_mfma.hip): p, plan,
+// workspace and merge as launch_mmha takes them (q_heads_per_workgroup is not read).  mmha_grouped_refusal: why a shape is not
+// served (null: served) - one query head per K/V head, more than 16 unless a multiple of 16, head sizes other than 64 / 128, a
+// beam, the paged cache; launch_mmha_grouped refuses those by name with nothing launched.
+const char* mmha_grouped_refusal(int32_t num_heads, int32_t num_kv_heads, int32_t head_size, int32_t beam_width, bool paged);
+int launch_mmha_grouped(const MmhaParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // Decode step, batch 1: the QKV projection (SmoothQuant int8, RMSNorm + quantiser prologue) of head h, RoPE, the cache append

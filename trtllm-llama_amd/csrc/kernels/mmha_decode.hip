@@ -36,6 +36,7 @@
 #include <type_traits>
 #include "kernels.h"
 #include "launch_util.h"
+#include "mmha_common.h"
 #include <math.h>
 
 namespace tllm
@@ -235,36 +236,9 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
         for (int i = 0; i < NIT; ++i)
             mk[i] = mask[min(t0 + i * NGRP + gid, Smax - 1)];
     }
-    // RoPE coefficients (cos, sin) of this lane's 8 elements: one row of the table, as 16-byte loads.
-    // NeoX pairs (d, d + rot/2) share coefficient d mod rot/2; GPT-J pairs (2i, 2i+1) share coefficient i.
-    float4 c4[4] = {make_float4(1.f, 0.f, 1.f, 0.f), make_float4(1.f, 0.f, 1.f, 0.f), make_float4(1.f, 0.f, 1.f, 0.f),
-        make_float4(1.f, 0.f, 1.f, 0.f)};
-    if (p.rotary_dim > 0) // uniform
-    {
-        const int half = p.rotary_dim >> 1;
-        const float2* row;
-        if (p.rope_row) // uniform: prepared by the sampler for this step
-            row = reinterpret_cast<const float2*>(p.rope_row) + (int64_t) b * half;
-        else
-        {
-            const int ts = p.timestep_host >= 0 ? p.timestep_host : tl;
-            int pos = ts - (p.max_input_len - p.input_lengths[b]);
-            pos = pos < 0 ? 0 : (pos >= p.rope_table_len ? p.rope_table_len - 1 : pos);
-            row = reinterpret_cast<const float2*>(p.rope_table) + (int64_t) pos * half;
-        }
-        const int d0 = li * 8;
-        int idx0 = p.neox ? (d0 >= half ? d0 - half : d0) : (d0 >> 1);
-        const int span = p.neox ? 8 : 4;
-        idx0 = idx0 + span <= half ? idx0 : (half >= span ? half - span : 0);
-        const float4* r4 = reinterpret_cast<const float4*>(row + idx0);
-        c4[0] = r4[0];
-        c4[1] = r4[1];
-        if (p.neox)
-        {
-            c4[2] = r4[2];
-            c4[3] = r4[3];
-        }
-    }
+    // RoPE coefficients (cos, sin) of this lane's 8 elements: one row of the table, as 16-byte loads (mmha_common.h)
+    float4 c4[4];
+    mmha::rope_coeffs(p, b, tl, li * 8, c4);
     // splits that hold at least one used slot (or the slot the new token goes to): ONE expression for the early return here and
     // for the ticket count of the merge below - a split that returns never takes a ticket, and the last ticket is nact - 1
     const int nact = min(tl / G::TCHUNK + 1, nsplit_max);
@@ -273,41 +247,7 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     // RoPE of one row (q of a head of the tile, or the new k - once per K/V head), fp32 -> fp16
     const float cs[16] = {c4[0].x, c4[0].y, c4[0].z, c4[0].w, c4[1].x, c4[1].y, c4[1].z, c4[1].w,
         c4[2].x, c4[2].y, c4[2].z, c4[2].w, c4[3].x, c4[3].y, c4[3].z, c4[3].w};
-    auto rope_row = [&](const uint4& raw) -> uint4 {
-        float xf[8];
-        h8_to_f(raw, xf);
-        if (p.rotary_dim > 0)
-        {
-            if (p.neox)
-            {
-                // pair (j, j + rot/2); rot == DH: the partner sits in lane li ^ (LPR/2)
-                const bool second = li >= LPR / 2;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                {
-                    const float xp = __shfl_xor(xf[j], LPR / 2, 64);
-                    // first half:  x' = x cos - y sin ; second half: y' = y cos + x sin
-                    // fp16 rounding of the rotated value (...Utils.h:1517-1531)
-                    const float c = cs[2 * j], sn = second ? cs[2 * j + 1] : -cs[2 * j + 1];
-                    xf[j] = h2f(f2h(c * xf[j] + sn * xp));
-                }
-            }
-            else
-            {
-                // GPT-J style: pair (2i, 2i+1), both in this lane
-#pragma unroll
-                for (int j = 0; j < 8; j += 2)
-                {
-                    const float c = (li * 8 + j < p.rotary_dim) ? cs[j] : 1.f;
-                    const float sn = (li * 8 + j < p.rotary_dim) ? cs[j + 1] : 0.f;
-                    const float x0 = xf[j], x1 = xf[j + 1];
-                    xf[j] = h2f(f2h(c * x0 - sn * x1));
-                    xf[j + 1] = h2f(f2h(c * x1 + sn * x0));
-                }
-            }
-        }
-        return f_to_h8(xf);
-    };
+    auto rope_row = [&](const uint4& raw) -> uint4 { return mmha::rope_row8<LPR>(raw, cs, p.rotary_dim, p.neox, li); };
     uint4 q16s[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt)
@@ -536,51 +476,7 @@ __global__ __launch_bounds__(256) void mmha_partial_kernel(const MmhaParams p, f
     //         (vmcnt(0) in asm: the compiler may drop its own wait), workgroup barrier, relaxed agent-scope ticket; the consumer reads
     //         the payload with agent-scope (L1-bypassing) loads behind the ticket it took.  The ticket word re-arms itself for the
     //         next launch; the session also zeroes it whenever a prompt is loaded (a launch that died mid-way must not poison the next).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    __shared__ uint32_t sm_ticket;
-    if (tid == 0)
-        sm_ticket = __hip_atomic_fetch_add(p.tail_tickets + b * H + h0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if ((int) sm_ticket != nact - 1)
-        return;
-    if (tid == 0) // re-arm for the next launch (ordered by the kernel boundary)
-        __hip_atomic_store(p.tail_tickets + b * H + h0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int e = tid; e < QT * DH; e += 256)
-    {
-        const int h = h0 + e / DH, d = e % DH;
-        const int64_t base = ((int64_t) b * H + h) * nsplit_max;
-        // the arithmetic of the O-projection's merge prologue (gemv_impl.h PK_ATTN), slot order, fp32: bit-identical results.
-        // Up to kTailSlots partials (the prologue form stops at 8: there every slot costs each of ~500 workgroups a load)
-        float ms[kTailSlots], ls[kTailSlots], os[kTailSlots];
-#pragma unroll
-        for (int i = 0; i < kTailSlots; ++i)
-        {
-            const int ic = i < nact ? i : 0;
-            const uint64_t mlb = __hip_atomic_load(reinterpret_cast<const uint64_t*>(ws_ml + base + ic), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ms[i] = __uint_as_float((uint32_t) mlb);
-            ls[i] = __uint_as_float((uint32_t) (mlb >> 32));
-            os[i] = __hip_atomic_load(ws_o + (base + ic) * DH + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        float Mx = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < kTailSlots; ++i)
-            Mx = i < nact ? fmaxf(Mx, ms[i]) : Mx;
-        float Lt = 0.f, Ot = 0.f;
-#pragma unroll
-        for (int i = 0; i < kTailSlots; ++i)
-        {
-            const bool act = i < nact && ms[i] != -INFINITY;
-            const float e = act ? __expf(ms[i] - Mx) : 0.f;
-            Lt += act ? ls[i] * e : 0.f;
-            Ot += act ? os[i] * e : 0.f;
-        }
-        const uint16_t h16 = f2h(Ot * (1.f / (Lt + 1.e-6f)));
-        const int64_t o = ((int64_t) b * H + h) * DH + d;
-        reinterpret_cast<uint16_t*>(p.out)[o] = h16;
-        if (p.tail_out_q8)
-            reinterpret_cast<int8_t*>(p.tail_out_q8)[o] = f2i8_rni_sat(h2f(h16) * p.tail_quant_scale[0]);
-    }
+    mmha::tail_merge<DH>(p, ws_ml, ws_o, nsplit_max, p.tail_tickets + b * H + h0, b, h0, QT, nact);
 }
 
 // ---- kernel 2: merge the splits of every (batch, head): 256 threads = (d, part), all loads independent
@@ -690,6 +586,28 @@ template <int DH>
 int launch_dh(const MmhaParams& p, hipStream_t stream)
 {
     const MmhaPlan plan = mmha_plan(DH, p.max_seq_len, p.batch, p.num_heads, p.rows_per_group);
+    if (mmha_check_plan(p, plan))
+        return -1;
+    switch (plan.rows_per_group)
+    {
+    case 16: return launch_nit<DH, 16>(p, plan, stream);
+    case 12: return launch_nit<DH, 12>(p, plan, stream);
+    default: return launch_nit<DH, 4>(p, plan, stream);
+    }
+}
+
+// the merge tickets of a workspace to zero: a kernel, so that an entry point that resets them per call can be captured in a graph
+__global__ void mmha_clear_tickets_kernel(uint32_t* tickets, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n)
+        tickets[i] = 0u;
+}
+
+} // namespace
+
+int mmha_check_plan(const MmhaParams& p, const MmhaPlan& plan)
+{
     if (p.rows_per_group == 0 || plan.rows_per_group != p.rows_per_group)
     {
         set_error("mmha: rows_per_group %d is not 4, 12 or 16 (0 is resolved by mmha_plan, before the launch)", p.rows_per_group);
@@ -705,15 +623,41 @@ int launch_dh(const MmhaParams& p, hipStream_t stream)
         set_error("mmha: the in-launch merge takes at most %d splits (got %d) and a scale with its int8 output", kTailSlots, plan.nsplit);
         return -1;
     }
-    switch (plan.rows_per_group)
-    {
-    case 16: return launch_nit<DH, 16>(p, plan, stream);
-    case 12: return launch_nit<DH, 12>(p, plan, stream);
-    default: return launch_nit<DH, 4>(p, plan, stream);
-    }
+    return 0;
 }
 
-} // namespace
+int launch_mmha_combine(const MmhaParams& p, const MmhaPlan& plan, hipStream_t stream)
+{
+    const float2* ws_ml = reinterpret_cast<const float2*>(p.workspace);
+    const float* ws_o = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.workspace) + plan.ml_bytes);
+    const dim3 grid(p.num_heads, p.batch);
+#define TLLM_MMHA_COMBINE(DH, NIT) hipLaunchKernelGGL((mmha_combine_kernel<DH, NIT>), grid, dim3(256), 0, stream, p, ws_ml, ws_o, plan.nsplit)
+    if (p.head_size == 64)
+    {
+        if (plan.rows_per_group == 16)
+            TLLM_MMHA_COMBINE(64, 16);
+        else if (plan.rows_per_group == 12)
+            TLLM_MMHA_COMBINE(64, 12);
+        else
+            TLLM_MMHA_COMBINE(64, 4);
+    }
+    else if (p.head_size == 128)
+    {
+        if (plan.rows_per_group == 16)
+            TLLM_MMHA_COMBINE(128, 16);
+        else if (plan.rows_per_group == 12)
+            TLLM_MMHA_COMBINE(128, 12);
+        else
+            TLLM_MMHA_COMBINE(128, 4);
+    }
+    else
+    {
+        set_error("mmha: the combine launch outside launch_mmha serves head sizes 64 and 128 (got %d)", p.head_size);
+        return -1;
+    }
+#undef TLLM_MMHA_COMBINE
+    return launch_util::check_launch("mmha (combine)");
+}
 
 MmhaPlan mmha_plan(int32_t head_size, int32_t max_seq_len, int32_t batch, int32_t num_heads, int32_t rows_per_group, bool force_combine)
 {
@@ -742,11 +686,11 @@ int mmha_bind_workspace(MmhaParams& p, const MmhaPlan& plan, void* workspace, bo
     p.rows_per_group = plan.rows_per_group;
     p.tail_tickets = plan.in_launch_merge ? static_cast<uint32_t*>(workspace) : nullptr;
     p.workspace = static_cast<char*>(workspace) + plan.ticket_bytes;
-    if (reset_tickets && p.tail_tickets
-        && hipMemsetAsync(workspace, 0, (size_t) p.batch * p.num_heads * sizeof(uint32_t), stream) != hipSuccess)
+    if (reset_tickets && p.tail_tickets)
     {
-        set_error("mmha: hipMemsetAsync(tickets) failed");
-        return -1;
+        const int n = p.batch * p.num_heads;
+        hipLaunchKernelGGL(mmha_clear_tickets_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, p.tail_tickets, n);
+        return launch_util::check_launch("mmha (ticket reset)");
     }
     return 0;
 }
@@ -807,11 +751,8 @@ int mmha_resolve_grouping(MmhaParams& p)
     return 0;
 }
 
-int launch_mmha(const MmhaParams& pin, hipStream_t stream)
+int mmha_check_launch(const MmhaParams& p)
 {
-    MmhaParams p = pin;
-    if (mmha_resolve_grouping(p))
-        return -1;
     if (p.rotary_dim > 0)
     {
         if (!p.rope_table || p.rope_table_len <= 0)
@@ -848,6 +789,14 @@ int launch_mmha(const MmhaParams& pin, hipStream_t stream)
             return -1;
         }
     }
+    return 0;
+}
+
+int launch_mmha(const MmhaParams& pin, hipStream_t stream)
+{
+    MmhaParams p = pin;
+    if (mmha_resolve_grouping(p) || mmha_check_launch(p))
+        return -1;
     switch (p.head_size)
     {
     case 32: return launch_dh<32>(p, stream);

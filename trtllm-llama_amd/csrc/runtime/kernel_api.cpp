@@ -171,6 +171,35 @@ int32_t tllm_attention_decode(const tllm_attention_params_t* q, tllm_stream_t st
     return launch_mmha(p, st) ? 1 : 0;
 }
 
+int32_t tllm_attention_decode_grouped(const tllm_attention_params_t* q, tllm_stream_t stream)
+{
+    MmhaParams p;
+    MmhaPlan plan;
+    if (attention_decode_params(q, p, plan))
+        return 1;
+    // what the kernel does not serve, before anything is enqueued (the ticket reset included)
+    if (const char* why = mmha_grouped_refusal(p.num_heads, p.num_kv_heads, p.head_size, q->beam_width, q->block_pointers != nullptr))
+    {
+        set_error("tllm_attention_decode_grouped: refused: %s", why);
+        return 1;
+    }
+    if (!q->qkv || !q->out || !q->workspace || !q->sequence_length || !q->input_lengths || !q->kv_cache)
+    {
+        set_error("tllm_attention_decode_grouped: qkv, out, workspace, sequence_length, input_lengths and kv_cache must be set");
+        return 1;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (p.rotary_dim > 0)
+    {
+        p.rope_table = tllm::plugins::rope_table(p.rotary_dim, p.max_seq_len, &p.rope_table_len);
+        if (!p.rope_table)
+            return 1;
+    }
+    if (mmha_bind_workspace(p, plan, q->workspace, true, st)) // the merge tickets are zeroed per call, as tllm_attention_decode does
+        return 1;
+    return launch_mmha_grouped(p, st) ? 1 : 0;
+}
+
 int32_t tllm_attention_context(const tllm_attention_params_t* q, tllm_stream_t stream)
 {
     if (!q || q->batch < 1 || q->seq < 1 || q->num_heads < 1 || !q->qkv || !q->out || !q->input_lengths

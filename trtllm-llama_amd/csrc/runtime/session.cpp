@@ -176,7 +176,10 @@ int32_t tllm_session_step(tllm_session_t s, int32_t n_steps, int32_t use_graph, 
     for (int i = 0; i < n_steps; ++i)
     {
         if (use_graph)
+        {
             HIP_OK(hipGraphLaunch(s->graph, st));
+            s->grouped_decode_launches += s->graph_grouped_launches;
+        }
         else
             RUN(s->run_decode_step(st));
     }
@@ -549,6 +552,17 @@ int32_t tllm_session_append_launches(tllm_session_t s, int64_t* wave, int64_t* m
         *wave = s->append_wave_launches;
     if (mfma)
         *mfma = s->append_mfma_launches;
+    return 0;
+}
+
+int32_t tllm_session_grouped_decode_launches(tllm_session_t s, int64_t* count)
+{
+    if (!s || !s->B || !count)
+    {
+        set_error("tllm_session_grouped_decode_launches: setup not called, or count is null");
+        return 1;
+    }
+    *count = s->grouped_decode_launches;
     return 0;
 }
 

@@ -149,6 +149,12 @@ struct tllm_session
     // (kernels/append_attn_split.hip) whenever Dh is 64 / 128 and the pass's N <= 32, else the rule as before.  Value 1: the linear cache only;
     // value 2: the paged cache too (with paged_append), through the kernel's paged instance - tllm_session_create holds the pairing
     bool append_split = false;
+    // session key gqa_mfma_decode (a key of the runtime): the attention launch of the generation step is the grouped MFMA kernel
+    // (kernels/mmha_gqa_mfma.hip) in place of launch_mmha.  Accepted with grouped K/V heads the kernel serves (num_kv_heads !=
+    // num_heads, head size 64 / 128) on a linear cache - tllm_session_create holds that - and beam width 1 - tllm_session_setup
+    bool gqa_mfma_decode = false;
+    int64_t grouped_decode_launches = 0; // its launches since setup: eager ones as enqueued, a replayed graph's per replay
+    int64_t graph_grouped_launches = 0;  // those the captured step holds
     // session key stream_gemm (a key of the runtime), 0 / 1 / 2.  1 (SmoothQuant and weight-only int8 / int4 engines): gemm() sends the
     // projections of 9 <= M <= 64 rows to the weight-streaming kernel (kernels/gemm_stream_sq.hip, gemm_stream_woq.hip) - every pass
     // through context_layer with that many rows.  The dual SwiGLU GEMM of context_gate_up (static scales, M >= 32) is not a gemm()

@@ -454,6 +454,13 @@ int tllm_session::stage_attention(const DecodeStep& ds, int li)
     }
     m.out = ctx;
     RUN(mmha_bind_workspace(m, attn_plan, mmha_ws, false, st)); // (the tickets: zero since setup / the prompt, re-armed by every launch)
+    if (gqa_mfma_decode) // session key: the query heads of a K/V head as MFMA columns (kernels/mmha_gqa_mfma.hip)
+    {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        (void) hipStreamIsCapturing(st, &cap);
+        ++(cap == hipStreamCaptureStatusActive ? graph_grouped_launches : grouped_decode_launches);
+        return timed(PC_ATTENTION, st, [&] { return launch_mmha_grouped(m, st); });
+    }
     return timed(PC_ATTENTION, st, [&] { return launch_mmha(m, st); });
 }
 

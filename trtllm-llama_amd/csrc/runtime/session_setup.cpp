@@ -15,6 +15,7 @@ void tllm_session::drop_graph()
         (void) hipGraphExecDestroy(graph);
         graph = nullptr;
     }
+    graph_grouped_launches = 0;
 }
 
 void tllm_session::free_runtime()
@@ -109,6 +110,7 @@ int tllm_session::alloc_buffers()
     RUN(dalloc(&in_len_ctx, (size_t) Bc * 4));
     RUN(dalloc(&append_last, (size_t) B * 4));
     append_wave_launches = append_mfma_launches = append_split_launches = 0;
+    grouped_decode_launches = 0;
     append_split_ws = nullptr;
     append_split_ws_bytes = 0;
     if (append_split && (Dh == 64 || Dh == 128))
@@ -433,6 +435,12 @@ int32_t tllm_session_setup_beam(tllm_session_t s, int32_t batch_size, int32_t be
         // the device-side beam step stages the cache-indirection rows it re-parents in LDS (decode_step.hip beam_step_kernel)
         set_error("tllm_session_setup: beam_width %d x max_seq_len %d exceeds the beam step's LDS staging (24576 int32)", beam_width,
             max_input_len + max_new_tokens);
+        return 1;
+    }
+    if (beam_width > 1 && s->gqa_mfma_decode)
+    {
+        set_error("tllm_session_setup: gqa_mfma_decode = 1 with beam_width %d is not built (the grouped MFMA decode attention has no "
+                  "beam instance; beam_width 1 only)", beam_width);
         return 1;
     }
     if (beam_width > 1 && s->lora_rank > 0)

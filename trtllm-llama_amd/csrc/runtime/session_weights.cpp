@@ -203,6 +203,7 @@ tllm_session_t tllm_session_create(const char* config_text)
                   "the append passes, which a paged session runs with that key only)");
         return nullptr;
     }
+    s->gqa_mfma_decode = geti("gqa_mfma_decode", 0) != 0;
     s->stream_gemm = geti("stream_gemm", 0);
     if (s->stream_gemm < 0 || s->stream_gemm > 2)
     {
@@ -249,6 +250,17 @@ tllm_session_t tllm_session_create(const char* config_text)
         return nullptr;
     }
     s->Hkvr = s->num_kv_heads / s->tp;
+    if (s->gqa_mfma_decode)
+    {
+        // (the beam width is a matter of tllm_session_setup)
+        const char* why = mmha_grouped_refusal(s->Hr, s->Hkvr, s->Dh, 1, s->paged_kv);
+        if (why)
+        {
+            set_error("tllm_session_create: gqa_mfma_decode = 1 refused (num_heads %d, num_kv_heads %d, head size %d, paged_kv_cache "
+                      "%d): %s", s->num_heads, s->num_kv_heads, s->Dh, (int) s->paged_kv, why);
+            return nullptr;
+        }
+    }
     s->QKVr = (s->Hr + 2 * s->Hkvr) * s->Dh;
     s->Ir = s->inter / s->tp;
     // vocab padded to a multiple of tp (PY/_utils.py:194-195, Q/llama_model.py:244)
@@ -591,9 +603,9 @@ tllm_session_t tllm_session_load_engine_keys(const void* engine, size_t nbytes, 
                 continue;
             const size_t e = eq == std::string::npos ? std::string::npos : line.find_last_not_of(" \t\r", eq - 1);
             const std::string key = eq == std::string::npos || eq == a ? std::string() : line.substr(a, e - a + 1);
-            if (key != "paged_append" && key != "append_split" && key != "stream_gemm")
+            if (key != "paged_append" && key != "append_split" && key != "stream_gemm" && key != "gqa_mfma_decode")
             {
-                set_error("tllm_session_load_engine_keys: '%s' is not a runtime key (paged_append, append_split, stream_gemm); the engine header holds the rest",
+                set_error("tllm_session_load_engine_keys: '%s' is not a runtime key (paged_append, append_split, stream_gemm, gqa_mfma_decode); the engine header holds the rest",
                     line.c_str());
                 return nullptr;
             }

@@ -59,6 +59,10 @@ def parse_arguments(args=None):
     p.add_argument('--stream_gemm_fp16', action='store_true',
                    help='every engine: what --stream_gemm does, and fp16 weights on the fp16 weight stream - the projections of an '
                    'fp16 engine at 9 to 64 rows and the lm_head of the verify passes (session key stream_gemm = 2)')
+    p.add_argument('--gqa_mfma_decode', action='store_true',
+                   help='engines with grouped K/V heads (num_kv_heads < num_heads, head size 64 / 128, linear cache, one beam): run the '
+                   'attention of the generation step on the grouped MFMA kernel, every cache row read once per K/V head (session key '
+                   'gqa_mfma_decode = 1)')
     # LoRA adapters (an engine built with --lora_max_rank): HF PEFT directories go into slots 0, 1, ... in the order given
     p.add_argument('--lora_dir', type=str, nargs='+', default=None, help='HF PEFT adapter directories (adapter_config.json + '
                    'adapter_model.safetensors)')
@@ -67,7 +71,7 @@ def parse_arguments(args=None):
     return p.parse_args(args)
 
 
-def load_session(engine_dir, append_split=False, stream_gemm=False):
+def load_session(engine_dir, append_split=False, stream_gemm=False, gqa_mfma_decode=False):
     with open(Path(engine_dir) / 'config.json') as f:
         config = json.load(f)
     bc = config['builder_config']
@@ -94,16 +98,18 @@ def load_session(engine_dir, append_split=False, stream_gemm=False):
     path = Path(engine_dir) / get_engine_name('llama', dtype, world_size, runtime_rank)
     with open(path, 'rb') as f:
         engine_buffer = f.read()
-    return GenerationSession(model_config, engine_buffer, mapping, append_split=append_split, stream_gemm=stream_gemm), runtime_rank
+    return GenerationSession(model_config, engine_buffer, mapping, append_split=append_split, stream_gemm=stream_gemm,
+                             gqa_mfma_decode=gqa_mfma_decode), runtime_rank
 
 
 def generate(max_output_len, log_level='error', engine_dir='llama_outputs', input_text=None, input_file=None,
              output_csv=None, output_npy=None, tokenizer_dir=None, num_beams=1, num_runs=55, top_k=1, top_p=0.0,
              temperature=1.0, repetition_penalty=1.0, random_seed=None, prompt_lookup_tokens=0, prompt_lookup_ngram=3,
              prompt_lookup_sampling=False, lora_dir=None, lora_slots=None, append_split_kv=False, stream_gemm=False,
-             stream_gemm_fp16=False):
+             stream_gemm_fp16=False, gqa_mfma_decode=False):
     tensorrt_llm.logger.set_level(log_level)
-    decoder, runtime_rank = load_session(engine_dir, append_split=append_split_kv, stream_gemm=2 if stream_gemm_fp16 else stream_gemm)
+    decoder, runtime_rank = load_session(engine_dir, append_split=append_split_kv, stream_gemm=2 if stream_gemm_fp16 else stream_gemm,
+                                         gqa_mfma_decode=gqa_mfma_decode)
     for slot, d in enumerate(lora_dir or []):
         decoder.load_lora(d, slot)
     if isinstance(lora_slots, str):

@@ -158,6 +158,8 @@ def load_library():
     lib.tllm_attention_workspace_size.restype = c.c_size_t
     lib.tllm_attention_decode.argtypes = [c.POINTER(AttentionParams), c.c_void_p]
     lib.tllm_attention_decode.restype = c.c_int32
+    lib.tllm_attention_decode_grouped.argtypes = [c.POINTER(AttentionParams), c.c_void_p]
+    lib.tllm_attention_decode_grouped.restype = c.c_int32
     lib.tllm_attention_context.argtypes = [c.POINTER(AttentionParams), c.c_void_p]
     lib.tllm_attention_context.restype = c.c_int32
     lib.tllm_attention_decode_layout.argtypes = [c.POINTER(AttentionParams)] + [c.POINTER(c.c_int32)] * 4

@@ -56,7 +56,7 @@ class SamplingConfig:
 class GenerationSession(object):
 
     def __init__(self, model_config: ModelConfig, engine_buffer, mapping: Mapping, debug_mode=False, append_split=False,
-                 stream_gemm=False):
+                 stream_gemm=False, gqa_mfma_decode=False):
         assert isinstance(model_config, ModelConfig)
         if not model_config.gpt_attention_plugin:
             raise ValueError('the MI355X LLaMA path needs the gpt_attention plugin (RoPE lives in it)')
@@ -68,12 +68,12 @@ class GenerationSession(object):
         if mapping.tp_size > 1:
             from ..parallel import ensure_tp_communicator
             ensure_tp_communicator(mapping)
-        self.runtime = NativeSession(engine=bytes(engine_buffer), runtime_keys=self._runtime_keys(model_config, append_split, stream_gemm))
+        self.runtime = NativeSession(engine=bytes(engine_buffer), runtime_keys=self._runtime_keys(model_config, append_split, stream_gemm, gqa_mfma_decode))
         self.runtime.vocab = model_config.vocab_size
         self.batch_size = self.max_input_length = self.max_new_tokens = 0
 
     @staticmethod
-    def _runtime_keys(model_config: ModelConfig, append_split=False, stream_gemm=False) -> dict:
+    def _runtime_keys(model_config: ModelConfig, append_split=False, stream_gemm=False, gqa_mfma_decode=False) -> dict:
         """Session keys that belong to the runtime and not to the engine header.  paged_append: a paged engine serves append(),
         verify() and decode_lookup() on its block table (the key is refused on a linear cache, so only a paged engine gets it).
         append_split: those passes run the split-KV attention kernel at N <= 32 ids - value 1 on a linear engine, value 2 (the
@@ -81,12 +81,16 @@ class GenerationSession(object):
         run the weight-streaming GEMM: SmoothQuant engines with the same bits, weight-only int8 / int4 engines (LoRA sessions
         included) within the weight-only kernels' bound (the session refuses value 1 on an fp16 engine by name).  stream_gemm=2
         (True means 1): every engine - the same, and fp16 weights on the fp16 stream: an fp16 engine's projections and the
-        lm_head of verify passes, within the fp16 kernels' bound."""
+        lm_head of verify passes, within the fp16 kernels' bound.  gqa_mfma_decode: the generation step of an engine with grouped
+        K/V heads runs its attention on the grouped MFMA kernel (head size 64 / 128, linear cache, beam width 1; the session
+        refuses the key by name anywhere else)."""
         keys = dict(paged_append=1) if model_config.paged_kv_cache else {}
         if append_split:
             keys['append_split'] = 2 if model_config.paged_kv_cache else 1
         if stream_gemm:
             keys['stream_gemm'] = int(stream_gemm)
+        if gqa_mfma_decode:
+            keys['gqa_mfma_decode'] = 1
         return keys
 
     @property

@@ -130,6 +130,8 @@ def _lib():
     lib.tllm_session_append_split_launches.restype = c.c_int32
     lib.tllm_session_stream_gemm_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
     lib.tllm_session_stream_gemm_launches.restype = c.c_int32
+    lib.tllm_session_grouped_decode_launches.argtypes = [c.c_void_p, c.POINTER(c.c_int64)]
+    lib.tllm_session_grouped_decode_launches.restype = c.c_int32
     lib.tllm_session_verify.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p, c.c_void_p, c.c_void_p]
     lib.tllm_session_verify.restype = c.c_int32
     lib.tllm_session_verify_top1.argtypes = [c.c_void_p, c.c_void_p, c.c_int32, c.c_void_p]
@@ -518,7 +520,7 @@ class NativeSession:
 
     def __init__(self, config: Optional[Dict] = None, engine: Optional[bytes] = None, runtime_keys: Optional[Dict] = None):
         """config: the session keys; or engine: a serialized engine, whose header holds them - then runtime_keys adds the keys
-        that belong to the runtime and not to the engine (paged_append, append_split, stream_gemm; tllm_session_load_engine_keys
+        that belong to the runtime and not to the engine (paged_append, append_split, stream_gemm, gqa_mfma_decode; tllm_session_load_engine_keys
         refuses every other)."""
         lib = _lib()
         self._keep = []  # torch tensors whose device memory the session references
@@ -786,6 +788,13 @@ class NativeSession:
         weight-only projections, and under value 2 fp16 projections and every lm_head call the fp16 stream served)"""
         n = ctypes.c_int64()
         _check(_lib().tllm_session_stream_gemm_launches(self._h, ctypes.byref(n)), 'stream_gemm_launches')
+        return int(n.value)
+
+    def grouped_decode_launches(self):
+        """decode attention launches the session key gqa_mfma_decode has sent to the grouped MFMA kernel since setup (one per layer
+        and generation step, eager or replayed)"""
+        n = ctypes.c_int64()
+        _check(_lib().tllm_session_grouped_decode_launches(self._h, ctypes.byref(n)), 'grouped_decode_launches')
         return int(n.value)
 
     attention_append = staticmethod(attention_append)
